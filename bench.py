@@ -2,6 +2,19 @@
 """Benchmark: Msamples/s of the path-tracing hot path (BASELINE.json metric), Cornell box.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5|...]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps,
+writes its outputs when --dump-outputs is given and prints the result line.  Everything that
+takes runs of its own -- the isolated-launch pass (roofline.per_launch), the interactive pass
+in the reference's loop shape (vs_baseline), the one-GPU render of the same frame at N > 1 and
+the CPU baseline -- runs only with --full; without it those fields of the line are null.
+
+--dump-outputs DIR writes what the timed path computed in its last step: the last timed
+frame, as its caller receives it (RGBA8, here as float32 0..255), to DIR/frame_rgba.npy; a
+frame above 2 Mpixel as a fixed, seeded sample of its pixels, with DIR/frame_pixel_index.npy
+naming them.  Scene, camera and the frames' time seeds depend on the arguments alone, so two
+builds run with the same arguments can be compared output for output.
 
 `--gpus N` (N > 1) without a launcher starts its N ranks itself (torch.distributed.run on
 127.0.0.1, see self_launch); under torch.distributed.run it is one rank.
@@ -36,7 +49,8 @@ Workloads (per BASELINE.json configs; the N=1 default is the headline C3):
       no exact-zero triangle component is left for the scene-specialised scan to drop.
   c3gen: the C3 frame with the generic scan (rvcp_config_t.specialize = OFF).
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the path-tracing kernel,
+Rank 0 prints ONE JSON line; `ms_per_step` is the wall time of the timed region over its K
+steps, in milliseconds.  `roofline` is for the dominant kernel (the path-tracing kernel,
 >99% of the frame's GPU time), whose bound is FP32 VALU issue:
   * `achieved` / `frac`: useful FLOP per frame (52 per reference-algorithm ray-triangle test,
     25 per ray-sphere test) / `ms_per_step` (the driver-comparable wall time
@@ -446,8 +460,9 @@ class CallSchedule:
     time (rvcp.h), so call c waits, before its enqueue, for the call its context ran `fif`
     calls earlier.  Frame f of the whole run (warm-up frames first) renders with the time seed
     TIME0 + f.  `run(n)` returns the stats of every call it made, each exactly once, in
-    completion order; `slot_time[i][j]` is the seed of the frame in context i's slot j and
-    `done_t` the (host time, frames) of each completed call of the last run.
+    completion order; `slot_time[i][j]` is the seed of the frame in context i's slot j,
+    `last_slot` the (context, slot) of the last frame enqueued and `done_t` the (host time,
+    frames) of each completed call of the last run.
 
     enqueue(i, pushes, nb) starts a call of nb frames on context i; finish(i, nb) waits for it
     and returns its stats.  Pure host logic: tests/test_bench_cpu.py drives it with a stub."""
@@ -459,6 +474,7 @@ class CallSchedule:
         self.pending = [0] * fif            # frames of the call in flight on each context
         self.frames_run = 0                 # frames enqueued so far (the next frame's index)
         self.slot_time = [[None] * batch for _ in range(fif)]
+        self.last_slot = None               # (context, slot) of the last frame enqueued
         self.done_t = []
 
     def calls(self, n):
@@ -482,10 +498,33 @@ class CallSchedule:
             ts = [TIME0 + float(self.frames_run + j) for j in range(nb)]
             self.frames_run += nb
             self.slot_time[i][:nb] = ts
+            self.last_slot = (i, nb - 1)
             self._enqueue(i, [self._push_of(t) for t in ts], nb)
             self.pending[i] = nb
         stats += [self._finish_ctx(i) for i in range(self.fif) if self.pending[i]]
         return stats
+
+
+# --dump-outputs: whole frames up to this many pixels (32 MiB of float32 RGBA), else a sample
+DUMP_MAX_PIXELS = 2 << 20
+
+
+def dump_outputs(path, rgba):
+    """Write the frame `rgba` (H x W x 4, uint8) under the directory `path` as float32:
+    frame_rgba.npy, the whole frame; above DUMP_MAX_PIXELS pixels a fixed, seeded sample of
+    DUMP_MAX_PIXELS pixels (N x 4) and frame_pixel_index.npy, their row-major indices (float64).
+    Returns the files written."""
+    os.makedirs(path, exist_ok=True)
+    px = rgba.reshape(-1, 4)
+    if len(px) <= DUMP_MAX_PIXELS:
+        arrays = {"frame_rgba": rgba.astype(np.float32)}
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(len(px), DUMP_MAX_PIXELS, replace=False))
+        arrays = {"frame_rgba": px[idx].astype(np.float32),
+                  "frame_pixel_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(name + ".npy" for name in arrays)
 
 
 def report_failure(rank, world, wl, stage, err):
@@ -537,6 +576,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=None, choices=["c1", "c2", "c3", "c4", "c5", "c6", "spheres", "c3m2", "c3rot", "c3gen"],
                     help="default: c3 at N=1 (headline), c4 at N>1 (BASELINE's 8-GPU config)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the timed "
+                         "steps: the isolated-launch pass (--launch-pass), the interactive pass "
+                         "(--interactive-pass), at N>1 rank 0's one-GPU render of the same frame, "
+                         "and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed frame as DIR/frame_rgba.npy (float32; see the "
+                         "module docstring)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="oracle threads for cpu_baseline (default: the CPUs this process is "
@@ -561,23 +608,29 @@ def main():
                          "wait (rvcp_rccl_set_timeout); past it the rank aborts its communicator "
                          "-- at creation every rank then takes the labelled host gather, during "
                          "the run the command exits non-zero with a line naming rank and stage")
-    ap.add_argument("--interactive-pass", type=int, default=60,
-                    help="N=1: frames of the post-timing pass in the reference's own loop shape "
+    ap.add_argument("--interactive-pass", type=int, default=None,
+                    help="with --full at N=1: frames of the post-timing pass in the reference's loop shape "
                          "(one frame per launch, one in flight per swapchain image -- at most 3, "
                          "vulkan.rs:213 -- each frame's push made just before its submission: "
                          "ray_tracer.rs:80-98, vulkan.rs:367-369) -> "
-                         "config.interactive_ms_per_step (0 = skip)")
+                         "config.interactive_ms_per_step (default 60; 0 = skip)")
     ap.add_argument("--interactive-frames-in-flight", type=int, default=0,
                     help="the interactive pass's frames in flight (1-3; 0 = auto_pipeline's "
                          "single-frame choice); for A/Bs")
     ap.add_argument("--interactive-grid-waves", type=int, default=-1,
                     help="the interactive pass's grid per frame in waves per SIMD (0 = every "
                          "resident slot; -1 = auto_pipeline's single-frame choice); for A/Bs")
-    ap.add_argument("--launch-pass", type=int, default=10,
-                    help="frames (at most --steps) of the post-timing one-frame-in-flight pass "
+    ap.add_argument("--launch-pass", type=int, default=None,
+                    help="with --full: frames (at most --steps) of the post-timing one-frame-in-flight "
+                         "pass "
                          "that measures the path kernel's isolated launch time "
-                         "(roofline.per_launch; 0 = skip)")
+                         "(roofline.per_launch; default 10; 0 = skip)")
     args = ap.parse_args()
+    if not args.full and (args.launch_pass or args.interactive_pass):
+        print("bench: --launch-pass / --interactive-pass run only with --full; ignored",
+              file=sys.stderr, flush=True)
+    args.launch_pass = 10 if args.launch_pass is None else args.launch_pass
+    args.interactive_pass = 60 if args.interactive_pass is None else args.interactive_pass
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # the driver's form `python bench.py --gpus N`: start the ranks ourselves, before
@@ -794,6 +847,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        # the last timed step's frame (outside timing; the passes of --full reuse the buffers)
+        last_i, last_j = sched.last_slot
+        last_time = sched.slot_time[last_i][last_j]
+        last_frame = frames[last_i][last_j].clone() if (rank == 0 and args.dump_outputs) else None
     except rvcp_amd.abi.RvcpError as e:
         # a gather that timed out (a peer rank missing or failed: RVCP_E_TIMEOUT, the
         # communicator aborted) or any other library error: a labelled line and a non-zero exit
@@ -825,7 +882,7 @@ def main():
     # launch a one-frame-at-a-time caller makes (a grid left partly free for the next frame,
     # grid_waves_per_simd, only pays off with frames beside it)
     iso_ms, latency_ms, iso_clk = [], [], []
-    if args.launch_pass > 0:
+    if args.full and args.launch_pass > 0:
         rt_iso = rt if grid_waves == 0 else rvcp_amd.RayTracer(**dict(cfg_kw, grid_waves_per_simd=0))
         if rt_iso is not rt:
             rt_iso.upload_scene(sc)
@@ -849,7 +906,7 @@ def main():
     # per frame is config.interactive_ms_per_step beside ms_per_step.
     interactive_ms = None
     fif_i = grid_i = None
-    if args.interactive_pass > 0 and world == 1:
+    if args.full and args.interactive_pass > 0 and world == 1:
         fif_i, grid_i, _ = auto_pipeline(W * H, spp, legacy, small_scene, hw_queues, args.accel, 1)
         fif_i = min(args.interactive_frames_in_flight or fif_i, 3)
         if args.interactive_grid_waves >= 0:
@@ -928,7 +985,7 @@ def main():
     iso_s = (float(np.mean(iso_ms)) / 1000.0) if iso_ms else None
 
     frame_check, one_gpu_ms = None, None
-    if world > 1 and rank == 0:
+    if args.full and world > 1 and rank == 0:
         # the assembled N-rank frame must be bit-identical to a 1-rank render of the same frame
         # (outside timing); the same frame rendered by this GPU alone, pipelined the way a
         # one-GPU run of that frame is (auto_pipeline for the whole frame, unless the command
@@ -996,6 +1053,10 @@ def main():
 
     if args.save_frame and rank == 0:
         np.save(args.save_frame, frame.cpu().numpy().view(np.uint8).reshape(H, W, 4))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs,
+                              last_frame.cpu().numpy().view(np.uint8).reshape(H, W, 4))
 
     if rank == 0:
         out = {
@@ -1005,6 +1066,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_per_step, 4),
             "fps": round(1000.0 / ms_per_step, 2),
             # median of the intervals between consecutive calls' completions (host clock),
@@ -1137,6 +1199,9 @@ def main():
             out["config"]["per_rank"] = per_rank
         if args.save_frame:
             out["config"]["saved_frame_time"] = frame_time      # the saved frame's time seed
+        if dumped:
+            out["config"]["dumped_outputs"] = dumped
+            out["config"]["dumped_frame_time"] = last_time      # the last timed frame's seed
         if frame_check is not None:
             out["config"]["assembled_frame_bitexact_vs_1gpu"] = frame_check
             out["config"]["one_gpu_ms"] = round(one_gpu_ms, 4)
@@ -1149,7 +1214,7 @@ def main():
             out["config"]["one_gpu_value"] = round(W * H * spp / (one_gpu_ms / 1000.0) / 1e6, 2)
             if rehearsal:
                 out["config"]["physical_gpus"] = 1
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = args.cpu_threads or granted_cpus()
             out["cpu_baseline"] = cpu_baseline(sc, cfg_kw, W, H, threads)
         print(json.dumps(out), flush=True)

@@ -351,6 +351,32 @@ def test_call_schedule_accounts_every_frame_once():
                 # slot 0 of context 0 holds the first frame of the last call made on it
                 c0 = [c for c in range(len(sched.calls(steps))) if c % fif == 0][-1]
                 assert sched.slot_time[0][0] == bench.TIME0 + warm + sum(sched.calls(steps)[:c0])
+                # --dump-outputs: last_slot is where the last timed frame was rendered
+                li, lj = sched.last_slot
+                assert sched.slot_time[li][lj] == want[-1], (fif, batch, steps)
+
+
+def test_dump_outputs_whole_frame_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a frame up to DUMP_MAX_PIXELS whole, as float32; a larger one as the same
+    seeded sample of its pixels on every call, with their indices."""
+    import numpy as np
+    rng = np.random.default_rng(5)
+    rgba = rng.integers(0, 256, (7, 9, 4), dtype=np.uint8)
+    assert bench.dump_outputs(str(tmp_path / "a"), rgba) == ["frame_rgba.npy"]
+    got = np.load(tmp_path / "a" / "frame_rgba.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, rgba)
+    assert bench.DUMP_MAX_PIXELS * 16 + bench.DUMP_MAX_PIXELS * 8 <= 64 * 1000 * 1000
+    monkeypatch.setattr(bench, "DUMP_MAX_PIXELS", 20)
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), rgba) == ["frame_pixel_index.npy",
+                                                               "frame_rgba.npy"]
+    idx = np.load(tmp_path / "b" / "frame_pixel_index.npy")
+    px = np.load(tmp_path / "b" / "frame_rgba.npy")
+    assert idx.dtype == np.float64 and px.dtype == np.float32 and px.shape == (20, 4)
+    assert len(np.unique(idx)) == 20 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(px, rgba.reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "frame_pixel_index.npy"))
+    assert np.array_equal(px, np.load(tmp_path / "c" / "frame_rgba.npy"))
 
 
 def test_report_failure_names_rank_and_stage(capsys):
@@ -369,3 +395,16 @@ def test_report_failure_names_rank_and_stage(capsys):
     bench.report_failure(3, 8, wl, "warm-up frames", err)
     cap = capsys.readouterr()
     assert cap.out == "" and json.loads(cap.err)["error"]["rank"] == 3
+
+
+def test_ab_bench_runner_calls_the_full_bench():
+    """tools/ab.py's bench runner measures fields of the passes behind --full (--field
+    config.frame_latency_ms_alone with --launch-pass N, --interactive-pass N in its case
+    files): it starts bench.py with --full and its own defaults switch the passes off."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("ab", os.path.join(ROOT, "tools", "ab.py"))
+    ab = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ab)
+    cmd = ab.RUNNERS["bench"]
+    assert cmd[1:3] == ["bench.py", "--full"] and "--no-cpu-baseline" in cmd
+    assert cmd[cmd.index("--launch-pass") + 1] == cmd[cmd.index("--interactive-pass") + 1] == "0"

@@ -1,7 +1,8 @@
 """bench.py end to end on the GPU (the driver's command, a short run): the JSON line carries
 the contract's fields, its roofline is the wall-clock one (frac <= 1, derived from
-ms_per_step), the per-launch pass ran with one frame in flight, and the frame it rendered is
-bit-identical to the oracle's on sampled rows (--save-frame)."""
+ms_per_step), with --full the per-launch pass ran with one frame in flight, and the frame it
+rendered is bit-identical to the oracle's on sampled rows (--save-frame).  A plain run (no
+--full) makes none of the extra passes, and --dump-outputs writes its last timed frame."""
 import json
 import os
 import subprocess
@@ -34,7 +35,7 @@ def test_bench_line(tmp_path, workload, side, spp, steps):
     env = dict(os.environ)
     env.pop("RVCP_LIB", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload,
-                        "--steps", str(steps), "--warmup", "2", "--no-cpu-baseline",
+                        "--steps", str(steps), "--warmup", "2", "--full", "--no-cpu-baseline",
                         "--save-frame", str(frame_path)],
                        capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -104,3 +105,42 @@ def test_bench_line(tmp_path, workload, side, spp, steps):
         _, o_rgba, _ = O.render(scene_arrays(sc), sc.push_constant(c["saved_frame_time"]), cfg, W, H,
                                 rect=(0, y, W, 1), want_linear=False)
         assert np.array_equal(frame[y:y + 1], o_rgba), y
+
+
+def test_bench_plain_run_dumps_last_frame(tmp_path):
+    """The plain command (no --full): the timed steps only -- no isolated-launch pass, no
+    interactive pass, no CPU baseline, their fields null -- and --dump-outputs writes the last
+    timed frame (here the single frame of a shorter last batch) as float32, the oracle's render
+    of its time seed, byte for byte."""
+    W = H = 384
+    spp, steps = 10, 9
+    out_dir = tmp_path / "outputs"
+    env = dict(os.environ)
+    env.pop("RVCP_LIB", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                        "--workload", "c2", "--steps", str(steps), "--warmup", "2",
+                        "--dump-outputs", str(out_dir)],
+                       capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == steps and d["n_gpus"] == 1
+    assert d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(W * H * spp / (d["ms_per_step"] / 1000.0) / 1e6, rel=2e-3)
+    c, rl = d["config"], d["roofline"]
+    assert d["cpu_baseline"] is None and d["vs_baseline"] is None
+    assert rl["per_launch"] is None and c["frame_latency_ms_alone"] is None
+    assert c["interactive_ms_per_step"] is None and c["interactive_frames"] == 0
+    assert 0 < rl["frac"] <= 1
+    assert c["frames_per_launch"] == 2                      # 4 batches of 2 and a single frame
+    assert c["dumped_outputs"] == ["frame_rgba.npy"]
+    assert c["dumped_frame_time"] == 123.0 + c["warmup_frames"] + steps - 1
+    assert sorted(os.listdir(out_dir)) == ["frame_rgba.npy"]
+    frame = np.load(out_dir / "frame_rgba.npy")
+    assert frame.dtype == np.float32 and frame.shape == (H, W, 4)
+    sc = rvcp_amd.Scene.default()
+    _, o_rgba, _ = O.render(scene_arrays(sc), sc.push_constant(c["dumped_frame_time"]),
+                            rvcp_amd.abi.make_config(spp=spp), W, H, want_linear=False)
+    assert np.array_equal(frame, o_rgba.astype(np.float32))

@@ -98,7 +98,8 @@ def test_bench_self_launch_rehearsal_n2():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RVCP_LIB"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                        "--workload", "c2", "--steps", "8", "--warmup", "2", "--launch-pass", "2"],
+                        "--workload", "c2", "--steps", "8", "--warmup", "2", "--full",
+                        "--launch-pass", "2"],
                        capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

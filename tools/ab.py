@@ -8,7 +8,7 @@ arguments of the runner.  Cases run interleaved, pass after pass, each under its
 limit; one line per (pass, case), then the median per case.
 
 Runners:
-  bench     python bench.py --no-cpu-baseline --launch-pass 0 --interactive-pass 0 --steps 40
+  bench     python bench.py --full --no-cpu-baseline --launch-pass 0 --interactive-pass 0 --steps 40
             --warmup 5 ARGS
             (ms_per_step, the driver's figure: frames in flight and batches as the bench
             picks them unless ARGS fix them; --field picks another key of the line, e.g.
@@ -32,7 +32,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RUNNERS = {
-    "bench": [sys.executable, "bench.py", "--no-cpu-baseline", "--launch-pass", "0",
+    "bench": [sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--launch-pass", "0",
               "--interactive-pass", "0", "--steps", "40", "--warmup", "5"],
     "frames": [sys.executable, "tools/frames.py", "--frames", "20"],
     "share": [sys.executable, "-u", "tools/rank_share.py"],
