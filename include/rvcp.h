@@ -238,6 +238,37 @@ typedef struct rvcp_stats {
 
 #define RVCP_VARIANT_SPECIALIZED 16
 
+/* ---------------------------------------------------------------------------------------
+ * G-buffer and denoiser.  The reference has no counterpart: it stores the raw Monte-Carlo
+ * frame (ray_tracer_games101_branch.comp:497-500) and its README lists only "BVH" and
+ * "importance sampling" as TODO (README.md:28-32).  The filter is the edge-avoiding a-trous
+ * wavelet transform of Dammertz, Sewtz, Hanika and Lensch (HPG 2010), guided by the primary
+ * hit the pre-pass of the render already finds.
+ * ------------------------------------------------------------------------------------- */
+#define RVCP_GBUFFER_MISS      0xFFFFFFFFu   /* face: the primary ray hit nothing */
+#define RVCP_GBUFFER_EMISSIVE  0x80000000u   /* material: bit 31 set when its ty is Light */
+
+/* One pixel of rvcp_render_gbuffer_async: the primary hit as get_intersection_with_scene
+ * (ray_tracer_games101_branch.comp:283-296) returns it for the pixel's sample_ray (:217-235).
+ * A miss holds face = RVCP_GBUFFER_MISS and zeros elsewhere. */
+typedef struct rvcp_gbuffer_texel {
+    float position[3];      /* hit point, o + d t (:268) */
+    uint32_t face;          /* face index, or RVCP_GBUFFER_MISS */
+    float normal[3];        /* interpolated shading normal, turned to face the ray (:262-271) */
+    uint32_t material;      /* face.material_id | RVCP_GBUFFER_EMISSIVE when its ty is 3 */
+} rvcp_gbuffer_texel_t;
+
+#define RVCP_DENOISE_MAX_ITERATIONS 8
+
+/* Parameters of rvcp_denoise_async (the filter's definition: DESIGN.md §4.9). */
+typedef struct rvcp_denoise_params {
+    uint32_t iterations;          /* a-trous passes, pass i with step 2^i; 1..8 */
+    uint32_t normal_power_log2;   /* w_n = max(0, n_p . n_q) squared this many times; 0..8 */
+    float sigma_color;            /* colour edge-stopping width at pass 0 (halved per pass),
+                                     > 0; +inf switches the colour weight off */
+    float sigma_plane;            /* plane-distance edge-stopping width, world units, > 0 */
+} rvcp_denoise_params_t;
+
 /* Layout checks: sizes/offsets the reference's Rust structs and std140/std430 blocks imply. */
 #ifdef __cplusplus
 #define RVCP_STATIC_ASSERT(c, m) static_assert(c, m)
@@ -259,6 +290,11 @@ RVCP_STATIC_ASSERT(sizeof(rvcp_face_t) == 16, "AlignedFace is 16 B");
 RVCP_STATIC_ASSERT(sizeof(rvcp_sphere_t) == 32, "AlignedSphere is 32 B");
 RVCP_STATIC_ASSERT(sizeof(rvcp_lengths_t) == 24, "LengthBuffer is 24 B");
 RVCP_STATIC_ASSERT(sizeof(rvcp_mandelbrot_push_t) == 12, "Mandelbrot CameraData is 12 B");
+RVCP_STATIC_ASSERT(sizeof(rvcp_gbuffer_texel_t) == 32, "G-buffer texel is 32 B");
+RVCP_STATIC_ASSERT(offsetof(rvcp_gbuffer_texel_t, face) == 12, "GBuffer.face @12");
+RVCP_STATIC_ASSERT(offsetof(rvcp_gbuffer_texel_t, normal) == 16, "GBuffer.normal @16");
+RVCP_STATIC_ASSERT(offsetof(rvcp_gbuffer_texel_t, material) == 28, "GBuffer.material @28");
+RVCP_STATIC_ASSERT(sizeof(rvcp_denoise_params_t) == 16, "denoise params are 16 B");
 
 typedef struct rvcp_ctx rvcp_ctx_t;
 
@@ -510,6 +546,55 @@ int rvcp_gather_frame_async(rvcp_ctx_t *ctx, const void *d_shard_rgba8, uint32_t
  * rvcp_sync_stats / rvcp_wait wait for the render only: rank 0's assembled frame (d_frame)
  * is complete after this call, not after theirs. */
 int rvcp_gather_wait(rvcp_ctx_t *ctx, float *gather_ms, float *frame_ms);
+
+/* ---------------------------------------------------------------------------------------
+ * G-buffer + edge-avoiding a-trous denoiser (opt-in; no other entry point changes).  No
+ * counterpart in the reference (see the structs above).
+ * ------------------------------------------------------------------------------------- */
+
+/* Enqueue the G-buffer of one frame on `stream`: W*H rvcp_gbuffer_texel_t, row-major, into
+ * device memory.  One lane per pixel traces the primary ray with the render's own scan (the
+ * BVH with accel = RVCP_ACCEL_BVH), so each texel is the hit the render's pre-pass finds and
+ * the shader's get_intersection_with_scene returns, bit for bit.  Ordered on `stream` like
+ * the other async calls; it is not the context's pending frame (nothing to wait for but the
+ * stream) and touches no statistics.  games101 integrator on a one-GPU context only:
+ * RVCP_INTEGRATOR_LEGACY and n_gpus > 1 return RVCP_E_UNSUPPORTED. */
+int rvcp_render_gbuffer_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push,
+                              uint32_t width, uint32_t height, void *d_gbuffer, void *stream);
+
+/* The default filter parameters (the best row on average of the sweep of
+ * tools/denoise_sweep.py over the Cornell box at SPP 1, 4 and 10).  Needs no device. */
+int rvcp_denoise_params_default(rvcp_denoise_params_t *params);
+
+/* Enqueue the filter on `stream`: d_linear_rgb_in (W*H*3 floats, e.g. the linear output of
+ * rvcp_render_async) filtered under d_gbuffer (W*H texels) into d_linear_rgb_out (W*H*3
+ * floats, must not overlap the input) and, when d_rgba8_out is not NULL, pow(clamp(c), 0.6) of
+ * the result as RGBA8 under the context's unorm_rule (W*H*4 bytes, alpha 255), exactly as the
+ * render stores its own frame.  A pixel is filterable when its texel is a hit on a
+ * non-emissive material; other pixels pass through unchanged and feed no neighbour.  All
+ * weights are single correctly rounded f32 operations in a fixed order, so
+ * the result is reproducible bit for bit.  params = NULL: the defaults.  Needs no scene.
+ * The passes between the first and the last go through buffers the context owns.  A render
+ * pending on the context is not an error: the filter is ordered behind it.
+ * RVCP_E_INVALID: NULL / zero arguments, overlapping input and output, iterations outside
+ * 1..RVCP_DENOISE_MAX_ITERATIONS, normal_power_log2 > 8, a sigma that is not > 0. */
+int rvcp_denoise_async(rvcp_ctx_t *ctx, const void *d_linear_rgb_in, const void *d_gbuffer,
+                       uint32_t width, uint32_t height, const rvcp_denoise_params_t *params,
+                       void *d_linear_rgb_out, void *d_rgba8_out, void *stream);
+
+/* Wait for the context's last rvcp_denoise_async; *denoise_ms (optional) gets its device
+ * time, first pass to the RGBA8 store (HIP events on its stream).  RVCP_E_INVALID when no
+ * filter was enqueued since the last call. */
+int rvcp_denoise_wait(rvcp_ctx_t *ctx, float *denoise_ms);
+
+/* Render + G-buffer + filter of one frame, synchronously into host memory, on the context's
+ * stream and in buffers the context owns: out_rgba8 (W*H*4 bytes) and out_linear_rgb
+ * (optional, W*H*3 floats) are the filtered frame; stats (optional) are the render's,
+ * *denoise_ms (optional) as rvcp_denoise_wait.  Restrictions of rvcp_render_gbuffer_async. */
+int rvcp_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push,
+                         uint32_t width, uint32_t height, const rvcp_denoise_params_t *params,
+                         uint8_t *out_rgba8, float *out_linear_rgb, rvcp_stats_t *stats,
+                         float *denoise_ms);
 
 #ifdef __cplusplus
 }

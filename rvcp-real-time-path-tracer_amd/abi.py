@@ -26,6 +26,14 @@ STATS_DTYPE = np.dtype([("kernel_ms", "<f8"), ("traversals", "<u8"),
                         ("kernel_variant", "<i4"), ("wave_iterations", "<u8"),
                         ("main_kernel_ms", "<f8"), ("shader_clock_ghz", "<f8")])
 assert CONFIG_DTYPE.itemsize == 64 and STATS_DTYPE.itemsize == 64
+# rvcp_gbuffer_texel_t / rvcp_denoise_params_t (G-buffer and a-trous denoiser)
+GBUFFER_DTYPE = np.dtype([("position", "<f4", (3,)), ("face", "<u4"),
+                          ("normal", "<f4", (3,)), ("material", "<u4")])
+DENOISE_PARAMS_DTYPE = np.dtype([("iterations", "<u4"), ("normal_power_log2", "<u4"),
+                                 ("sigma_color", "<f4"), ("sigma_plane", "<f4")])
+assert GBUFFER_DTYPE.itemsize == 32 and DENOISE_PARAMS_DTYPE.itemsize == 16
+GBUFFER_MISS, GBUFFER_EMISSIVE = 0xFFFFFFFF, 0x80000000
+DENOISE_MAX_ITERATIONS = 8
 # rvcp_stats_t.kernel_variant -> the dominant kernel's name as rocprofv3 reports it
 KERNEL_NAMES = {1: "games101_kernel", 2: "games101_dual_kernel", 3: "games101_path_kernel<5>",
                 4: "games101_tiled_kernel", 5: "games101_tiled_single_kernel",
@@ -55,7 +63,9 @@ EXPORTED = ["rvcp_version", "rvcp_config_default", "rvcp_config_default_for", "r
             "rvcp_upload_scene_file", "rvcp_mandelbrot", "rvcp_render_async", "rvcp_wait",
             "rvcp_rccl_unique_id", "rvcp_rccl_init", "rvcp_rccl_attach", "rvcp_gather_frame_async",
             "rvcp_gather_wait", "rvcp_render_frames_async", "rvcp_rccl_set_timeout",
-            "rvcp_abi_version", "rvcp_set_code_cache_dir", "rvcp_code_cache_counts"]
+            "rvcp_abi_version", "rvcp_set_code_cache_dir", "rvcp_code_cache_counts",
+            "rvcp_render_gbuffer_async", "rvcp_denoise_params_default", "rvcp_denoise_async",
+            "rvcp_denoise_wait", "rvcp_render_denoised"]
 
 
 # Integrator mode 2 (ray_tracer.comp ray_trace): its own #defines (ray_tracer.comp:5-13).
@@ -77,6 +87,19 @@ def make_config(**kw) -> np.ndarray:
     for k, v in vals.items():
         cfg[k] = v
     return cfg
+
+
+def make_denoise_params(**overrides) -> np.ndarray:
+    """rvcp_denoise_params_t with the library's defaults (rvcp_denoise_params_default),
+    overridden by the keyword arguments (sigma_color=float("inf") switches the colour weight
+    off)."""
+    p = np.zeros((), dtype=DENOISE_PARAMS_DTYPE)
+    rc = load().rvcp_denoise_params_default(ptr(p))
+    if rc != RVCP_OK:
+        raise RvcpError(rc, "rvcp_denoise_params_default failed")
+    for k, v in overrides.items():
+        p[k] = v
+    return p
 
 
 class RvcpError(RuntimeError):
@@ -148,13 +171,20 @@ def load():
     L.rvcp_rccl_set_timeout.argtypes = [P, u32]
     L.rvcp_gather_frame_async.argtypes = [P, P, u32, u32, P, P, P]
     L.rvcp_gather_wait.argtypes = [P, P, P]
+    L.rvcp_render_gbuffer_async.argtypes = [P, P, u32, u32, P, P]
+    L.rvcp_denoise_params_default.argtypes = [P]
+    L.rvcp_denoise_async.argtypes = [P, P, P, u32, u32, P, P, P, P]
+    L.rvcp_denoise_wait.argtypes = [P, P]
+    L.rvcp_render_denoised.argtypes = [P, P, u32, u32, P, P, P, P, P]
     for name in ("rvcp_config_default", "rvcp_config_default_for", "rvcp_create", "rvcp_destroy", "rvcp_upload_scene",
                  "rvcp_render", "rvcp_render_shard_async", "rvcp_sync_stats",
                  "rvcp_assemble_frame_async", "rvcp_upload_scene_file", "rvcp_mandelbrot",
                  "rvcp_render_async", "rvcp_wait", "rvcp_rccl_unique_id", "rvcp_rccl_init",
                  "rvcp_rccl_attach", "rvcp_gather_frame_async", "rvcp_gather_wait",
                  "rvcp_render_frames_async", "rvcp_rccl_set_timeout", "rvcp_set_code_cache_dir",
-                 "rvcp_code_cache_counts"):
+                 "rvcp_code_cache_counts", "rvcp_render_gbuffer_async",
+                 "rvcp_denoise_params_default", "rvcp_denoise_async", "rvcp_denoise_wait",
+                 "rvcp_render_denoised"):
         getattr(L, name).restype = ctypes.c_int
     if L.rvcp_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI revision {L.rvcp_abi_version()}, this binding "

@@ -12,6 +12,7 @@
 #include <rccl/rccl.h>
 
 #include <atomic>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -126,6 +127,18 @@ struct rvcp_ctx {
     uint32_t *d_pack_rgba = nullptr;
     float *d_pack_lin = nullptr;
     size_t cap_surf_pack = 0;
+
+    // denoiser (rvcp_denoise_async): the passes between the first and the last ping-pong
+    // between d_dn[0] and d_dn[1]; evd0 / evd1 bracket the last filter on its stream (created
+    // by the first call).  rvcp_render_denoised keeps its G-buffer and linear frames here too.
+    float *d_dn[2] = {nullptr, nullptr};
+    size_t cap_dn[2] = {0, 0};
+    hipEvent_t evd0 = nullptr, evd1 = nullptr;
+    bool denoise_recorded = false;      // evd1 has been recorded at least once
+    bool denoise_pending = false;       // ... and not yet waited for with rvcp_denoise_wait
+    void *d_gbuf = nullptr;
+    float *d_dn_in = nullptr, *d_dn_out = nullptr;
+    size_t cap_gbuf = 0, cap_dn_io = 0;
 
     // debug build: per-wave timeline of the path kernel appended per render
     unsigned long long *d_timeline = nullptr;
@@ -338,7 +351,7 @@ static int wait_gather_done(rvcp_ctx_t *ctx);
 extern "C" {
 
 // 0.2.0: ABI revision 2 (rvcp.h RVCP_ABI_VERSION: rvcp_stats_t is 64 B)
-const char *rvcp_version(void) { return "rvcp-mi355x 0.2.0 (gfx950, ABI 2)"; }
+const char *rvcp_version(void) { return "rvcp-mi355x 0.3.0 (gfx950, ABI 2)"; }
 
 uint32_t rvcp_abi_version(void) { return RVCP_ABI_VERSION; }
 
@@ -574,6 +587,8 @@ static int impl_destroy(rvcp_ctx_t *ctx)
         delete ctx;
         return RVCP_E_TIMEOUT;
     }
+    // a filter still in flight (possibly on the caller's stream) reads the buffers freed below
+    if (ctx->denoise_recorded) (void)hipEventSynchronize(ctx->evd1);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm && ctx->comm_owned) (void)rccl_api().comm_destroy(ctx->comm);
     ctx->comm = nullptr;
@@ -592,6 +607,13 @@ static int impl_destroy(rvcp_ctx_t *ctx)
     (void)hipFree(ctx->d_timeline);
     (void)hipFree(ctx->d_pack_rgba);
     (void)hipFree(ctx->d_pack_lin);
+    (void)hipFree(ctx->d_dn[0]);
+    (void)hipFree(ctx->d_dn[1]);
+    (void)hipFree(ctx->d_gbuf);
+    (void)hipFree(ctx->d_dn_in);
+    (void)hipFree(ctx->d_dn_out);
+    if (ctx->evd0) (void)hipEventDestroy(ctx->evd0);
+    if (ctx->evd1) (void)hipEventDestroy(ctx->evd1);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->evm) (void)hipEventDestroy(ctx->evm);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -1335,6 +1357,203 @@ static int impl_mandelbrot(rvcp_ctx_t *ctx, const rvcp_mandelbrot_push_t *push, 
     return RVCP_OK;
 }
 
+// ---- G-buffer and denoiser ---------------------------------------------
+
+static int impl_render_gbuffer_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push,
+                                     uint32_t width, uint32_t height, void *d_gbuffer, void *stream)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!push || !d_gbuffer || width == 0 || height == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid G-buffer arguments");
+    if ((uint64_t)width * height >= (1ull << 31))
+        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
+        return fail(ctx, RVCP_E_UNSUPPORTED, "the G-buffer is implemented for the games101 integrator");
+    if (!ctx->subs.empty())
+        return fail(ctx, RVCP_E_UNSUPPORTED, "the G-buffer drives one GPU (n_gpus = 1)");
+    if (!ctx->has_scene) return fail(ctx, RVCP_E_NO_SCENE, "G-buffer before rvcp_upload_scene");
+    if (!primary_t_range_ok(*push, width, height))
+        return fail(ctx, RVCP_E_INVALID, "camera t_far x t_coef must stay below 2^24 (the "
+                    "shader's miss test t_max + 1, :287, :424)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    // the fields the primary ray and its scan read (render_frames fills the same ones)
+    FrameArgs A;
+    std::memset(&A, 0, sizeof(A));
+    camera_constants(*push, width, height, A);
+    A.width = width;
+    A.height = height;
+    A.shard_index = 0;
+    A.shard_count = 1;
+    A.n_pixels = width * height;
+    A.n_faces = ctx->n_faces;
+    A.accel = (ctx->cfg.accel == RVCP_ACCEL_BVH && ctx->n_faces > 0) ? RVCP_ACCEL_BVH : RVCP_ACCEL_NONE;
+    A.bvh_root = ctx->bvh_root;
+    A.bvh_n4 = ctx->bvh_n4;
+    A.bvh_slots = ctx->bvh_slots;
+    A.bvh_prefix = A.accel == RVCP_ACCEL_BVH ? ctx->bvh_prefix : 0u;
+    if (rvcp_launch_gbuffer(&A, ctx->d_tri, ctx->d_shade, ctx->d_bvh_nodes, ctx->d_bvh_tris,
+                            d_gbuffer, s) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string("G-buffer launch failed: ") +
+                                         hipGetErrorString(hipGetLastError()));
+    return RVCP_OK;
+}
+
+static int impl_denoise_params_default(rvcp_denoise_params_t *params)
+{
+    if (!params) return RVCP_E_INVALID;
+    // the best row on average of tools/denoise_sweep.py
+    params->iterations = 2;
+    params->normal_power_log2 = 7;
+    params->sigma_color = INFINITY;
+    params->sigma_plane = 0.1f;
+    return RVCP_OK;
+}
+
+// sigma_i^2 of pass i: sigma_i = sigma_color 2^-i (an exact scaling), squared with one rounding
+static float denoise_color_s2(float sigma_color, uint32_t i)
+{
+    const float sig = sigma_color * std::ldexp(1.0f, -(int)i);
+    return sig * sig;
+}
+
+static int grow(rvcp_ctx_t *ctx, void **buf, size_t *cap, size_t n, size_t elem)
+{
+    if (*cap >= n) return RVCP_OK;
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    HIP_TRY(ctx, hipMalloc(buf, n * elem));
+    *cap = n;
+    return RVCP_OK;
+}
+
+static int impl_denoise_async(rvcp_ctx_t *ctx, const void *d_in, const void *d_gbuffer,
+                              uint32_t width, uint32_t height, const rvcp_denoise_params_t *params,
+                              void *d_out, void *d_rgba8_out, void *stream)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!d_in || !d_gbuffer || !d_out || width == 0 || height == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid denoise arguments");
+    if ((uint64_t)width * height >= (1ull << 31))
+        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    rvcp_denoise_params_t P;
+    if (params) P = *params;
+    else (void)impl_denoise_params_default(&P);
+    if (P.iterations < 1 || P.iterations > RVCP_DENOISE_MAX_ITERATIONS)
+        return fail(ctx, RVCP_E_INVALID, "denoise iterations must be in 1..8");
+    if (P.normal_power_log2 > 8)
+        return fail(ctx, RVCP_E_INVALID, "denoise normal_power_log2 must be in 0..8");
+    const bool use_color = !std::isinf(P.sigma_color);
+    // (negated compares: a NaN sigma is rejected too)
+    if (!(P.sigma_color > 0.0f) || !(P.sigma_plane > 0.0f))
+        return fail(ctx, RVCP_E_INVALID, "denoise sigma_color and sigma_plane must be > 0");
+    // the last pass's sigma_i^2 is the smallest: it must not underflow (a zero divisor)
+    if (use_color && !(denoise_color_s2(P.sigma_color, P.iterations - 1) >= FLT_MIN))
+        return fail(ctx, RVCP_E_INVALID, "denoise sigma_color is too small (sigma_i^2 underflows)");
+    const size_t npx = (size_t)width * height;
+    {   // the output must not overlap the input: a pass reads neighbours it would have overwritten
+        const uintptr_t a = (uintptr_t)d_in, b = (uintptr_t)d_out, n = npx * 12;
+        if (a < b + n && b < a + n)
+            return fail(ctx, RVCP_E_INVALID, "denoise output overlaps the input");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if (!ctx->evd0) {
+        HIP_TRY(ctx, hipEventCreate(&ctx->evd0));
+        HIP_TRY(ctx, hipEventCreate(&ctx->evd1));
+    }
+    // intermediates: none for one pass, one buffer for two, both from three passes on
+    int rc;
+    for (uint32_t b = 0; b < 2 && b + 1 < P.iterations; ++b)
+        if ((rc = grow(ctx, (void **)&ctx->d_dn[b], &ctx->cap_dn[b], npx, 12)) != RVCP_OK) return rc;
+    // behind a render pending on this context (when it runs on another stream), and behind the
+    // context's previous filter, which used the same intermediates
+    if (ctx->pending && ctx->render_stream != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev1, 0));
+    if (ctx->denoise_recorded) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evd1, 0));
+    HIP_TRY(ctx, hipEventRecord(ctx->evd0, s));
+    const float *src = (const float *)d_in;
+    for (uint32_t i = 0; i < P.iterations; ++i) {
+        float *dst = i + 1 == P.iterations ? (float *)d_out : ctx->d_dn[i & 1u];
+        if (rvcp_launch_denoise_pass(src, d_gbuffer, dst, width, height, 1u << i,
+                                     P.normal_power_log2, use_color ? 1u : 0u,
+                                     use_color ? denoise_color_s2(P.sigma_color, i) : 1.0f,
+                                     P.sigma_plane, s) != 0)
+            return fail(ctx, RVCP_E_HIP, std::string("denoise launch failed: ") +
+                                             hipGetErrorString(hipGetLastError()));
+        src = dst;
+    }
+    if (d_rgba8_out &&
+        rvcp_launch_tonemap((const float *)d_out, (uint32_t)npx, ctx->d_gamma,
+                            (uint32_t *)d_rgba8_out, s) != 0)
+        return fail(ctx, RVCP_E_HIP, "denoise tone-map launch failed");
+    HIP_TRY(ctx, hipEventRecord(ctx->evd1, s));
+    ctx->denoise_recorded = true;
+    ctx->denoise_pending = true;
+    return RVCP_OK;
+}
+
+static int impl_denoise_wait(rvcp_ctx_t *ctx, float *denoise_ms)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!ctx->denoise_pending) return fail(ctx, RVCP_E_INVALID, "no denoise in flight");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->evd1));
+    if (denoise_ms) HIP_TRY(ctx, hipEventElapsedTime(denoise_ms, ctx->evd0, ctx->evd1));
+    ctx->denoise_pending = false;
+    return RVCP_OK;
+}
+
+static int impl_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                                uint32_t height, const rvcp_denoise_params_t *params,
+                                uint8_t *out_rgba8, float *out_linear_rgb, rvcp_stats_t *stats,
+                                float *denoise_ms)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!push || !out_rgba8 || width == 0 || height == 0 ||
+        (uint64_t)width * height >= (1ull << 31))
+        return fail(ctx, RVCP_E_INVALID, "invalid render_denoised arguments");
+    if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
+        return fail(ctx, RVCP_E_UNSUPPORTED, "the G-buffer is implemented for the games101 integrator");
+    if (!ctx->subs.empty())
+        return fail(ctx, RVCP_E_UNSUPPORTED, "render_denoised drives one GPU (n_gpus = 1)");
+    if (ctx->pending)
+        return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t npx = (size_t)width * height;
+    int rc;
+    if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, npx, 4)) != RVCP_OK) return rc;
+    if ((rc = grow(ctx, &ctx->d_gbuf, &ctx->cap_gbuf, npx, sizeof(rvcp_gbuffer_texel_t))) != RVCP_OK)
+        return rc;
+    if (ctx->cap_dn_io < npx) {
+        (void)hipFree(ctx->d_dn_in);
+        (void)hipFree(ctx->d_dn_out);
+        ctx->d_dn_in = ctx->d_dn_out = nullptr;
+        ctx->cap_dn_io = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_dn_in, npx * 12));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_dn_out, npx * 12));
+        ctx->cap_dn_io = npx;
+    }
+    // render (raw linear frame), G-buffer and filter, in this order on the context's stream; the
+    // filter's RGBA8 store overwrites the render's
+    if ((rc = rvcp_render_async(ctx, push, width, height, ctx->d_rgba, ctx->d_dn_in, ctx->stream)) != RVCP_OK)
+        return rc;
+    if ((rc = impl_render_gbuffer_async(ctx, push, width, height, ctx->d_gbuf, ctx->stream)) != RVCP_OK ||
+        (rc = impl_denoise_async(ctx, ctx->d_dn_in, ctx->d_gbuf, width, height, params,
+                                 ctx->d_dn_out, ctx->d_rgba, ctx->stream)) != RVCP_OK) {
+        const std::string why = ctx->err;
+        (void)rvcp_wait(ctx, nullptr);          // the render is enqueued: leave no frame pending
+        ctx->err = why;
+        return rc;
+    }
+    if ((rc = rvcp_wait(ctx, stats)) != RVCP_OK) return rc;
+    if ((rc = impl_denoise_wait(ctx, denoise_ms)) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, npx * 4, hipMemcpyDeviceToHost));
+    if (out_linear_rgb)
+        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, ctx->d_dn_out, npx * 12, hipMemcpyDeviceToHost));
+    return RVCP_OK;
+}
+
 static int impl_assemble_frame_async(rvcp_ctx_t *ctx, const void *d_gathered, uint32_t slot_rows,
                               uint32_t width, uint32_t height, uint32_t shard_count,
                               void *d_frame, void *stream)
@@ -1805,6 +2024,42 @@ int rvcp_mandelbrot(rvcp_ctx_t *ctx, const rvcp_mandelbrot_push_t *push, uint32_
 {
     return barrier(ctx, [&] { return impl_mandelbrot(ctx, push, width, height, out_rgba8,
         out_value, stats); });
+}
+
+int rvcp_render_gbuffer_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                              uint32_t height, void *d_gbuffer, void *stream)
+{
+    return barrier(ctx, [&] { return impl_render_gbuffer_async(ctx, push, width, height, d_gbuffer, stream); });
+}
+
+int rvcp_denoise_params_default(rvcp_denoise_params_t *params)
+{
+    return barrier(nullptr, [&] { return impl_denoise_params_default(params); });
+}
+
+int rvcp_denoise_async(rvcp_ctx_t *ctx, const void *d_linear_rgb_in, const void *d_gbuffer,
+                       uint32_t width, uint32_t height, const rvcp_denoise_params_t *params,
+                       void *d_linear_rgb_out, void *d_rgba8_out, void *stream)
+{
+    return barrier(ctx, [&] {
+        return impl_denoise_async(ctx, d_linear_rgb_in, d_gbuffer, width, height, params,
+                                  d_linear_rgb_out, d_rgba8_out, stream);
+    });
+}
+
+int rvcp_denoise_wait(rvcp_ctx_t *ctx, float *denoise_ms)
+{
+    return barrier(ctx, [&] { return impl_denoise_wait(ctx, denoise_ms); });
+}
+
+int rvcp_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                         uint32_t height, const rvcp_denoise_params_t *params, uint8_t *out_rgba8,
+                         float *out_linear_rgb, rvcp_stats_t *stats, float *denoise_ms)
+{
+    return barrier(ctx, [&] {
+        return impl_render_denoised(ctx, push, width, height, params, out_rgba8, out_linear_rgb,
+                                    stats, denoise_ms);
+    });
 }
 
 int rvcp_assemble_frame_async(rvcp_ctx_t *ctx, const void *d_gathered, uint32_t slot_rows,

@@ -324,6 +324,18 @@ int rvcp_legacy_occupancy(int *blocks_per_cu);
 int rvcp_launch_mandelbrot(float pos_x, float pos_y, float scale, uint32_t width,
                            uint32_t height, const float *unorm_t, uint32_t *out_rgba,
                            float *out_value, void *stream);
+// The G-buffer of one frame (rvcp_render_gbuffer_async): args->n_pixels texels of 32 B into out
+int rvcp_launch_gbuffer(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
+                        const rvcp::FaceShade *shade, const rvcp::Bvh4Node *bvh_nodes,
+                        const rvcp::TriRecord *bvh_tris, void *out, void *stream);
+// tonemap_kernel alone (the denoiser's RGBA8 store)
+int rvcp_launch_tonemap(const float *lin, uint32_t n, const float *gamma_t, uint32_t *out_rgba,
+                        void *stream);
+// One a-trous pass (rvcp_denoise.hip): step = 2^i, color_s2 = sigma_i^2 (use_color = 0: the
+// colour weight is 1)
+int rvcp_launch_denoise_pass(const float *in, const void *gbuffer, float *out, uint32_t width,
+                             uint32_t height, uint32_t step, uint32_t normal_power_log2,
+                             uint32_t use_color, float color_s2, float sigma_plane, void *stream);
 int rvcp_launch_assemble(const uint32_t *gathered, uint32_t slot_rows, uint32_t width,
                          uint32_t height, uint32_t shard_count, uint32_t *frame, void *stream);
 int rvcp_launch_fill(uint32_t *out_rgba, float *out_lin, uint32_t n_pixels, uint32_t rgba,

@@ -1732,6 +1732,54 @@ __global__ __launch_bounds__(kPrimaryBlock) void games101_primary_kernel(
     primary_body<BVH, false>(A, tri, faces, verts, mats, gamma_t, out_rgba, out_lin, counters,
                              surf, shade, bvh_nodes, bvh_tris, cams, frame_stride);
 }
+
+// The G-buffer (rvcp_render_gbuffer_async): the pre-pass's primary hit of every
+// pixel, written out as a rvcp_gbuffer_texel_t instead of being shaded -- the same ray
+// (pixel_uv, primary_ray), the same tests in the same order (the generic scan, or the hybrid's
+// prefix faces and then the BVH) and the same hit record (hit_shade) as primary_body, so the
+// texel is the hit the render starts from.  One lane per pixel; a texel leaves as two 16-byte
+// stores.
+template <bool BVH>
+__global__ __launch_bounds__(kPrimaryBlock) void games101_gbuffer_kernel(
+    FrameArgs A, const TriRecord *__restrict__ tri, const FaceShade *__restrict__ shade,
+    const Bvh4Node *__restrict__ bvh_nodes, const TriRecord *__restrict__ bvh_tris,
+    float4 *__restrict__ out)
+{
+    const uint32_t pix = blockIdx.x * kPrimaryBlock + threadIdx.x;
+    if (pix < A.n_pixels) {
+        float u_, v_, tmin, tmax;
+        f3 o, d;
+        pixel_uv(A, pix, u_, v_);
+        primary_ray(A, u_, v_, o, d, tmin, tmax);
+        int best = -1;
+        float bt = tmax;
+        if (BVH) {
+            for (uint32_t i = 0; i < A.bvh_prefix; ++i) {
+                float t;
+                if (tri_accept(tri[i], o, d, tmin, bt, t)) { bt = t; best = (int)i; }
+            }
+            bvh_nearest<false>(bvh_nodes, bvh_tris, A.bvh_root, nullptr, o, d, tmin, bt, best, A.bvh_n4, A.bvh_slots);
+        } else {
+#pragma unroll 2
+            for (uint32_t i = 0; i < A.n_faces; ++i) {
+                float t;
+                if (tri_accept(tri[i], o, d, tmin, bt, t)) { bt = t; best = (int)i; }
+            }
+        }
+        float4 g0 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(RVCP_GBUFFER_MISS));
+        float4 g1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (best >= 0) {
+            f3 hpos, hn;
+            FaceShade fs;
+            hit_shade(tri, shade, best, o, d, bt, hpos, hn, fs);
+            const uint32_t mat = fs.mat | (fs.ty == kLight ? RVCP_GBUFFER_EMISSIVE : 0u);
+            g0 = make_float4(hpos.x, hpos.y, hpos.z, __uint_as_float((uint32_t)best));
+            g1 = make_float4(hn.x, hn.y, hn.z, __uint_as_float(mat));
+        }
+        out[2 * (size_t)pix] = g0;
+        out[2 * (size_t)pix + 1] = g1;
+    }
+}
 #endif
 
 // ======================================================================================
@@ -3478,6 +3526,29 @@ extern "C" int rvcp_launch_games101_v3(const rvcp::FrameArgs *args, uint32_t n_f
     if (tb > 8192u) tb = 8192u;
     hipLaunchKernelGGL(rvcp::tonemap_kernel, dim3(tb), dim3(rvcp::kToneBlock), 0, (hipStream_t)stream,
                        out_lin, n_tone, gamma_t, out_rgba);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int rvcp_launch_gbuffer(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
+                                   const rvcp::FaceShade *shade, const rvcp::Bvh4Node *bvh_nodes,
+                                   const rvcp::TriRecord *bvh_tris, void *out, void *stream)
+{
+    const uint32_t blocks = (args->n_pixels + rvcp::kPrimaryBlock - 1) / rvcp::kPrimaryBlock;
+    hipLaunchKernelGGL(args->accel ? rvcp::games101_gbuffer_kernel<true>
+                                   : rvcp::games101_gbuffer_kernel<false>,
+                       dim3(blocks), dim3(rvcp::kPrimaryBlock), 0, (hipStream_t)stream, *args, tri,
+                       shade, bvh_nodes, bvh_tris, (float4 *)out);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// tonemap_kernel alone: the denoiser's RGBA8 store (rvcp_denoise_async) of n pixels
+extern "C" int rvcp_launch_tonemap(const float *lin, uint32_t n, const float *gamma_t,
+                                   uint32_t *out_rgba, void *stream)
+{
+    uint32_t tb = (n + rvcp::kToneBlock - 1) / rvcp::kToneBlock;
+    if (tb > 8192u) tb = 8192u;
+    hipLaunchKernelGGL(rvcp::tonemap_kernel, dim3(tb), dim3(rvcp::kToneBlock), 0, (hipStream_t)stream,
+                       lin, n, gamma_t, out_rgba);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -130,6 +130,28 @@ class RayTracer:
             self.fps_last_time = now
         return img
 
+    def render_denoised(self, width: int, height: int, time: float, params=None,
+                        want_linear: bool = False):
+        """rvcp_render_denoised: one frame rendered, then filtered by the edge-avoiding a-trous
+        denoiser under its own G-buffer (params: abi.make_denoise_params(...), None = the
+        defaults).  Returns the filtered RGBA8 frame [, the filtered linear RGB]; last_stats are
+        the render's and last_denoise_ms the filter's device time."""
+        if self.scene is None:
+            raise RuntimeError("upload_scene first")
+        push = np.ascontiguousarray(push_constant(self.scene.camera, time), dtype=PUSH_DTYPE)
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=abi.DENOISE_PARAMS_DTYPE)
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        lin = np.empty((height, width, 3), dtype=np.float32) if want_linear else None
+        stats = np.zeros((), dtype=abi.STATS_DTYPE)
+        ms = ctypes.c_float(0.0)
+        self._check(self._lib.rvcp_render_denoised(
+            self._ctx, abi.ptr(push), width, height, abi.ptr(params), abi.ptr(rgba), abi.ptr(lin),
+            abi.ptr(stats), ctypes.cast(ctypes.byref(ms), ctypes.c_void_p)))
+        self.last_stats = stats
+        self.last_denoise_ms = float(ms.value)
+        return (rgba, lin) if want_linear else rgba
+
     def mandelbrot(self, push: np.ndarray, width: int, height: int, want_value: bool = False):
         """The Mandelbrot operator (rvcp_mandelbrot): grey RGBA8 frame [, escape values]."""
         from .mandelbrot import MANDELBROT_PUSH_DTYPE
@@ -172,6 +194,34 @@ class RayTracer:
             self._ctx, abi.ptr(push), width, height, ctypes.c_void_p(d_rgba),
             ctypes.c_void_p(d_linear) if d_linear else None,
             ctypes.c_void_p(stream) if stream else None))
+
+    def render_gbuffer_async(self, push, width, height, d_gbuffer: int, stream: int = 0):
+        """rvcp_render_gbuffer_async: enqueue the frame's G-buffer (width * height records of
+        abi.GBUFFER_DTYPE) into device memory; ordered on the stream, nothing to wait for."""
+        push = np.ascontiguousarray(push, dtype=PUSH_DTYPE)
+        self._check(self._lib.rvcp_render_gbuffer_async(
+            self._ctx, abi.ptr(push), width, height, ctypes.c_void_p(d_gbuffer),
+            ctypes.c_void_p(stream) if stream else None))
+
+    def denoise_async(self, d_linear_in: int, d_gbuffer: int, width, height, d_linear_out: int,
+                      d_rgba: int = 0, params=None, stream: int = 0):
+        """rvcp_denoise_async: enqueue the a-trous filter of a linear-RGB frame in device memory
+        under a G-buffer; the filtered floats go to d_linear_out (no overlap with the input) and,
+        when given, their gamma / UNORM8 bytes to d_rgba.  Wait with denoise_wait()."""
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=abi.DENOISE_PARAMS_DTYPE)
+        self._check(self._lib.rvcp_denoise_async(
+            self._ctx, ctypes.c_void_p(d_linear_in), ctypes.c_void_p(d_gbuffer), width, height,
+            abi.ptr(params), ctypes.c_void_p(d_linear_out),
+            ctypes.c_void_p(d_rgba) if d_rgba else None,
+            ctypes.c_void_p(stream) if stream else None))
+
+    def denoise_wait(self) -> float:
+        """rvcp_denoise_wait: block until the last denoise_async is done; its device time, ms."""
+        ms = ctypes.c_float(0.0)
+        self._check(self._lib.rvcp_denoise_wait(self._ctx, ctypes.cast(ctypes.byref(ms),
+                                                                       ctypes.c_void_p)))
+        return float(ms.value)
 
     def wait(self):
         """rvcp_wait: block until the last async render is done; returns its stats."""
