@@ -269,6 +269,31 @@ typedef struct rvcp_denoise_params {
     float sigma_plane;            /* plane-distance edge-stopping width, world units, > 0 */
 } rvcp_denoise_params_t;
 
+/* Temporal reprojection and accumulation.  No counterpart in the reference:
+ * each of its frames starts from nothing. */
+#define RVCP_TEMPORAL_MAX_HISTORY 65535u
+#define RVCP_TEMPORAL_DENOISE     1u     /* rvcp_render_temporal flags: filter the displayed frame */
+
+/* Parameters of rvcp_temporal_accumulate_async (the rule's definition: DESIGN.md §4.10). */
+typedef struct rvcp_temporal_params {
+    float alpha_min;        /* lower bound of the blend factor, 0..1 */
+    uint32_t max_history;   /* cap of the per-pixel history length, 1..65535 */
+    float sigma_plane;      /* a history tap is accepted within this distance of the pixel's
+                               tangent plane, world units, > 0 */
+    float normal_min;       /* ... and when n_p . n_q >= normal_min, -1..1 */
+} rvcp_temporal_params_t;
+
+/* The PREVIOUS frame's camera, ready to project a world point x into its pixel grid
+ * (rvcp_temporal_view_from_push): with e = x - position and z = e . forward, the point lies at
+ * pixel (e . right / z * k + W / 2 - 1/2, e . down / z * k + H / 2 - 1/2), pixel centres at the
+ * integers -- the inverse of the shader's sample_ray (ray_tracer_games101_branch.comp:217-235). */
+typedef struct rvcp_temporal_view {
+    float position[3]; float k;         /* k = H / (2 tan(vfov/2 * PI/180)): pixels per unit slope */
+    float right[3];    float _pad0;     /* normalize(forward x up) */
+    float down[3];     float _pad1;     /* normalize(forward x right)  (sample_ray's v points down) */
+    float forward[3];  float _pad2;     /* forward / (forward . forward) */
+} rvcp_temporal_view_t;
+
 /* Layout checks: sizes/offsets the reference's Rust structs and std140/std430 blocks imply. */
 #ifdef __cplusplus
 #define RVCP_STATIC_ASSERT(c, m) static_assert(c, m)
@@ -295,6 +320,15 @@ RVCP_STATIC_ASSERT(offsetof(rvcp_gbuffer_texel_t, face) == 12, "GBuffer.face @12
 RVCP_STATIC_ASSERT(offsetof(rvcp_gbuffer_texel_t, normal) == 16, "GBuffer.normal @16");
 RVCP_STATIC_ASSERT(offsetof(rvcp_gbuffer_texel_t, material) == 28, "GBuffer.material @28");
 RVCP_STATIC_ASSERT(sizeof(rvcp_denoise_params_t) == 16, "denoise params are 16 B");
+RVCP_STATIC_ASSERT(sizeof(rvcp_temporal_params_t) == 16, "temporal params are 16 B");
+RVCP_STATIC_ASSERT(offsetof(rvcp_temporal_params_t, max_history) == 4, "TemporalParams.max_history @4");
+RVCP_STATIC_ASSERT(offsetof(rvcp_temporal_params_t, sigma_plane) == 8, "TemporalParams.sigma_plane @8");
+RVCP_STATIC_ASSERT(offsetof(rvcp_temporal_params_t, normal_min) == 12, "TemporalParams.normal_min @12");
+RVCP_STATIC_ASSERT(sizeof(rvcp_temporal_view_t) == 64, "temporal view is 64 B");
+RVCP_STATIC_ASSERT(offsetof(rvcp_temporal_view_t, k) == 12, "TemporalView.k @12");
+RVCP_STATIC_ASSERT(offsetof(rvcp_temporal_view_t, right) == 16, "TemporalView.right @16");
+RVCP_STATIC_ASSERT(offsetof(rvcp_temporal_view_t, down) == 32, "TemporalView.down @32");
+RVCP_STATIC_ASSERT(offsetof(rvcp_temporal_view_t, forward) == 48, "TemporalView.forward @48");
 
 typedef struct rvcp_ctx rvcp_ctx_t;
 
@@ -595,6 +629,72 @@ int rvcp_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push,
                          uint32_t width, uint32_t height, const rvcp_denoise_params_t *params,
                          uint8_t *out_rgba8, float *out_linear_rgb, rvcp_stats_t *stats,
                          float *denoise_ms);
+
+/* ---------------------------------------------------------------------------------------
+ * Temporal reprojection and accumulation of frames across calls (opt-in; no other entry point
+ * changes).  No counterpart in the reference.
+ * ------------------------------------------------------------------------------------- */
+
+/* The default parameters: alpha_min 0.05, max_history 32, sigma_plane 0.1, normal_min 0.9.
+ * Needs no device. */
+int rvcp_temporal_params_default(rvcp_temporal_params_t *params);
+
+/* The projection of `push`'s camera for a width x height frame, computed in double and rounded
+ * once to float (PI = 3.1415926, the shader's constant).  Needs no device.  RVCP_E_INVALID:
+ * NULL / zero arguments, or a camera whose forward is zero or parallel to up. */
+int rvcp_temporal_view_from_push(const rvcp_push_constant_t *push, uint32_t width, uint32_t height,
+                                 rvcp_temporal_view_t *out_view);
+
+/* Enqueue one accumulation step on `stream`; stateless, every buffer is the caller's device
+ * memory.  d_cur_linear (W*H*3 floats) and d_cur_gbuffer (W*H texels) are the current frame;
+ * d_prev_linear, d_prev_gbuffer and d_prev_len (W*H uint32_t) the accumulated previous frame, its
+ * G-buffer and its per-pixel history lengths -- all three NULL: no history, every filterable
+ * pixel starts one.  `view` is the previous frame's camera (rvcp_temporal_view_from_push); NULL
+ * means the camera did not move and pixel p continues the history of pixel p.  Written:
+ * d_out_linear (W*H*3 floats), d_out_len (W*H uint32_t: 0 on a non-filterable pixel, which passes
+ * through; 1 where a history starts) and, when d_rgba8_out is not NULL, pow(clamp(c), 0.6) of the
+ * result as RGBA8 under the context's unorm_rule, exactly as the render stores its own frame.
+ * All arithmetic is single correctly rounded f32 operations in a fixed order,
+ * so the result is reproducible bit for bit.  params = NULL: the defaults.  Needs no scene.  A
+ * render pending on the context is not an error: the step is ordered behind it, and behind the
+ * context's previous step.
+ * RVCP_E_INVALID: NULL / zero arguments, an output that overlaps an input or another output,
+ * some but not all of d_prev_*, alpha_min outside 0..1, max_history outside 1..65535,
+ * sigma_plane not > 0, normal_min outside -1..1 (a NaN is outside every range). */
+int rvcp_temporal_accumulate_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *view,
+                                   const void *d_cur_linear, const void *d_cur_gbuffer,
+                                   const void *d_prev_linear, const void *d_prev_gbuffer,
+                                   const void *d_prev_len, uint32_t width, uint32_t height,
+                                   const rvcp_temporal_params_t *params, void *d_out_linear,
+                                   void *d_out_len, void *d_rgba8_out, void *stream);
+
+/* Wait for the context's last rvcp_temporal_accumulate_async; *temporal_ms (optional) gets its
+ * device time, kernel to the RGBA8 store (HIP events on its stream).  RVCP_E_INVALID when no
+ * step was enqueued since the last call. */
+int rvcp_temporal_wait(rvcp_ctx_t *ctx, float *temporal_ms);
+
+/* Render + G-buffer + accumulation [+ filter] of one frame, synchronously into host memory, on
+ * the context's stream and in buffers the context owns.  The context keeps the accumulated
+ * frame, its history lengths and its G-buffer from call to call, with the camera they were
+ * rendered from; the next call reprojects through that camera, or continues pixel by pixel when
+ * the 64 camera bytes of `push` equal the previous call's.  The history is dropped (every
+ * filterable pixel restarts at length 1) on the first call, when width or height change, on
+ * rvcp_upload_scene / rvcp_upload_scene_file and on rvcp_temporal_reset.
+ * flags & RVCP_TEMPORAL_DENOISE: the displayed frame is rvcp_denoise_async(dparams) of the
+ * accumulated one; the history keeps the unfiltered accumulation.
+ * out_rgba8 (W*H*4 bytes) and out_linear_rgb (optional, W*H*3 floats) are the displayed frame,
+ * out_history_len (optional, W*H uint32_t) the history lengths; stats (optional) are the
+ * render's; *temporal_ms / *denoise_ms (optional) as rvcp_temporal_wait / rvcp_denoise_wait
+ * (denoise_ms is 0 without the flag).  tparams / dparams = NULL: the defaults.
+ * Restrictions of rvcp_render_gbuffer_async. */
+int rvcp_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push,
+                         uint32_t width, uint32_t height, const rvcp_temporal_params_t *tparams,
+                         uint32_t flags, const rvcp_denoise_params_t *dparams,
+                         uint8_t *out_rgba8, float *out_linear_rgb, uint32_t *out_history_len,
+                         rvcp_stats_t *stats, float *temporal_ms, float *denoise_ms);
+
+/* Drop the history rvcp_render_temporal keeps on the context. */
+int rvcp_temporal_reset(rvcp_ctx_t *ctx);
 
 #ifdef __cplusplus
 }

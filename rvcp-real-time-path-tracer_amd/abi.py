@@ -34,6 +34,16 @@ DENOISE_PARAMS_DTYPE = np.dtype([("iterations", "<u4"), ("normal_power_log2", "<
 assert GBUFFER_DTYPE.itemsize == 32 and DENOISE_PARAMS_DTYPE.itemsize == 16
 GBUFFER_MISS, GBUFFER_EMISSIVE = 0xFFFFFFFF, 0x80000000
 DENOISE_MAX_ITERATIONS = 8
+# rvcp_temporal_params_t / rvcp_temporal_view_t (temporal accumulation)
+TEMPORAL_PARAMS_DTYPE = np.dtype([("alpha_min", "<f4"), ("max_history", "<u4"),
+                                  ("sigma_plane", "<f4"), ("normal_min", "<f4")])
+TEMPORAL_VIEW_DTYPE = np.dtype([("position", "<f4", (3,)), ("k", "<f4"),
+                                ("right", "<f4", (3,)), ("_pad0", "<f4"),
+                                ("down", "<f4", (3,)), ("_pad1", "<f4"),
+                                ("forward", "<f4", (3,)), ("_pad2", "<f4")])
+assert TEMPORAL_PARAMS_DTYPE.itemsize == 16 and TEMPORAL_VIEW_DTYPE.itemsize == 64
+TEMPORAL_MAX_HISTORY = 65535
+TEMPORAL_DENOISE = 1            # rvcp_render_temporal flags
 # rvcp_stats_t.kernel_variant -> the dominant kernel's name as rocprofv3 reports it
 KERNEL_NAMES = {1: "games101_kernel", 2: "games101_dual_kernel", 3: "games101_path_kernel<5>",
                 4: "games101_tiled_kernel", 5: "games101_tiled_single_kernel",
@@ -65,7 +75,10 @@ EXPORTED = ["rvcp_version", "rvcp_config_default", "rvcp_config_default_for", "r
             "rvcp_gather_wait", "rvcp_render_frames_async", "rvcp_rccl_set_timeout",
             "rvcp_abi_version", "rvcp_set_code_cache_dir", "rvcp_code_cache_counts",
             "rvcp_render_gbuffer_async", "rvcp_denoise_params_default", "rvcp_denoise_async",
-            "rvcp_denoise_wait", "rvcp_render_denoised"]
+            "rvcp_denoise_wait", "rvcp_render_denoised",
+            "rvcp_temporal_params_default", "rvcp_temporal_view_from_push",
+            "rvcp_temporal_accumulate_async", "rvcp_temporal_wait", "rvcp_render_temporal",
+            "rvcp_temporal_reset"]
 
 
 # Integrator mode 2 (ray_tracer.comp ray_trace): its own #defines (ray_tracer.comp:5-13).
@@ -100,6 +113,30 @@ def make_denoise_params(**overrides) -> np.ndarray:
     for k, v in overrides.items():
         p[k] = v
     return p
+
+
+def make_temporal_params(**overrides) -> np.ndarray:
+    """rvcp_temporal_params_t with the library's defaults (rvcp_temporal_params_default),
+    overridden by the keyword arguments."""
+    p = np.zeros((), dtype=TEMPORAL_PARAMS_DTYPE)
+    rc = load().rvcp_temporal_params_default(ptr(p))
+    if rc != RVCP_OK:
+        raise RvcpError(rc, "rvcp_temporal_params_default failed")
+    for k, v in overrides.items():
+        p[k] = v
+    return p
+
+
+def temporal_view(push, width: int, height: int) -> np.ndarray:
+    """rvcp_temporal_view_from_push: the camera of a push constant as rvcp_temporal_view_t, the
+    `view` of the NEXT frame's rvcp_temporal_accumulate_async."""
+    from .scene import PUSH_DTYPE
+    push = np.ascontiguousarray(push, dtype=PUSH_DTYPE)
+    v = np.zeros((), dtype=TEMPORAL_VIEW_DTYPE)
+    rc = load().rvcp_temporal_view_from_push(ptr(push), width, height, ptr(v))
+    if rc != RVCP_OK:
+        raise RvcpError(rc, "rvcp_temporal_view_from_push failed")
+    return v
 
 
 class RvcpError(RuntimeError):
@@ -176,6 +213,12 @@ def load():
     L.rvcp_denoise_async.argtypes = [P, P, P, u32, u32, P, P, P, P]
     L.rvcp_denoise_wait.argtypes = [P, P]
     L.rvcp_render_denoised.argtypes = [P, P, u32, u32, P, P, P, P, P]
+    L.rvcp_temporal_params_default.argtypes = [P]
+    L.rvcp_temporal_view_from_push.argtypes = [P, u32, u32, P]
+    L.rvcp_temporal_accumulate_async.argtypes = [P, P, P, P, P, P, P, u32, u32, P, P, P, P, P]
+    L.rvcp_temporal_wait.argtypes = [P, P]
+    L.rvcp_render_temporal.argtypes = [P, P, u32, u32, P, u32, P, P, P, P, P, P, P]
+    L.rvcp_temporal_reset.argtypes = [P]
     for name in ("rvcp_config_default", "rvcp_config_default_for", "rvcp_create", "rvcp_destroy", "rvcp_upload_scene",
                  "rvcp_render", "rvcp_render_shard_async", "rvcp_sync_stats",
                  "rvcp_assemble_frame_async", "rvcp_upload_scene_file", "rvcp_mandelbrot",
@@ -184,7 +227,9 @@ def load():
                  "rvcp_render_frames_async", "rvcp_rccl_set_timeout", "rvcp_set_code_cache_dir",
                  "rvcp_code_cache_counts", "rvcp_render_gbuffer_async",
                  "rvcp_denoise_params_default", "rvcp_denoise_async", "rvcp_denoise_wait",
-                 "rvcp_render_denoised"):
+                 "rvcp_render_denoised", "rvcp_temporal_params_default",
+                 "rvcp_temporal_view_from_push", "rvcp_temporal_accumulate_async",
+                 "rvcp_temporal_wait", "rvcp_render_temporal", "rvcp_temporal_reset"):
         getattr(L, name).restype = ctypes.c_int
     if L.rvcp_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI revision {L.rvcp_abi_version()}, this binding "

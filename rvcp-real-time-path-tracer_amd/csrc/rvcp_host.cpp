@@ -140,6 +140,23 @@ struct rvcp_ctx {
     float *d_dn_in = nullptr, *d_dn_out = nullptr;
     size_t cap_gbuf = 0, cap_dn_io = 0;
 
+    // temporal accumulation (rvcp_temporal_accumulate_async): evt0 / evt1 bracket the last step
+    // on its stream (created by the first call).  rvcp_render_temporal keeps its history here:
+    // accumulated colour, history length and G-buffer ping-pong between slots tp_slot (the
+    // previous frame) and tp_slot ^ 1; d_tp_cur is the raw frame, d_tp_show the filtered one.
+    hipEvent_t evt0 = nullptr, evt1 = nullptr;
+    bool temporal_recorded = false;     // evt1 has been recorded at least once
+    bool temporal_pending = false;      // ... and not yet waited for with rvcp_temporal_wait
+    float *d_tp_lin[2] = {nullptr, nullptr};
+    uint32_t *d_tp_len[2] = {nullptr, nullptr};
+    void *d_tp_gbuf[2] = {nullptr, nullptr};
+    float *d_tp_cur = nullptr, *d_tp_show = nullptr;
+    size_t cap_tp = 0, cap_tp_show = 0;
+    uint32_t tp_slot = 0, tp_width = 0, tp_height = 0;
+    bool tp_valid = false;              // slot tp_slot holds a frame of tp_width x tp_height
+    rvcp_camera_t tp_camera = {};       // ... rendered from this camera
+    rvcp_temporal_view_t tp_view = {};  // ... whose projection this is
+
     // debug build: per-wave timeline of the path kernel appended per render
     unsigned long long *d_timeline = nullptr;
     size_t cap_timeline = 0, last_timeline_waves = 0;
@@ -589,6 +606,7 @@ static int impl_destroy(rvcp_ctx_t *ctx)
     }
     // a filter still in flight (possibly on the caller's stream) reads the buffers freed below
     if (ctx->denoise_recorded) (void)hipEventSynchronize(ctx->evd1);
+    if (ctx->temporal_recorded) (void)hipEventSynchronize(ctx->evt1);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm && ctx->comm_owned) (void)rccl_api().comm_destroy(ctx->comm);
     ctx->comm = nullptr;
@@ -612,6 +630,15 @@ static int impl_destroy(rvcp_ctx_t *ctx)
     (void)hipFree(ctx->d_gbuf);
     (void)hipFree(ctx->d_dn_in);
     (void)hipFree(ctx->d_dn_out);
+    for (int i = 0; i < 2; ++i) {
+        (void)hipFree(ctx->d_tp_lin[i]);
+        (void)hipFree(ctx->d_tp_len[i]);
+        (void)hipFree(ctx->d_tp_gbuf[i]);
+    }
+    (void)hipFree(ctx->d_tp_cur);
+    (void)hipFree(ctx->d_tp_show);
+    if (ctx->evt0) (void)hipEventDestroy(ctx->evt0);
+    if (ctx->evt1) (void)hipEventDestroy(ctx->evt1);
     if (ctx->evd0) (void)hipEventDestroy(ctx->evd0);
     if (ctx->evd1) (void)hipEventDestroy(ctx->evd1);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -641,6 +668,7 @@ static int impl_upload_scene(rvcp_ctx_t *ctx, const rvcp_material_t *materials, 
                       const uint32_t *lum_sphere_ids, uint32_t n_lum_sphere_ids)
 {
     if (!ctx) return RVCP_E_INVALID;
+    ctx->tp_valid = false;      // rvcp_render_temporal: another scene, no history
     int rc = upload_one(ctx, materials, n_materials, vertices, n_vertices, faces, n_faces,
                         spheres, n_spheres, lum_face_ids, n_lum_face_ids, lum_sphere_ids,
                         n_lum_sphere_ids);
@@ -1554,6 +1582,246 @@ static int impl_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
     return RVCP_OK;
 }
 
+// ---- temporal reprojection and accumulation -----------------------------
+
+static int impl_temporal_params_default(rvcp_temporal_params_t *params)
+{
+    if (!params) return RVCP_E_INVALID;
+    params->alpha_min = 0.05f;
+    params->max_history = 32;
+    params->sigma_plane = 0.1f;       // the denoiser's plane-distance width
+    params->normal_min = 0.9f;
+    return RVCP_OK;
+}
+
+// The camera of `push` as the kernel projects through it: the inverse of sample_ray
+// (ray_tracer_games101_branch.comp:217-235).  Its u points along normalize(forward x up), its v
+// along normalize(forward x u) (down the image), and a pixel centre lies at slope
+// (px + 1/2 - W/2) / k, k = H / (2 tan(vfov/2 * PI/180)), in both directions (w = h W / H).
+// Everything in double, each output rounded once.
+static int impl_temporal_view_from_push(const rvcp_push_constant_t *push, uint32_t width,
+                                        uint32_t height, rvcp_temporal_view_t *out)
+{
+    if (!push || !out || width == 0 || height == 0) return RVCP_E_INVALID;
+    const rvcp_camera_t &c = push->camera;
+    const double f[3] = {c.forward[0], c.forward[1], c.forward[2]};
+    const double up[3] = {c.up[0], c.up[1], c.up[2]};
+    double r[3] = {f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]};
+    const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    const double ff = f[0] * f[0] + f[1] * f[1] + f[2] * f[2];
+    if (!(rl > 0.0) || !(ff > 0.0)) return RVCP_E_INVALID;
+    for (double &v : r) v /= rl;
+    double d[3] = {f[1] * r[2] - f[2] * r[1], f[2] * r[0] - f[0] * r[2], f[0] * r[1] - f[1] * r[0]};
+    const double dl = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    if (!(dl > 0.0)) return RVCP_E_INVALID;
+    const double PI = 3.1415926;      // the shader's constant (:15)
+    const double k = (double)height / (2.0 * std::tan((double)c.vertical_fov / 2.0 * PI / 180.0));
+    std::memset(out, 0, sizeof(*out));
+    for (int i = 0; i < 3; ++i) {
+        out->position[i] = c.position[i];
+        out->right[i] = (float)r[i];
+        out->down[i] = (float)(d[i] / dl);
+        out->forward[i] = (float)(f[i] / ff);
+    }
+    out->k = (float)k;
+    return RVCP_OK;
+}
+
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && x < y + nb && y < x + na;
+}
+
+static int impl_temporal_accumulate_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *view,
+                                          const void *d_cur, const void *d_cur_g,
+                                          const void *d_prev, const void *d_prev_g,
+                                          const void *d_prev_len, uint32_t width, uint32_t height,
+                                          const rvcp_temporal_params_t *params, void *d_out,
+                                          void *d_out_len, void *d_rgba8_out, void *stream)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!d_cur || !d_cur_g || !d_out || !d_out_len || width == 0 || height == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid temporal arguments");
+    if ((uint64_t)width * height >= (1ull << 31))
+        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    const int n_prev = (d_prev ? 1 : 0) + (d_prev_g ? 1 : 0) + (d_prev_len ? 1 : 0);
+    if (n_prev != 0 && n_prev != 3)
+        return fail(ctx, RVCP_E_INVALID, "temporal history needs d_prev_linear, d_prev_gbuffer "
+                    "and d_prev_len together");
+    rvcp_temporal_params_t P;
+    if (params) P = *params;
+    else (void)impl_temporal_params_default(&P);
+    // (negated compares: a NaN is rejected too)
+    if (!(P.alpha_min >= 0.0f && P.alpha_min <= 1.0f))
+        return fail(ctx, RVCP_E_INVALID, "temporal alpha_min must be in 0..1");
+    if (P.max_history < 1 || P.max_history > RVCP_TEMPORAL_MAX_HISTORY)
+        return fail(ctx, RVCP_E_INVALID, "temporal max_history must be in 1..65535");
+    if (!(P.sigma_plane > 0.0f))
+        return fail(ctx, RVCP_E_INVALID, "temporal sigma_plane must be > 0");
+    if (!(P.normal_min >= -1.0f && P.normal_min <= 1.0f))
+        return fail(ctx, RVCP_E_INVALID, "temporal normal_min must be in -1..1");
+    const size_t npx = (size_t)width * height;
+    {   // a lane reads its neighbours' history, and the frames are not the caller's to lose: no
+        // output may overlap an input or another output
+        const struct { const void *p; size_t n; } in[5] = {
+            {d_cur, npx * 12}, {d_cur_g, npx * 32}, {d_prev, npx * 12}, {d_prev_g, npx * 32},
+            {d_prev_len, npx * 4}};
+        const struct { const void *p; size_t n; } out[3] = {
+            {d_out, npx * 12}, {d_out_len, npx * 4}, {d_rgba8_out, npx * 4}};
+        for (int o = 0; o < 3; ++o) {
+            for (int i = 0; i < 5; ++i)
+                if (ranges_overlap(out[o].p, out[o].n, in[i].p, in[i].n))
+                    return fail(ctx, RVCP_E_INVALID, "temporal output overlaps an input");
+            for (int q = o + 1; q < 3; ++q)
+                if (ranges_overlap(out[o].p, out[o].n, out[q].p, out[q].n))
+                    return fail(ctx, RVCP_E_INVALID, "temporal outputs overlap each other");
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if (!ctx->evt0) {
+        HIP_TRY(ctx, hipEventCreate(&ctx->evt0));
+        HIP_TRY(ctx, hipEventCreate(&ctx->evt1));
+    }
+    // behind a render pending on this context (when it runs on another stream), and behind the
+    // context's previous step, whose outputs are usually this one's history
+    if (ctx->pending && ctx->render_stream != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev1, 0));
+    if (ctx->temporal_recorded) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evt1, 0));
+    HIP_TRY(ctx, hipEventRecord(ctx->evt0, s));
+    const uint32_t mode = n_prev == 0 ? 0u : view ? 2u : 1u;
+    if (rvcp_launch_temporal((const float *)d_cur, d_cur_g, (const float *)d_prev, d_prev_g,
+                             (const uint32_t *)d_prev_len, (float *)d_out, (uint32_t *)d_out_len,
+                             width, height, mode, view, &P, s) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string("temporal launch failed: ") +
+                                         hipGetErrorString(hipGetLastError()));
+    if (d_rgba8_out &&
+        rvcp_launch_tonemap((const float *)d_out, (uint32_t)npx, ctx->d_gamma,
+                            (uint32_t *)d_rgba8_out, s) != 0)
+        return fail(ctx, RVCP_E_HIP, "temporal tone-map launch failed");
+    HIP_TRY(ctx, hipEventRecord(ctx->evt1, s));
+    ctx->temporal_recorded = true;
+    ctx->temporal_pending = true;
+    return RVCP_OK;
+}
+
+static int impl_temporal_wait(rvcp_ctx_t *ctx, float *temporal_ms)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!ctx->temporal_pending) return fail(ctx, RVCP_E_INVALID, "no temporal step in flight");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->evt1));
+    if (temporal_ms) HIP_TRY(ctx, hipEventElapsedTime(temporal_ms, ctx->evt0, ctx->evt1));
+    ctx->temporal_pending = false;
+    return RVCP_OK;
+}
+
+static int impl_temporal_reset(rvcp_ctx_t *ctx)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    ctx->tp_valid = false;
+    return RVCP_OK;
+}
+
+static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                                uint32_t height, const rvcp_temporal_params_t *tparams,
+                                uint32_t flags, const rvcp_denoise_params_t *dparams,
+                                uint8_t *out_rgba8, float *out_linear_rgb,
+                                uint32_t *out_history_len, rvcp_stats_t *stats, float *temporal_ms,
+                                float *denoise_ms)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!push || !out_rgba8 || width == 0 || height == 0 ||
+        (uint64_t)width * height >= (1ull << 31) || (flags & ~RVCP_TEMPORAL_DENOISE))
+        return fail(ctx, RVCP_E_INVALID, "invalid render_temporal arguments");
+    if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
+        return fail(ctx, RVCP_E_UNSUPPORTED, "the G-buffer is implemented for the games101 integrator");
+    if (!ctx->subs.empty())
+        return fail(ctx, RVCP_E_UNSUPPORTED, "render_temporal drives one GPU (n_gpus = 1)");
+    if (ctx->pending)
+        return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    rvcp_temporal_view_t view_now;
+    if (impl_temporal_view_from_push(push, width, height, &view_now) != RVCP_OK)
+        return fail(ctx, RVCP_E_INVALID, "render_temporal: the camera's forward is zero or parallel to up");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool denoise = (flags & RVCP_TEMPORAL_DENOISE) != 0;
+    const size_t npx = (size_t)width * height;
+    int rc;
+    if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, npx, 4)) != RVCP_OK) return rc;
+    if (ctx->cap_tp < npx) {            // (a larger frame: the history is dropped with its buffers)
+        ctx->tp_valid = false;
+        ctx->cap_tp = 0;
+        for (int i = 0; i < 2; ++i) {
+            (void)hipFree(ctx->d_tp_lin[i]);
+            (void)hipFree(ctx->d_tp_len[i]);
+            (void)hipFree(ctx->d_tp_gbuf[i]);
+            ctx->d_tp_lin[i] = nullptr;
+            ctx->d_tp_len[i] = nullptr;
+            ctx->d_tp_gbuf[i] = nullptr;
+        }
+        (void)hipFree(ctx->d_tp_cur);
+        ctx->d_tp_cur = nullptr;
+        for (int i = 0; i < 2; ++i) {
+            HIP_TRY(ctx, hipMalloc((void **)&ctx->d_tp_lin[i], npx * 12));
+            HIP_TRY(ctx, hipMalloc((void **)&ctx->d_tp_len[i], npx * 4));
+            HIP_TRY(ctx, hipMalloc(&ctx->d_tp_gbuf[i], npx * sizeof(rvcp_gbuffer_texel_t)));
+        }
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_tp_cur, npx * 12));
+        ctx->cap_tp = npx;
+    }
+    if (denoise &&
+        (rc = grow(ctx, (void **)&ctx->d_tp_show, &ctx->cap_tp_show, npx, 12)) != RVCP_OK)
+        return rc;
+    const bool have = ctx->tp_valid && ctx->tp_width == width && ctx->tp_height == height;
+    const bool same_camera = have && std::memcmp(&ctx->tp_camera, &push->camera, sizeof(rvcp_camera_t)) == 0;
+    const uint32_t prev = ctx->tp_slot, cur = prev ^ 1u;
+    ctx->tp_valid = false;              // until this frame is complete
+    // render (raw linear frame), G-buffer, accumulation [, filter], in this order on the context's
+    // stream; the last RGBA8 store overwrites the render's
+    if ((rc = rvcp_render_async(ctx, push, width, height, ctx->d_rgba, ctx->d_tp_cur, ctx->stream)) != RVCP_OK)
+        return rc;
+    bool step_enqueued = false, filter_enqueued = false;
+    rc = impl_render_gbuffer_async(ctx, push, width, height, ctx->d_tp_gbuf[cur], ctx->stream);
+    if (rc == RVCP_OK) {
+        rc = impl_temporal_accumulate_async(
+            ctx, same_camera ? nullptr : &ctx->tp_view, ctx->d_tp_cur, ctx->d_tp_gbuf[cur],
+            have ? ctx->d_tp_lin[prev] : nullptr, have ? ctx->d_tp_gbuf[prev] : nullptr,
+            have ? ctx->d_tp_len[prev] : nullptr, width, height, tparams, ctx->d_tp_lin[cur],
+            ctx->d_tp_len[cur], denoise ? nullptr : ctx->d_rgba, ctx->stream);
+        step_enqueued = rc == RVCP_OK;
+    }
+    if (rc == RVCP_OK && denoise) {
+        rc = impl_denoise_async(ctx, ctx->d_tp_lin[cur], ctx->d_tp_gbuf[cur], width, height, dparams,
+                                ctx->d_tp_show, ctx->d_rgba, ctx->stream);
+        filter_enqueued = rc == RVCP_OK;
+    }
+    if (rc != RVCP_OK) {
+        const std::string why = ctx->err;
+        (void)rvcp_wait(ctx, nullptr);          // the render is enqueued: leave nothing pending
+        if (step_enqueued) (void)impl_temporal_wait(ctx, nullptr);
+        if (filter_enqueued) (void)impl_denoise_wait(ctx, nullptr);
+        ctx->err = why;
+        return rc;
+    }
+    if ((rc = rvcp_wait(ctx, stats)) != RVCP_OK) return rc;
+    if ((rc = impl_temporal_wait(ctx, temporal_ms)) != RVCP_OK) return rc;
+    if (denoise_ms) *denoise_ms = 0.0f;
+    if (denoise && (rc = impl_denoise_wait(ctx, denoise_ms)) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, npx * 4, hipMemcpyDeviceToHost));
+    if (out_linear_rgb)
+        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, denoise ? ctx->d_tp_show : ctx->d_tp_lin[cur],
+                               npx * 12, hipMemcpyDeviceToHost));
+    if (out_history_len)
+        HIP_TRY(ctx, hipMemcpy(out_history_len, ctx->d_tp_len[cur], npx * 4, hipMemcpyDeviceToHost));
+    ctx->tp_slot = cur;
+    ctx->tp_width = width;
+    ctx->tp_height = height;
+    ctx->tp_camera = push->camera;
+    ctx->tp_view = view_now;
+    ctx->tp_valid = true;
+    return RVCP_OK;
+}
+
 static int impl_assemble_frame_async(rvcp_ctx_t *ctx, const void *d_gathered, uint32_t slot_rows,
                               uint32_t width, uint32_t height, uint32_t shard_count,
                               void *d_frame, void *stream)
@@ -2059,6 +2327,53 @@ int rvcp_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint
     return barrier(ctx, [&] {
         return impl_render_denoised(ctx, push, width, height, params, out_rgba8, out_linear_rgb,
                                     stats, denoise_ms);
+    });
+}
+
+int rvcp_temporal_params_default(rvcp_temporal_params_t *params)
+{
+    return barrier(nullptr, [&] { return impl_temporal_params_default(params); });
+}
+
+int rvcp_temporal_view_from_push(const rvcp_push_constant_t *push, uint32_t width, uint32_t height,
+                                 rvcp_temporal_view_t *out_view)
+{
+    return barrier(nullptr, [&] { return impl_temporal_view_from_push(push, width, height, out_view); });
+}
+
+int rvcp_temporal_accumulate_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *view,
+                                   const void *d_cur_linear, const void *d_cur_gbuffer,
+                                   const void *d_prev_linear, const void *d_prev_gbuffer,
+                                   const void *d_prev_len, uint32_t width, uint32_t height,
+                                   const rvcp_temporal_params_t *params, void *d_out_linear,
+                                   void *d_out_len, void *d_rgba8_out, void *stream)
+{
+    return barrier(ctx, [&] {
+        return impl_temporal_accumulate_async(ctx, view, d_cur_linear, d_cur_gbuffer, d_prev_linear,
+                                              d_prev_gbuffer, d_prev_len, width, height, params,
+                                              d_out_linear, d_out_len, d_rgba8_out, stream);
+    });
+}
+
+int rvcp_temporal_wait(rvcp_ctx_t *ctx, float *temporal_ms)
+{
+    return barrier(ctx, [&] { return impl_temporal_wait(ctx, temporal_ms); });
+}
+
+int rvcp_temporal_reset(rvcp_ctx_t *ctx)
+{
+    return barrier(ctx, [&] { return impl_temporal_reset(ctx); });
+}
+
+int rvcp_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                         uint32_t height, const rvcp_temporal_params_t *tparams, uint32_t flags,
+                         const rvcp_denoise_params_t *dparams, uint8_t *out_rgba8,
+                         float *out_linear_rgb, uint32_t *out_history_len, rvcp_stats_t *stats,
+                         float *temporal_ms, float *denoise_ms)
+{
+    return barrier(ctx, [&] {
+        return impl_render_temporal(ctx, push, width, height, tparams, flags, dparams, out_rgba8,
+                                    out_linear_rgb, out_history_len, stats, temporal_ms, denoise_ms);
     });
 }
 

@@ -336,6 +336,13 @@ int rvcp_launch_tonemap(const float *lin, uint32_t n, const float *gamma_t, uint
 int rvcp_launch_denoise_pass(const float *in, const void *gbuffer, float *out, uint32_t width,
                              uint32_t height, uint32_t step, uint32_t normal_power_log2,
                              uint32_t use_color, float color_s2, float sigma_plane, void *stream);
+// One temporal accumulation step (rvcp_temporal.hip): mode 0 no history (prev_* unused), 1 the
+// identity mapping, 2 reprojection through *view
+int rvcp_launch_temporal(const float *cur_c, const void *cur_g, const float *prev_c,
+                         const void *prev_g, const uint32_t *prev_len, float *out_c,
+                         uint32_t *out_len, uint32_t width, uint32_t height, uint32_t mode,
+                         const struct rvcp_temporal_view *view,
+                         const struct rvcp_temporal_params *params, void *stream);
 int rvcp_launch_assemble(const uint32_t *gathered, uint32_t slot_rows, uint32_t width,
                          uint32_t height, uint32_t shard_count, uint32_t *frame, void *stream);
 int rvcp_launch_fill(uint32_t *out_rgba, float *out_lin, uint32_t n_pixels, uint32_t rgba,

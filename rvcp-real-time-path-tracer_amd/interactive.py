@@ -156,7 +156,8 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
                  events: Iterable[Event] = (), fixed_dt: Optional[float] = None,
                  time_seed: Optional[Callable[[int], float]] = None,
                  dump_dir: Optional[str] = None, dump_format: str = "ppm",
-                 on_fps: Optional[Callable[[int], None]] = None, denoise=None) -> dict:
+                 on_fps: Optional[Callable[[int], None]] = None, denoise=None,
+                 temporal=None) -> dict:
     """``main_loop`` (ray_tracer.rs:22-100) without a window.
 
     Per frame: apply this frame's scripted events, count FPS (printed once a second as
@@ -165,6 +166,9 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
     with time seed ``time_seed(i)`` or ``unix_secs % 1000``, and optionally dump the frame.
     ``denoise``: an ``abi.make_denoise_params(...)`` record to render every frame through the
     a-trous denoiser (``tracer.render_denoised``); None (default) renders the raw frame.
+    ``temporal``: an ``abi.make_temporal_params(...)`` record to accumulate the frames across the
+    loop (``tracer.render_temporal``, reprojected when the camera moves), with ``denoise``
+    selecting the spatial pass on top of the accumulated frame; None (default): no accumulation.
     Returns per-frame render times and the final camera."""
     info = RuntimeInfo(window_size=(width, height))
     by_frame: Dict[int, List[Event]] = {}
@@ -197,8 +201,11 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
         moved.append(update_camera_state(info, cam, dt))
         t = time_seed(i) if time_seed else float(f32(_time.time() % 1000.0))
         t0 = _time.perf_counter()
-        rgba = (tracer.render(width, height, t) if denoise is None
-                else tracer.render_denoised(width, height, t, denoise))
+        if temporal is not None:
+            rgba = tracer.render_temporal(width, height, t, temporal, denoise)
+        else:
+            rgba = (tracer.render(width, height, t) if denoise is None
+                    else tracer.render_denoised(width, height, t, denoise))
         frame_ms.append((_time.perf_counter() - t0) * 1000.0)
         if dump_dir:
             path = os.path.join(dump_dir, f"frame_{i:05d}.{dump_format}")

@@ -36,6 +36,8 @@ class RayTracer:
         self._ctx = h
         self.scene: Optional[Scene] = None
         self.last_stats = None
+        self.last_temporal_ms = None
+        self.last_denoise_ms = None
         # FPS counter (src/ray_tracer/ray_tracer.rs:80-86)
         self.fps_frame_count = 0
         self.fps_last_time = _time.perf_counter()
@@ -152,6 +154,50 @@ class RayTracer:
         self.last_denoise_ms = float(ms.value)
         return (rgba, lin) if want_linear else rgba
 
+    def render_temporal_push(self, push: np.ndarray, width: int, height: int, params=None,
+                             denoise=None, want_linear: bool = False, want_history: bool = False):
+        """rvcp_render_temporal for an explicit push constant (see render_temporal)."""
+        push = np.ascontiguousarray(push, dtype=PUSH_DTYPE)
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=abi.TEMPORAL_PARAMS_DTYPE)
+        if denoise is not None:
+            denoise = np.ascontiguousarray(denoise, dtype=abi.DENOISE_PARAMS_DTYPE)
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        lin = np.empty((height, width, 3), dtype=np.float32) if want_linear else None
+        hist = np.empty((height, width), dtype=np.uint32) if want_history else None
+        stats = np.zeros((), dtype=abi.STATS_DTYPE)
+        t_ms, d_ms = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        self._check(self._lib.rvcp_render_temporal(
+            self._ctx, abi.ptr(push), width, height, abi.ptr(params),
+            abi.TEMPORAL_DENOISE if denoise is not None else 0, abi.ptr(denoise), abi.ptr(rgba),
+            abi.ptr(lin), abi.ptr(hist), abi.ptr(stats),
+            ctypes.cast(ctypes.byref(t_ms), ctypes.c_void_p),
+            ctypes.cast(ctypes.byref(d_ms), ctypes.c_void_p)))
+        self.last_stats = stats
+        self.last_temporal_ms = float(t_ms.value)
+        self.last_denoise_ms = float(d_ms.value)
+        out = (rgba,) + ((lin,) if want_linear else ()) + ((hist,) if want_history else ())
+        return out if len(out) > 1 else rgba
+
+    def render_temporal(self, width: int, height: int, time: float, params=None, denoise=None,
+                        want_linear: bool = False, want_history: bool = False):
+        """rvcp_render_temporal: one frame rendered and blended into the history the context keeps
+        from call to call, reprojected through the previous call's camera when the scene's camera
+        moved (params: abi.make_temporal_params(...), None = the defaults).  denoise: an
+        abi.make_denoise_params(...) record to show the a-trous filter of the accumulated frame
+        (the history stays unfiltered); None: no spatial pass.  Returns the RGBA8 frame [, its
+        linear RGB] [, the per-pixel history lengths]; last_stats are the render's,
+        last_temporal_ms / last_denoise_ms the device times of the two steps.  The history restarts
+        on a size change, upload_scene and temporal_reset()."""
+        if self.scene is None:
+            raise RuntimeError("upload_scene first")
+        return self.render_temporal_push(push_constant(self.scene.camera, time), width, height,
+                                         params, denoise, want_linear, want_history)
+
+    def temporal_reset(self):
+        """rvcp_temporal_reset: drop the history render_temporal keeps."""
+        self._check(self._lib.rvcp_temporal_reset(self._ctx))
+
     def mandelbrot(self, push: np.ndarray, width: int, height: int, want_value: bool = False):
         """The Mandelbrot operator (rvcp_mandelbrot): grey RGBA8 frame [, escape values]."""
         from .mandelbrot import MANDELBROT_PUSH_DTYPE
@@ -221,6 +267,31 @@ class RayTracer:
         ms = ctypes.c_float(0.0)
         self._check(self._lib.rvcp_denoise_wait(self._ctx, ctypes.cast(ctypes.byref(ms),
                                                                        ctypes.c_void_p)))
+        return float(ms.value)
+
+    def temporal_accumulate_async(self, view, d_cur_linear: int, d_cur_gbuffer: int,
+                                  d_prev_linear: int, d_prev_gbuffer: int, d_prev_len: int,
+                                  width, height, d_out_linear: int, d_out_len: int,
+                                  d_rgba: int = 0, params=None, stream: int = 0):
+        """rvcp_temporal_accumulate_async: enqueue one accumulation step on frames in device
+        memory.  view: the previous frame's abi.temporal_view(...) record, or None when the camera
+        did not move; d_prev_* all 0: no history.  Wait with temporal_wait()."""
+        if view is not None:
+            view = np.ascontiguousarray(view, dtype=abi.TEMPORAL_VIEW_DTYPE)
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=abi.TEMPORAL_PARAMS_DTYPE)
+        P = lambda a: ctypes.c_void_p(a) if a else None   # noqa: E731
+        self._check(self._lib.rvcp_temporal_accumulate_async(
+            self._ctx, abi.ptr(view), P(d_cur_linear), P(d_cur_gbuffer), P(d_prev_linear),
+            P(d_prev_gbuffer), P(d_prev_len), width, height, abi.ptr(params), P(d_out_linear),
+            P(d_out_len), P(d_rgba), P(stream)))
+
+    def temporal_wait(self) -> float:
+        """rvcp_temporal_wait: block until the last temporal_accumulate_async is done; its device
+        time, ms."""
+        ms = ctypes.c_float(0.0)
+        self._check(self._lib.rvcp_temporal_wait(self._ctx, ctypes.cast(ctypes.byref(ms),
+                                                                        ctypes.c_void_p)))
         return float(ms.value)
 
     def wait(self):
