@@ -294,6 +294,28 @@ typedef struct rvcp_temporal_view {
     float forward[3];  float _pad2;     /* forward / (forward . forward) */
 } rvcp_temporal_view_t;
 
+/* Spatiotemporal variance-guided filtering (Schied et al., HPG 2017).  No
+ * counterpart in the reference. */
+#define RVCP_SVGF_MAX_ITERATIONS    8
+#define RVCP_SVGF_MAX_SPATIAL_BELOW 16u
+#define RVCP_SVGF_FEEDBACK          1u   /* rvcp_render_svgf flags: the colour history of the next
+                                            frame is pass 0's output, not the raw accumulation */
+
+/* Parameters of rvcp_svgf_accumulate_async (alpha_moments_min) and rvcp_svgf_filter_async (the
+ * rest); the definitions: DESIGN.md §4.11. */
+typedef struct rvcp_svgf_params {
+    uint32_t iterations;          /* guided a-trous passes, pass i with step 2^i; 1..8 */
+    uint32_t normal_power_log2;   /* w_n = max(0, n_p . n_q) squared this many times; 0..8 */
+    float sigma_luminance;        /* luminance edge-stopping width in standard deviations of the
+                                     pixel's own luminance, > 0; +inf switches the weight off */
+    float sigma_plane;            /* plane-distance edge-stopping width, world units, > 0 */
+    float epsilon;                /* added to sigma_luminance^2 x variance, > 0 */
+    float alpha_moments_min;      /* lower bound of the moments' blend factor, 0..1 */
+    uint32_t spatial_below;       /* a history shorter than this takes the 7 x 7 spatial variance
+                                     estimate; 1..16, 1 = never */
+    uint32_t _pad;                /* must be 0 */
+} rvcp_svgf_params_t;
+
 /* Layout checks: sizes/offsets the reference's Rust structs and std140/std430 blocks imply. */
 #ifdef __cplusplus
 #define RVCP_STATIC_ASSERT(c, m) static_assert(c, m)
@@ -329,6 +351,14 @@ RVCP_STATIC_ASSERT(offsetof(rvcp_temporal_view_t, k) == 12, "TemporalView.k @12"
 RVCP_STATIC_ASSERT(offsetof(rvcp_temporal_view_t, right) == 16, "TemporalView.right @16");
 RVCP_STATIC_ASSERT(offsetof(rvcp_temporal_view_t, down) == 32, "TemporalView.down @32");
 RVCP_STATIC_ASSERT(offsetof(rvcp_temporal_view_t, forward) == 48, "TemporalView.forward @48");
+RVCP_STATIC_ASSERT(sizeof(rvcp_svgf_params_t) == 32, "SVGF params are 32 B");
+RVCP_STATIC_ASSERT(offsetof(rvcp_svgf_params_t, normal_power_log2) == 4, "SvgfParams.normal_power_log2 @4");
+RVCP_STATIC_ASSERT(offsetof(rvcp_svgf_params_t, sigma_luminance) == 8, "SvgfParams.sigma_luminance @8");
+RVCP_STATIC_ASSERT(offsetof(rvcp_svgf_params_t, sigma_plane) == 12, "SvgfParams.sigma_plane @12");
+RVCP_STATIC_ASSERT(offsetof(rvcp_svgf_params_t, epsilon) == 16, "SvgfParams.epsilon @16");
+RVCP_STATIC_ASSERT(offsetof(rvcp_svgf_params_t, alpha_moments_min) == 20, "SvgfParams.alpha_moments_min @20");
+RVCP_STATIC_ASSERT(offsetof(rvcp_svgf_params_t, spatial_below) == 24, "SvgfParams.spatial_below @24");
+RVCP_STATIC_ASSERT(offsetof(rvcp_svgf_params_t, _pad) == 28, "SvgfParams._pad @28");
 
 typedef struct rvcp_ctx rvcp_ctx_t;
 
@@ -695,6 +725,80 @@ int rvcp_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push,
 
 /* Drop the history rvcp_render_temporal keeps on the context. */
 int rvcp_temporal_reset(rvcp_ctx_t *ctx);
+
+/* ---------------------------------------------------------------------------------------
+ * SVGF: per-pixel variance from accumulated luminance moments and a variance-guided a-trous
+ * filter (opt-in; no other entry point changes).  No counterpart in the
+ * reference.
+ * ------------------------------------------------------------------------------------- */
+
+/* The default parameters (chosen by tools/svgf_sweep.py).  Needs no device.
+ * No counterpart in the reference. */
+int rvcp_svgf_params_default(rvcp_svgf_params_t *params);
+
+/* rvcp_temporal_accumulate_async with moments: the same step, colour and length bit for bit,
+ * which also carries the first two moments of the luminance l(c) = 0.2126 r + 0.7152 g +
+ * 0.0722 b through the same taps.  d_prev_moments (W*H pairs of floats) belongs to the
+ * all-or-none d_prev_* set; d_out_moments (W*H pairs) receives (m1, m2): the current frame's
+ * (l, l^2) where a history starts, the history's blended with max(1/n, alpha_moments_min)
+ * where one continues, (0, 0) on a non-filterable pixel.  tparams / sparams = NULL: the
+ * defaults; of sparams only alpha_moments_min is read, but the whole record is validated.
+ * Ordered behind a render pending on the context and behind the context's previous SVGF
+ * accumulation and filter.  RVCP_E_INVALID as rvcp_temporal_accumulate_async, and for SVGF
+ * parameters outside their ranges, NaN, or _pad != 0.  No counterpart in the reference. */
+int rvcp_svgf_accumulate_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *view,
+                               const void *d_cur_linear, const void *d_cur_gbuffer,
+                               const void *d_prev_linear, const void *d_prev_gbuffer,
+                               const void *d_prev_len, const void *d_prev_moments,
+                               uint32_t width, uint32_t height,
+                               const rvcp_temporal_params_t *tparams,
+                               const rvcp_svgf_params_t *sparams, void *d_out_linear,
+                               void *d_out_len, void *d_out_moments, void *d_rgba8_out,
+                               void *stream);
+
+/* Enqueue the variance estimate, the guided passes and the tone map on `stream`: d_linear
+ * (W*H*3 floats), d_moments (W*H pairs) and d_len (W*H uint32_t) as
+ * rvcp_svgf_accumulate_async leaves them, under d_gbuffer (W*H texels).  Written:
+ * d_linear_out (W*H*3 floats), and when not NULL d_variance_out (W*H floats: the variance of
+ * the filtered luminance after the last pass), d_feedback_out (W*H*3 floats: the colour after
+ * pass 0) and d_rgba8_out (pow(clamp(c), 0.6) as RGBA8 under the context's unorm_rule).
+ * Intermediates live in buffers the context owns.  params = NULL: the defaults.  Needs no
+ * scene.  Ordered behind a render pending on the context and behind the context's previous
+ * SVGF accumulation and filter.  RVCP_E_INVALID: NULL / zero arguments, an output that
+ * overlaps an input or another output, parameters outside their ranges, NaN, _pad != 0.
+ * No counterpart in the reference. */
+int rvcp_svgf_filter_async(rvcp_ctx_t *ctx, const void *d_linear, const void *d_moments,
+                           const void *d_len, const void *d_gbuffer, uint32_t width,
+                           uint32_t height, const rvcp_svgf_params_t *params,
+                           void *d_linear_out, void *d_variance_out, void *d_feedback_out,
+                           void *d_rgba8_out, void *stream);
+
+/* Wait for the context's last rvcp_svgf_accumulate_async and / or rvcp_svgf_filter_async;
+ * *accumulate_ms / *filter_ms (optional) get their device times (HIP events on their streams;
+ * 0 for a step that was not enqueued since the last call).  RVCP_E_INVALID when neither was.
+ * No counterpart in the reference. */
+int rvcp_svgf_wait(rvcp_ctx_t *ctx, float *accumulate_ms, float *filter_ms);
+
+/* Render + G-buffer + accumulation with moments + variance + guided filter of one frame,
+ * synchronously into host memory, on the context's stream and in buffers the context owns.
+ * Stateful like rvcp_render_temporal, with a history of its own (colour, moments, length,
+ * G-buffer, camera): the two never touch each other.  The history is dropped on the first
+ * call, when width or height change, on rvcp_upload_scene / rvcp_upload_scene_file, on
+ * rvcp_svgf_reset and when a call fails midway.  flags & RVCP_SVGF_FEEDBACK: the next frame's
+ * colour history is pass 0's output instead of the unfiltered accumulation; moments and
+ * lengths are always unfiltered.  out_rgba8 (W*H*4 bytes), out_linear_rgb (optional, W*H*3
+ * floats) and out_variance (optional, W*H floats) are the filtered frame, out_history_len
+ * (optional, W*H uint32_t) the history lengths; stats (optional) are the render's.
+ * tparams / sparams = NULL: the defaults.  Restrictions of rvcp_render_gbuffer_async.
+ * No counterpart in the reference. */
+int rvcp_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                     uint32_t height, const rvcp_temporal_params_t *tparams,
+                     const rvcp_svgf_params_t *sparams, uint32_t flags, uint8_t *out_rgba8,
+                     float *out_linear_rgb, float *out_variance, uint32_t *out_history_len,
+                     rvcp_stats_t *stats, float *accumulate_ms, float *filter_ms);
+
+/* Drop the history rvcp_render_svgf keeps on the context.  No counterpart in the reference. */
+int rvcp_svgf_reset(rvcp_ctx_t *ctx);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,14 @@ TEMPORAL_VIEW_DTYPE = np.dtype([("position", "<f4", (3,)), ("k", "<f4"),
 assert TEMPORAL_PARAMS_DTYPE.itemsize == 16 and TEMPORAL_VIEW_DTYPE.itemsize == 64
 TEMPORAL_MAX_HISTORY = 65535
 TEMPORAL_DENOISE = 1            # rvcp_render_temporal flags
+# rvcp_svgf_params_t (moments, variance and the variance-guided filter)
+SVGF_PARAMS_DTYPE = np.dtype([("iterations", "<u4"), ("normal_power_log2", "<u4"),
+                              ("sigma_luminance", "<f4"), ("sigma_plane", "<f4"),
+                              ("epsilon", "<f4"), ("alpha_moments_min", "<f4"),
+                              ("spatial_below", "<u4"), ("_pad", "<u4")])
+assert SVGF_PARAMS_DTYPE.itemsize == 32
+SVGF_MAX_ITERATIONS, SVGF_MAX_SPATIAL_BELOW = 8, 16
+SVGF_FEEDBACK = 1               # rvcp_render_svgf flags
 # rvcp_stats_t.kernel_variant -> the dominant kernel's name as rocprofv3 reports it
 KERNEL_NAMES = {1: "games101_kernel", 2: "games101_dual_kernel", 3: "games101_path_kernel<5>",
                 4: "games101_tiled_kernel", 5: "games101_tiled_single_kernel",
@@ -78,7 +86,9 @@ EXPORTED = ["rvcp_version", "rvcp_config_default", "rvcp_config_default_for", "r
             "rvcp_denoise_wait", "rvcp_render_denoised",
             "rvcp_temporal_params_default", "rvcp_temporal_view_from_push",
             "rvcp_temporal_accumulate_async", "rvcp_temporal_wait", "rvcp_render_temporal",
-            "rvcp_temporal_reset"]
+            "rvcp_temporal_reset",
+            "rvcp_svgf_params_default", "rvcp_svgf_accumulate_async", "rvcp_svgf_filter_async",
+            "rvcp_svgf_wait", "rvcp_render_svgf", "rvcp_svgf_reset"]
 
 
 # Integrator mode 2 (ray_tracer.comp ray_trace): its own #defines (ray_tracer.comp:5-13).
@@ -122,6 +132,18 @@ def make_temporal_params(**overrides) -> np.ndarray:
     rc = load().rvcp_temporal_params_default(ptr(p))
     if rc != RVCP_OK:
         raise RvcpError(rc, "rvcp_temporal_params_default failed")
+    for k, v in overrides.items():
+        p[k] = v
+    return p
+
+
+def make_svgf_params(**overrides) -> np.ndarray:
+    """rvcp_svgf_params_t with the library's defaults (rvcp_svgf_params_default), overridden by
+    the keyword arguments (sigma_luminance=float("inf") switches the luminance weight off)."""
+    p = np.zeros((), dtype=SVGF_PARAMS_DTYPE)
+    rc = load().rvcp_svgf_params_default(ptr(p))
+    if rc != RVCP_OK:
+        raise RvcpError(rc, "rvcp_svgf_params_default failed")
     for k, v in overrides.items():
         p[k] = v
     return p
@@ -219,6 +241,12 @@ def load():
     L.rvcp_temporal_wait.argtypes = [P, P]
     L.rvcp_render_temporal.argtypes = [P, P, u32, u32, P, u32, P, P, P, P, P, P, P]
     L.rvcp_temporal_reset.argtypes = [P]
+    L.rvcp_svgf_params_default.argtypes = [P]
+    L.rvcp_svgf_accumulate_async.argtypes = [P, P, P, P, P, P, P, P, u32, u32, P, P, P, P, P, P, P]
+    L.rvcp_svgf_filter_async.argtypes = [P, P, P, P, P, u32, u32, P, P, P, P, P, P]
+    L.rvcp_svgf_wait.argtypes = [P, P, P]
+    L.rvcp_render_svgf.argtypes = [P, P, u32, u32, P, P, u32, P, P, P, P, P, P, P]
+    L.rvcp_svgf_reset.argtypes = [P]
     for name in ("rvcp_config_default", "rvcp_config_default_for", "rvcp_create", "rvcp_destroy", "rvcp_upload_scene",
                  "rvcp_render", "rvcp_render_shard_async", "rvcp_sync_stats",
                  "rvcp_assemble_frame_async", "rvcp_upload_scene_file", "rvcp_mandelbrot",
@@ -229,7 +257,10 @@ def load():
                  "rvcp_denoise_params_default", "rvcp_denoise_async", "rvcp_denoise_wait",
                  "rvcp_render_denoised", "rvcp_temporal_params_default",
                  "rvcp_temporal_view_from_push", "rvcp_temporal_accumulate_async",
-                 "rvcp_temporal_wait", "rvcp_render_temporal", "rvcp_temporal_reset"):
+                 "rvcp_temporal_wait", "rvcp_render_temporal", "rvcp_temporal_reset",
+                 "rvcp_svgf_params_default", "rvcp_svgf_accumulate_async",
+                 "rvcp_svgf_filter_async", "rvcp_svgf_wait", "rvcp_render_svgf",
+                 "rvcp_svgf_reset"):
         getattr(L, name).restype = ctypes.c_int
     if L.rvcp_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI revision {L.rvcp_abi_version()}, this binding "

@@ -157,6 +157,27 @@ struct rvcp_ctx {
     rvcp_camera_t tp_camera = {};       // ... rendered from this camera
     rvcp_temporal_view_t tp_view = {};  // ... whose projection this is
 
+    // SVGF (rvcp_svgf_accumulate_async / rvcp_svgf_filter_async): an event pair
+    // per step; the filter's variance planes (d_sv_var: the estimate and the passes' ping-pong)
+    // and colour intermediates.  rvcp_render_svgf keeps a history of its own, apart from
+    // rvcp_render_temporal's: colour, moments, length and G-buffer ping-pong between slots
+    // sv_slot (the previous frame) and sv_slot ^ 1; d_sv_cur is the raw frame, d_sv_show and
+    // d_sv_showvar the filtered one and its variance, d_sv_fb pass 0's colour (feedback).
+    hipEvent_t evsa0 = nullptr, evsa1 = nullptr, evsf0 = nullptr, evsf1 = nullptr;
+    bool svgf_acc_recorded = false, svgf_acc_pending = false;
+    bool svgf_flt_recorded = false, svgf_flt_pending = false;
+    float *d_sv_var[2] = {nullptr, nullptr}, *d_sv_tmp[2] = {nullptr, nullptr};
+    size_t cap_sv_var[2] = {0, 0}, cap_sv_tmp[2] = {0, 0};
+    float *d_sv_lin[2] = {nullptr, nullptr}, *d_sv_mom[2] = {nullptr, nullptr};
+    uint32_t *d_sv_len[2] = {nullptr, nullptr};
+    void *d_sv_gbuf[2] = {nullptr, nullptr};
+    float *d_sv_cur = nullptr, *d_sv_show = nullptr, *d_sv_showvar = nullptr, *d_sv_fb = nullptr;
+    size_t cap_sv = 0;
+    uint32_t sv_slot = 0, sv_width = 0, sv_height = 0;
+    bool sv_valid = false;              // slot sv_slot holds a frame of sv_width x sv_height
+    rvcp_camera_t sv_camera = {};       // ... rendered from this camera
+    rvcp_temporal_view_t sv_view = {};  // ... whose projection this is
+
     // debug build: per-wave timeline of the path kernel appended per render
     unsigned long long *d_timeline = nullptr;
     size_t cap_timeline = 0, last_timeline_waves = 0;
@@ -607,6 +628,8 @@ static int impl_destroy(rvcp_ctx_t *ctx)
     // a filter still in flight (possibly on the caller's stream) reads the buffers freed below
     if (ctx->denoise_recorded) (void)hipEventSynchronize(ctx->evd1);
     if (ctx->temporal_recorded) (void)hipEventSynchronize(ctx->evt1);
+    if (ctx->svgf_acc_recorded) (void)hipEventSynchronize(ctx->evsa1);
+    if (ctx->svgf_flt_recorded) (void)hipEventSynchronize(ctx->evsf1);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm && ctx->comm_owned) (void)rccl_api().comm_destroy(ctx->comm);
     ctx->comm = nullptr;
@@ -637,6 +660,20 @@ static int impl_destroy(rvcp_ctx_t *ctx)
     }
     (void)hipFree(ctx->d_tp_cur);
     (void)hipFree(ctx->d_tp_show);
+    for (int i = 0; i < 2; ++i) {
+        (void)hipFree(ctx->d_sv_var[i]);
+        (void)hipFree(ctx->d_sv_tmp[i]);
+        (void)hipFree(ctx->d_sv_lin[i]);
+        (void)hipFree(ctx->d_sv_mom[i]);
+        (void)hipFree(ctx->d_sv_len[i]);
+        (void)hipFree(ctx->d_sv_gbuf[i]);
+    }
+    (void)hipFree(ctx->d_sv_cur);
+    (void)hipFree(ctx->d_sv_show);
+    (void)hipFree(ctx->d_sv_showvar);
+    (void)hipFree(ctx->d_sv_fb);
+    for (hipEvent_t e : {ctx->evsa0, ctx->evsa1, ctx->evsf0, ctx->evsf1})
+        if (e) (void)hipEventDestroy(e);
     if (ctx->evt0) (void)hipEventDestroy(ctx->evt0);
     if (ctx->evt1) (void)hipEventDestroy(ctx->evt1);
     if (ctx->evd0) (void)hipEventDestroy(ctx->evd0);
@@ -669,6 +706,7 @@ static int impl_upload_scene(rvcp_ctx_t *ctx, const rvcp_material_t *materials, 
 {
     if (!ctx) return RVCP_E_INVALID;
     ctx->tp_valid = false;      // rvcp_render_temporal: another scene, no history
+    ctx->sv_valid = false;      // rvcp_render_svgf likewise
     int rc = upload_one(ctx, materials, n_materials, vertices, n_vertices, faces, n_faces,
                         spheres, n_spheres, lum_face_ids, n_lum_face_ids, lum_sphere_ids,
                         n_lum_sphere_ids);
@@ -1822,6 +1860,352 @@ static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
     return RVCP_OK;
 }
 
+// ---- SVGF: moments, variance and the variance-guided filter --------------
+
+static int impl_svgf_params_default(rvcp_svgf_params_t *params)
+{
+    if (!params) return RVCP_E_INVALID;
+    // the best row of tools/svgf_sweep.py; spatial_below ties there and takes the SVGF paper's 4
+    // 
+    params->iterations = 3;
+    params->normal_power_log2 = 7;    // the denoiser's
+    params->sigma_luminance = 1.0f;
+    params->sigma_plane = 0.1f;       // the denoiser's plane-distance width
+    params->epsilon = 1.0e-4f;        // the square of a 1 % luminance step
+    params->alpha_moments_min = 0.05f;    // the colour's alpha_min
+    params->spatial_below = 4;
+    params->_pad = 0;
+    return RVCP_OK;
+}
+
+// *out = *params or the defaults, validated (negated compares: a NaN is rejected too)
+static int svgf_params_checked(rvcp_ctx_t *ctx, const rvcp_svgf_params_t *params,
+                               rvcp_svgf_params_t *out)
+{
+    if (params) *out = *params;
+    else (void)impl_svgf_params_default(out);
+    if (out->iterations < 1 || out->iterations > RVCP_SVGF_MAX_ITERATIONS)
+        return fail(ctx, RVCP_E_INVALID, "svgf iterations must be in 1..8");
+    if (out->normal_power_log2 > 8)
+        return fail(ctx, RVCP_E_INVALID, "svgf normal_power_log2 must be in 0..8");
+    if (!(out->sigma_luminance > 0.0f) || !(out->sigma_plane > 0.0f) || !(out->epsilon > 0.0f))
+        return fail(ctx, RVCP_E_INVALID, "svgf sigma_luminance, sigma_plane and epsilon must be > 0");
+    if (!(out->alpha_moments_min >= 0.0f && out->alpha_moments_min <= 1.0f))
+        return fail(ctx, RVCP_E_INVALID, "svgf alpha_moments_min must be in 0..1");
+    if (out->spatial_below < 1 || out->spatial_below > RVCP_SVGF_MAX_SPATIAL_BELOW)
+        return fail(ctx, RVCP_E_INVALID, "svgf spatial_below must be in 1..16");
+    if (out->_pad != 0) return fail(ctx, RVCP_E_INVALID, "svgf _pad must be 0");
+    return RVCP_OK;
+}
+
+struct DevRange { const void *p; size_t n; };
+
+// no output may overlap an input or another output (NULL ranges overlap nothing)
+static bool outputs_overlap(const DevRange *in, int n_in, const DevRange *out, int n_out,
+                            const char **what)
+{
+    for (int o = 0; o < n_out; ++o) {
+        for (int i = 0; i < n_in; ++i)
+            if (ranges_overlap(out[o].p, out[o].n, in[i].p, in[i].n)) {
+                *what = "output overlaps an input";
+                return true;
+            }
+        for (int q = o + 1; q < n_out; ++q)
+            if (ranges_overlap(out[o].p, out[o].n, out[q].p, out[q].n)) {
+                *what = "outputs overlap each other";
+                return true;
+            }
+    }
+    return false;
+}
+
+// the SVGF steps share buffers from call to call: each is ordered behind a render pending on the
+// context (when it runs on another stream) and behind the context's previous accumulation and
+// filter
+static int svgf_order(rvcp_ctx_t *ctx, hipStream_t s)
+{
+    if (ctx->pending && ctx->render_stream != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev1, 0));
+    if (ctx->svgf_acc_recorded) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evsa1, 0));
+    if (ctx->svgf_flt_recorded) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evsf1, 0));
+    return RVCP_OK;
+}
+
+static int impl_svgf_accumulate_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *view,
+                                      const void *d_cur, const void *d_cur_g, const void *d_prev,
+                                      const void *d_prev_g, const void *d_prev_len,
+                                      const void *d_prev_m, uint32_t width, uint32_t height,
+                                      const rvcp_temporal_params_t *tparams,
+                                      const rvcp_svgf_params_t *sparams, void *d_out,
+                                      void *d_out_len, void *d_out_m, void *d_rgba8_out,
+                                      void *stream)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!d_cur || !d_cur_g || !d_out || !d_out_len || !d_out_m || width == 0 || height == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid svgf accumulation arguments");
+    if ((uint64_t)width * height >= (1ull << 31))
+        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    const int n_prev = (d_prev ? 1 : 0) + (d_prev_g ? 1 : 0) + (d_prev_len ? 1 : 0) + (d_prev_m ? 1 : 0);
+    if (n_prev != 0 && n_prev != 4)
+        return fail(ctx, RVCP_E_INVALID, "svgf history needs d_prev_linear, d_prev_gbuffer, "
+                    "d_prev_len and d_prev_moments together");
+    rvcp_temporal_params_t P;
+    if (tparams) P = *tparams;
+    else (void)impl_temporal_params_default(&P);
+    if (!(P.alpha_min >= 0.0f && P.alpha_min <= 1.0f))
+        return fail(ctx, RVCP_E_INVALID, "temporal alpha_min must be in 0..1");
+    if (P.max_history < 1 || P.max_history > RVCP_TEMPORAL_MAX_HISTORY)
+        return fail(ctx, RVCP_E_INVALID, "temporal max_history must be in 1..65535");
+    if (!(P.sigma_plane > 0.0f))
+        return fail(ctx, RVCP_E_INVALID, "temporal sigma_plane must be > 0");
+    if (!(P.normal_min >= -1.0f && P.normal_min <= 1.0f))
+        return fail(ctx, RVCP_E_INVALID, "temporal normal_min must be in -1..1");
+    rvcp_svgf_params_t S;
+    int rc;
+    if ((rc = svgf_params_checked(ctx, sparams, &S)) != RVCP_OK) return rc;
+    const size_t npx = (size_t)width * height;
+    {
+        const DevRange in[6] = {{d_cur, npx * 12}, {d_cur_g, npx * 32}, {d_prev, npx * 12},
+                                {d_prev_g, npx * 32}, {d_prev_len, npx * 4}, {d_prev_m, npx * 8}};
+        const DevRange out[4] = {{d_out, npx * 12}, {d_out_len, npx * 4}, {d_out_m, npx * 8},
+                                 {d_rgba8_out, npx * 4}};
+        const char *what = nullptr;
+        if (outputs_overlap(in, 6, out, 4, &what))
+            return fail(ctx, RVCP_E_INVALID, std::string("svgf accumulation ") + what);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if (!ctx->evsa0) {
+        HIP_TRY(ctx, hipEventCreate(&ctx->evsa0));
+        HIP_TRY(ctx, hipEventCreate(&ctx->evsa1));
+    }
+    if ((rc = svgf_order(ctx, s)) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->evsa0, s));
+    const uint32_t mode = n_prev == 0 ? 0u : view ? 2u : 1u;
+    if (rvcp_launch_svgf_temporal((const float *)d_cur, d_cur_g, (const float *)d_prev, d_prev_g,
+                                  (const uint32_t *)d_prev_len, (const float *)d_prev_m,
+                                  (float *)d_out, (uint32_t *)d_out_len, (float *)d_out_m, width,
+                                  height, mode, view, &P, S.alpha_moments_min, s) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string("svgf accumulation launch failed: ") +
+                                         hipGetErrorString(hipGetLastError()));
+    if (d_rgba8_out &&
+        rvcp_launch_tonemap((const float *)d_out, (uint32_t)npx, ctx->d_gamma,
+                            (uint32_t *)d_rgba8_out, s) != 0)
+        return fail(ctx, RVCP_E_HIP, "svgf accumulation tone-map launch failed");
+    HIP_TRY(ctx, hipEventRecord(ctx->evsa1, s));
+    ctx->svgf_acc_recorded = true;
+    ctx->svgf_acc_pending = true;
+    return RVCP_OK;
+}
+
+static int impl_svgf_filter_async(rvcp_ctx_t *ctx, const void *d_lin, const void *d_mom,
+                                  const void *d_len, const void *d_gbuffer, uint32_t width,
+                                  uint32_t height, const rvcp_svgf_params_t *params, void *d_out,
+                                  void *d_var_out, void *d_fb_out, void *d_rgba8_out, void *stream)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!d_lin || !d_mom || !d_len || !d_gbuffer || !d_out || width == 0 || height == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid svgf filter arguments");
+    if ((uint64_t)width * height >= (1ull << 31))
+        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    rvcp_svgf_params_t P;
+    int rc;
+    if ((rc = svgf_params_checked(ctx, params, &P)) != RVCP_OK) return rc;
+    const size_t npx = (size_t)width * height;
+    {
+        const DevRange in[4] = {{d_lin, npx * 12}, {d_mom, npx * 8}, {d_len, npx * 4},
+                                {d_gbuffer, npx * 32}};
+        const DevRange out[4] = {{d_out, npx * 12}, {d_var_out, npx * 4}, {d_fb_out, npx * 12},
+                                 {d_rgba8_out, npx * 4}};
+        const char *what = nullptr;
+        if (outputs_overlap(in, 4, out, 4, &what))
+            return fail(ctx, RVCP_E_INVALID, std::string("svgf filter ") + what);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if (!ctx->evsf0) {
+        HIP_TRY(ctx, hipEventCreate(&ctx->evsf0));
+        HIP_TRY(ctx, hipEventCreate(&ctx->evsf1));
+    }
+    // variance: the estimate in plane 0, pass i from plane i & 1 into the other one; colour
+    // intermediates from two passes on (pass 0 may write the caller's feedback buffer instead)
+    for (uint32_t b = 0; b < 2; ++b)
+        if ((rc = grow(ctx, (void **)&ctx->d_sv_var[b], &ctx->cap_sv_var[b], npx, 4)) != RVCP_OK)
+            return rc;
+    for (uint32_t b = 0; b < 2 && b + 1 < P.iterations; ++b)
+        if ((rc = grow(ctx, (void **)&ctx->d_sv_tmp[b], &ctx->cap_sv_tmp[b], npx, 12)) != RVCP_OK)
+            return rc;
+    if ((rc = svgf_order(ctx, s)) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->evsf0, s));
+    if (rvcp_launch_svgf_variance((const float *)d_mom, (const uint32_t *)d_len, d_gbuffer,
+                                  ctx->d_sv_var[0], width, height, P.spatial_below,
+                                  P.normal_power_log2, P.sigma_plane, s) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string("svgf variance launch failed: ") +
+                                         hipGetErrorString(hipGetLastError()));
+    const bool use_lum = !std::isinf(P.sigma_luminance);
+    const float sigma_l2 = use_lum ? P.sigma_luminance * P.sigma_luminance : 1.0f;
+    const float *src = (const float *)d_lin;
+    for (uint32_t i = 0; i < P.iterations; ++i) {
+        const bool last = i + 1 == P.iterations;
+        float *dst = last ? (float *)d_out
+                          : (i == 0 && d_fb_out) ? (float *)d_fb_out : ctx->d_sv_tmp[i & 1u];
+        float *vdst = last && d_var_out ? (float *)d_var_out : ctx->d_sv_var[(i + 1u) & 1u];
+        if (rvcp_launch_svgf_pass(src, ctx->d_sv_var[i & 1u], d_gbuffer, dst, vdst, width, height,
+                                  1u << i, P.normal_power_log2, use_lum ? 1u : 0u, sigma_l2,
+                                  P.epsilon, P.sigma_plane, 0u, s) != 0)
+            return fail(ctx, RVCP_E_HIP, std::string("svgf pass launch failed: ") +
+                                             hipGetErrorString(hipGetLastError()));
+        src = dst;
+    }
+    if (d_fb_out && P.iterations == 1)          // pass 0 is the last pass
+        HIP_TRY(ctx, hipMemcpyAsync(d_fb_out, d_out, npx * 12, hipMemcpyDeviceToDevice, s));
+    if (d_rgba8_out &&
+        rvcp_launch_tonemap((const float *)d_out, (uint32_t)npx, ctx->d_gamma,
+                            (uint32_t *)d_rgba8_out, s) != 0)
+        return fail(ctx, RVCP_E_HIP, "svgf tone-map launch failed");
+    HIP_TRY(ctx, hipEventRecord(ctx->evsf1, s));
+    ctx->svgf_flt_recorded = true;
+    ctx->svgf_flt_pending = true;
+    return RVCP_OK;
+}
+
+static int impl_svgf_wait(rvcp_ctx_t *ctx, float *accumulate_ms, float *filter_ms)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!ctx->svgf_acc_pending && !ctx->svgf_flt_pending)
+        return fail(ctx, RVCP_E_INVALID, "no svgf step in flight");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (accumulate_ms) *accumulate_ms = 0.0f;
+    if (filter_ms) *filter_ms = 0.0f;
+    if (ctx->svgf_acc_pending) {
+        HIP_TRY(ctx, hipEventSynchronize(ctx->evsa1));
+        if (accumulate_ms) HIP_TRY(ctx, hipEventElapsedTime(accumulate_ms, ctx->evsa0, ctx->evsa1));
+        ctx->svgf_acc_pending = false;
+    }
+    if (ctx->svgf_flt_pending) {
+        HIP_TRY(ctx, hipEventSynchronize(ctx->evsf1));
+        if (filter_ms) HIP_TRY(ctx, hipEventElapsedTime(filter_ms, ctx->evsf0, ctx->evsf1));
+        ctx->svgf_flt_pending = false;
+    }
+    return RVCP_OK;
+}
+
+static int impl_svgf_reset(rvcp_ctx_t *ctx)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    ctx->sv_valid = false;
+    return RVCP_OK;
+}
+
+static void svgf_free_state(rvcp_ctx_t *ctx)
+{
+    for (int i = 0; i < 2; ++i) {
+        (void)hipFree(ctx->d_sv_lin[i]);
+        (void)hipFree(ctx->d_sv_mom[i]);
+        (void)hipFree(ctx->d_sv_len[i]);
+        (void)hipFree(ctx->d_sv_gbuf[i]);
+        ctx->d_sv_lin[i] = ctx->d_sv_mom[i] = nullptr;
+        ctx->d_sv_len[i] = nullptr;
+        ctx->d_sv_gbuf[i] = nullptr;
+    }
+    (void)hipFree(ctx->d_sv_cur);
+    (void)hipFree(ctx->d_sv_show);
+    (void)hipFree(ctx->d_sv_showvar);
+    (void)hipFree(ctx->d_sv_fb);
+    ctx->d_sv_cur = ctx->d_sv_show = ctx->d_sv_showvar = ctx->d_sv_fb = nullptr;
+    ctx->cap_sv = 0;
+}
+
+static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                            uint32_t height, const rvcp_temporal_params_t *tparams,
+                            const rvcp_svgf_params_t *sparams, uint32_t flags, uint8_t *out_rgba8,
+                            float *out_linear_rgb, float *out_variance, uint32_t *out_history_len,
+                            rvcp_stats_t *stats, float *accumulate_ms, float *filter_ms)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!push || !out_rgba8 || width == 0 || height == 0 ||
+        (uint64_t)width * height >= (1ull << 31) || (flags & ~RVCP_SVGF_FEEDBACK))
+        return fail(ctx, RVCP_E_INVALID, "invalid render_svgf arguments");
+    if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
+        return fail(ctx, RVCP_E_UNSUPPORTED, "the G-buffer is implemented for the games101 integrator");
+    if (!ctx->subs.empty())
+        return fail(ctx, RVCP_E_UNSUPPORTED, "render_svgf drives one GPU (n_gpus = 1)");
+    if (ctx->pending)
+        return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    rvcp_temporal_view_t view_now;
+    if (impl_temporal_view_from_push(push, width, height, &view_now) != RVCP_OK)
+        return fail(ctx, RVCP_E_INVALID, "render_svgf: the camera's forward is zero or parallel to up");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool feedback = (flags & RVCP_SVGF_FEEDBACK) != 0;
+    const size_t npx = (size_t)width * height;
+    int rc;
+    if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, npx, 4)) != RVCP_OK) return rc;
+    if (ctx->cap_sv < npx) {            // (a larger frame: the history is dropped with its buffers)
+        ctx->sv_valid = false;
+        svgf_free_state(ctx);
+        for (int i = 0; i < 2; ++i) {
+            HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_lin[i], npx * 12));
+            HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_mom[i], npx * 8));
+            HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_len[i], npx * 4));
+            HIP_TRY(ctx, hipMalloc(&ctx->d_sv_gbuf[i], npx * sizeof(rvcp_gbuffer_texel_t)));
+        }
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_cur, npx * 12));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_show, npx * 12));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_showvar, npx * 4));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_fb, npx * 12));
+        ctx->cap_sv = npx;
+    }
+    const bool have = ctx->sv_valid && ctx->sv_width == width && ctx->sv_height == height;
+    const bool same_camera = have && std::memcmp(&ctx->sv_camera, &push->camera, sizeof(rvcp_camera_t)) == 0;
+    const uint32_t prev = ctx->sv_slot, cur = prev ^ 1u;
+    ctx->sv_valid = false;              // until this frame is complete
+    // render (raw linear frame), G-buffer, accumulation, filter, in this order on the context's
+    // stream; the filter's RGBA8 store overwrites the render's
+    if ((rc = rvcp_render_async(ctx, push, width, height, ctx->d_rgba, ctx->d_sv_cur, ctx->stream)) != RVCP_OK)
+        return rc;
+    bool enqueued = false;
+    rc = impl_render_gbuffer_async(ctx, push, width, height, ctx->d_sv_gbuf[cur], ctx->stream);
+    if (rc == RVCP_OK) {
+        rc = impl_svgf_accumulate_async(
+            ctx, same_camera ? nullptr : &ctx->sv_view, ctx->d_sv_cur, ctx->d_sv_gbuf[cur],
+            have ? ctx->d_sv_lin[prev] : nullptr, have ? ctx->d_sv_gbuf[prev] : nullptr,
+            have ? ctx->d_sv_len[prev] : nullptr, have ? ctx->d_sv_mom[prev] : nullptr, width,
+            height, tparams, sparams, ctx->d_sv_lin[cur], ctx->d_sv_len[cur], ctx->d_sv_mom[cur],
+            nullptr, ctx->stream);
+        enqueued = enqueued || rc == RVCP_OK;
+    }
+    if (rc == RVCP_OK) {
+        rc = impl_svgf_filter_async(ctx, ctx->d_sv_lin[cur], ctx->d_sv_mom[cur], ctx->d_sv_len[cur],
+                                    ctx->d_sv_gbuf[cur], width, height, sparams, ctx->d_sv_show,
+                                    ctx->d_sv_showvar, feedback ? ctx->d_sv_fb : nullptr,
+                                    ctx->d_rgba, ctx->stream);
+    }
+    if (rc != RVCP_OK) {
+        const std::string why = ctx->err;
+        (void)rvcp_wait(ctx, nullptr);          // the render is enqueued: leave nothing pending
+        if (enqueued) (void)impl_svgf_wait(ctx, nullptr, nullptr);
+        ctx->err = why;
+        return rc;
+    }
+    if ((rc = rvcp_wait(ctx, stats)) != RVCP_OK) return rc;
+    if ((rc = impl_svgf_wait(ctx, accumulate_ms, filter_ms)) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, npx * 4, hipMemcpyDeviceToHost));
+    if (out_linear_rgb)
+        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, ctx->d_sv_show, npx * 12, hipMemcpyDeviceToHost));
+    if (out_variance)
+        HIP_TRY(ctx, hipMemcpy(out_variance, ctx->d_sv_showvar, npx * 4, hipMemcpyDeviceToHost));
+    if (out_history_len)
+        HIP_TRY(ctx, hipMemcpy(out_history_len, ctx->d_sv_len[cur], npx * 4, hipMemcpyDeviceToHost));
+    // feedback: the next frame's colour history is pass 0's output (moments and lengths stay)
+    if (feedback) std::swap(ctx->d_sv_lin[cur], ctx->d_sv_fb);
+    ctx->sv_slot = cur;
+    ctx->sv_width = width;
+    ctx->sv_height = height;
+    ctx->sv_camera = push->camera;
+    ctx->sv_view = view_now;
+    ctx->sv_valid = true;
+    return RVCP_OK;
+}
+
 static int impl_assemble_frame_async(rvcp_ctx_t *ctx, const void *d_gathered, uint32_t slot_rows,
                               uint32_t width, uint32_t height, uint32_t shard_count,
                               void *d_frame, void *stream)
@@ -2415,6 +2799,65 @@ int rvcp_gather_frame_async(rvcp_ctx_t *ctx, const void *d_shard_rgba8, uint32_t
 int rvcp_gather_wait(rvcp_ctx_t *ctx, float *gather_ms, float *frame_ms)
 {
     return barrier(ctx, [&] { return impl_gather_wait(ctx, gather_ms, frame_ms); });
+}
+
+int rvcp_svgf_params_default(rvcp_svgf_params_t *params)
+{
+    return barrier(nullptr, [&] { return impl_svgf_params_default(params); });
+}
+
+int rvcp_svgf_accumulate_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *view,
+                               const void *d_cur_linear, const void *d_cur_gbuffer,
+                               const void *d_prev_linear, const void *d_prev_gbuffer,
+                               const void *d_prev_len, const void *d_prev_moments,
+                               uint32_t width, uint32_t height,
+                               const rvcp_temporal_params_t *tparams,
+                               const rvcp_svgf_params_t *sparams, void *d_out_linear,
+                               void *d_out_len, void *d_out_moments, void *d_rgba8_out,
+                               void *stream)
+{
+    return barrier(ctx, [&] {
+        return impl_svgf_accumulate_async(ctx, view, d_cur_linear, d_cur_gbuffer, d_prev_linear,
+                                          d_prev_gbuffer, d_prev_len, d_prev_moments, width, height,
+                                          tparams, sparams, d_out_linear, d_out_len, d_out_moments,
+                                          d_rgba8_out, stream);
+    });
+}
+
+int rvcp_svgf_filter_async(rvcp_ctx_t *ctx, const void *d_linear, const void *d_moments,
+                           const void *d_len, const void *d_gbuffer, uint32_t width,
+                           uint32_t height, const rvcp_svgf_params_t *params,
+                           void *d_linear_out, void *d_variance_out, void *d_feedback_out,
+                           void *d_rgba8_out, void *stream)
+{
+    return barrier(ctx, [&] {
+        return impl_svgf_filter_async(ctx, d_linear, d_moments, d_len, d_gbuffer, width, height,
+                                      params, d_linear_out, d_variance_out, d_feedback_out,
+                                      d_rgba8_out, stream);
+    });
+}
+
+int rvcp_svgf_wait(rvcp_ctx_t *ctx, float *accumulate_ms, float *filter_ms)
+{
+    return barrier(ctx, [&] { return impl_svgf_wait(ctx, accumulate_ms, filter_ms); });
+}
+
+int rvcp_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                     uint32_t height, const rvcp_temporal_params_t *tparams,
+                     const rvcp_svgf_params_t *sparams, uint32_t flags, uint8_t *out_rgba8,
+                     float *out_linear_rgb, float *out_variance, uint32_t *out_history_len,
+                     rvcp_stats_t *stats, float *accumulate_ms, float *filter_ms)
+{
+    return barrier(ctx, [&] {
+        return impl_render_svgf(ctx, push, width, height, tparams, sparams, flags, out_rgba8,
+                                out_linear_rgb, out_variance, out_history_len, stats,
+                                accumulate_ms, filter_ms);
+    });
+}
+
+int rvcp_svgf_reset(rvcp_ctx_t *ctx)
+{
+    return barrier(ctx, [&] { return impl_svgf_reset(ctx); });
 }
 
 }  // extern "C"

@@ -343,6 +343,25 @@ int rvcp_launch_temporal(const float *cur_c, const void *cur_g, const float *pre
                          uint32_t *out_len, uint32_t width, uint32_t height, uint32_t mode,
                          const struct rvcp_temporal_view *view,
                          const struct rvcp_temporal_params *params, void *stream);
+// SVGF (rvcp_svgf.hip): the accumulation step with moments (modes as
+// rvcp_launch_temporal), moments -> variance, and one variance-guided a-trous pass (step = 2^i,
+// sigma_l2 = sigma_luminance^2; use_lum = 0: the luminance weight is 1; force_direct: steps 1
+// and 2 through the direct kernel too)
+int rvcp_launch_svgf_temporal(const float *cur_c, const void *cur_g, const float *prev_c,
+                              const void *prev_g, const uint32_t *prev_len, const float *prev_m,
+                              float *out_c, uint32_t *out_len, float *out_m, uint32_t width,
+                              uint32_t height, uint32_t mode,
+                              const struct rvcp_temporal_view *view,
+                              const struct rvcp_temporal_params *params, float alpha_moments_min,
+                              void *stream);
+int rvcp_launch_svgf_variance(const float *moments, const uint32_t *len, const void *gbuffer,
+                              float *out_v, uint32_t width, uint32_t height,
+                              uint32_t spatial_below, uint32_t normal_power_log2,
+                              float sigma_plane, void *stream);
+int rvcp_launch_svgf_pass(const float *in_c, const float *in_v, const void *gbuffer, float *out_c,
+                          float *out_v, uint32_t width, uint32_t height, uint32_t step,
+                          uint32_t normal_power_log2, uint32_t use_lum, float sigma_l2,
+                          float epsilon, float sigma_plane, uint32_t force_direct, void *stream);
 int rvcp_launch_assemble(const uint32_t *gathered, uint32_t slot_rows, uint32_t width,
                          uint32_t height, uint32_t shard_count, uint32_t *frame, void *stream);
 int rvcp_launch_fill(uint32_t *out_rgba, float *out_lin, uint32_t n_pixels, uint32_t rgba,

@@ -157,7 +157,7 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
                  time_seed: Optional[Callable[[int], float]] = None,
                  dump_dir: Optional[str] = None, dump_format: str = "ppm",
                  on_fps: Optional[Callable[[int], None]] = None, denoise=None,
-                 temporal=None) -> dict:
+                 temporal=None, svgf=None) -> dict:
     """``main_loop`` (ray_tracer.rs:22-100) without a window.
 
     Per frame: apply this frame's scripted events, count FPS (printed once a second as
@@ -169,6 +169,10 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
     ``temporal``: an ``abi.make_temporal_params(...)`` record to accumulate the frames across the
     loop (``tracer.render_temporal``, reprojected when the camera moves), with ``denoise``
     selecting the spatial pass on top of the accumulated frame; None (default): no accumulation.
+    ``svgf``: an ``abi.make_svgf_params(...)`` record to run every frame through SVGF
+    (``tracer.render_svgf``: accumulation with moments, variance, variance-guided filter); it takes
+    precedence over ``temporal`` (whose record, when given, supplies the accumulation's parameters)
+    and ``denoise`` (ignored); None (default): unchanged behaviour.
     Returns per-frame render times and the final camera."""
     info = RuntimeInfo(window_size=(width, height))
     by_frame: Dict[int, List[Event]] = {}
@@ -201,7 +205,9 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
         moved.append(update_camera_state(info, cam, dt))
         t = time_seed(i) if time_seed else float(f32(_time.time() % 1000.0))
         t0 = _time.perf_counter()
-        if temporal is not None:
+        if svgf is not None:
+            rgba = tracer.render_svgf(width, height, t, temporal, svgf)
+        elif temporal is not None:
             rgba = tracer.render_temporal(width, height, t, temporal, denoise)
         else:
             rgba = (tracer.render(width, height, t) if denoise is None

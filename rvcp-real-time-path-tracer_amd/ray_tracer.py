@@ -38,6 +38,8 @@ class RayTracer:
         self.last_stats = None
         self.last_temporal_ms = None
         self.last_denoise_ms = None
+        self.last_svgf_accumulate_ms = None
+        self.last_svgf_filter_ms = None
         # FPS counter (src/ray_tracer/ray_tracer.rs:80-86)
         self.fps_frame_count = 0
         self.fps_last_time = _time.perf_counter()
@@ -198,6 +200,53 @@ class RayTracer:
         """rvcp_temporal_reset: drop the history render_temporal keeps."""
         self._check(self._lib.rvcp_temporal_reset(self._ctx))
 
+    def render_svgf_push(self, push: np.ndarray, width: int, height: int, params=None, svgf=None,
+                         feedback: bool = False, want_linear: bool = False,
+                         want_variance: bool = False, want_history: bool = False):
+        """rvcp_render_svgf for an explicit push constant (see render_svgf)."""
+        push = np.ascontiguousarray(push, dtype=PUSH_DTYPE)
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=abi.TEMPORAL_PARAMS_DTYPE)
+        if svgf is not None:
+            svgf = np.ascontiguousarray(svgf, dtype=abi.SVGF_PARAMS_DTYPE)
+        rgba = np.empty((height, width, 4), dtype=np.uint8)
+        lin = np.empty((height, width, 3), dtype=np.float32) if want_linear else None
+        var = np.empty((height, width), dtype=np.float32) if want_variance else None
+        hist = np.empty((height, width), dtype=np.uint32) if want_history else None
+        stats = np.zeros((), dtype=abi.STATS_DTYPE)
+        a_ms, f_ms = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        self._check(self._lib.rvcp_render_svgf(
+            self._ctx, abi.ptr(push), width, height, abi.ptr(params), abi.ptr(svgf),
+            abi.SVGF_FEEDBACK if feedback else 0, abi.ptr(rgba), abi.ptr(lin), abi.ptr(var),
+            abi.ptr(hist), abi.ptr(stats), ctypes.cast(ctypes.byref(a_ms), ctypes.c_void_p),
+            ctypes.cast(ctypes.byref(f_ms), ctypes.c_void_p)))
+        self.last_stats = stats
+        self.last_svgf_accumulate_ms = float(a_ms.value)
+        self.last_svgf_filter_ms = float(f_ms.value)
+        out = (rgba,) + ((lin,) if want_linear else ()) + ((var,) if want_variance else ()) + \
+            ((hist,) if want_history else ())
+        return out if len(out) > 1 else rgba
+
+    def render_svgf(self, width: int, height: int, time: float, params=None, svgf=None,
+                    feedback: bool = False, want_linear: bool = False,
+                    want_variance: bool = False, want_history: bool = False):
+        """rvcp_render_svgf: one frame rendered, blended with its luminance moments into the SVGF
+        history the context keeps (apart from render_temporal's), turned into a per-pixel variance
+        and filtered by the variance-guided a-trous passes (params: abi.make_temporal_params(...),
+        svgf: abi.make_svgf_params(...); None = the defaults).  feedback: the next frame's colour
+        history is pass 0's output.  Returns the RGBA8 frame [, its linear RGB] [, its variance]
+        [, the history lengths]; last_stats are the render's, last_svgf_accumulate_ms /
+        last_svgf_filter_ms the device times of the two steps.  The history restarts on a size
+        change, upload_scene and svgf_reset()."""
+        if self.scene is None:
+            raise RuntimeError("upload_scene first")
+        return self.render_svgf_push(push_constant(self.scene.camera, time), width, height, params,
+                                     svgf, feedback, want_linear, want_variance, want_history)
+
+    def svgf_reset(self):
+        """rvcp_svgf_reset: drop the history render_svgf keeps."""
+        self._check(self._lib.rvcp_svgf_reset(self._ctx))
+
     def mandelbrot(self, push: np.ndarray, width: int, height: int, want_value: bool = False):
         """The Mandelbrot operator (rvcp_mandelbrot): grey RGBA8 frame [, escape values]."""
         from .mandelbrot import MANDELBROT_PUSH_DTYPE
@@ -293,6 +342,47 @@ class RayTracer:
         self._check(self._lib.rvcp_temporal_wait(self._ctx, ctypes.cast(ctypes.byref(ms),
                                                                         ctypes.c_void_p)))
         return float(ms.value)
+
+    def svgf_accumulate_async(self, view, d_cur_linear: int, d_cur_gbuffer: int,
+                              d_prev_linear: int, d_prev_gbuffer: int, d_prev_len: int,
+                              d_prev_moments: int, width, height, d_out_linear: int,
+                              d_out_len: int, d_out_moments: int, d_rgba: int = 0, params=None,
+                              svgf=None, stream: int = 0):
+        """rvcp_svgf_accumulate_async: temporal_accumulate_async that also carries the luminance
+        moments (width * height float pairs); d_prev_* all 0: no history.  Wait with
+        svgf_wait()."""
+        if view is not None:
+            view = np.ascontiguousarray(view, dtype=abi.TEMPORAL_VIEW_DTYPE)
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=abi.TEMPORAL_PARAMS_DTYPE)
+        if svgf is not None:
+            svgf = np.ascontiguousarray(svgf, dtype=abi.SVGF_PARAMS_DTYPE)
+        P = lambda a: ctypes.c_void_p(a) if a else None   # noqa: E731
+        self._check(self._lib.rvcp_svgf_accumulate_async(
+            self._ctx, abi.ptr(view), P(d_cur_linear), P(d_cur_gbuffer), P(d_prev_linear),
+            P(d_prev_gbuffer), P(d_prev_len), P(d_prev_moments), width, height, abi.ptr(params),
+            abi.ptr(svgf), P(d_out_linear), P(d_out_len), P(d_out_moments), P(d_rgba), P(stream)))
+
+    def svgf_filter_async(self, d_linear: int, d_moments: int, d_len: int, d_gbuffer: int, width,
+                          height, d_linear_out: int, d_variance_out: int = 0,
+                          d_feedback_out: int = 0, d_rgba: int = 0, svgf=None, stream: int = 0):
+        """rvcp_svgf_filter_async: variance estimate, guided a-trous passes and tone map of an
+        accumulated frame in device memory; optional outputs are 0.  Wait with svgf_wait()."""
+        if svgf is not None:
+            svgf = np.ascontiguousarray(svgf, dtype=abi.SVGF_PARAMS_DTYPE)
+        P = lambda a: ctypes.c_void_p(a) if a else None   # noqa: E731
+        self._check(self._lib.rvcp_svgf_filter_async(
+            self._ctx, P(d_linear), P(d_moments), P(d_len), P(d_gbuffer), width, height,
+            abi.ptr(svgf), P(d_linear_out), P(d_variance_out), P(d_feedback_out), P(d_rgba),
+            P(stream)))
+
+    def svgf_wait(self):
+        """rvcp_svgf_wait: block until the last svgf_accumulate_async / svgf_filter_async are done;
+        their device times (accumulate_ms, filter_ms), 0 for a step that was not enqueued."""
+        a, f = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        self._check(self._lib.rvcp_svgf_wait(self._ctx, ctypes.cast(ctypes.byref(a), ctypes.c_void_p),
+                                             ctypes.cast(ctypes.byref(f), ctypes.c_void_p)))
+        return float(a.value), float(f.value)
 
     def wait(self):
         """rvcp_wait: block until the last async render is done; returns its stats."""

@@ -1,0 +1,541 @@
+"""SVGF on the GPU: the accumulation with moments, the variance estimate and the
+variance-guided a-trous passes bit-identical to the numpy restatement (tests/svgf_ref.py) for
+colour, moments, variance and length with no pixel excluded, the RGBA8 store equal to
+oracle.gamma_u8 of those floats, the optional outputs, the stateful chain of rvcp_render_svgf with
+and without feedback against the restatement fed the same context's own frames and texels, the
+restarts, the quality gate, the argument checks (every rejected call is rejected on the host
+before any launch) and the interactive loop."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import denoise_ref as R
+import svgf_ref as S
+import temporal_ref as T
+import rvcp_amd
+from rvcp_amd import abi
+from rvcp_amd import interactive as I
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+f32 = np.float32
+TILE_W, TILE_H = 32, 8          # the workgroup tile of the variance and the LDS a-trous kernels
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def dev(a):
+    """A numpy array's bytes in a torch device tensor."""
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+
+
+def blank(nbytes, fill=0xA5):
+    """An output buffer that starts from a pattern no result has."""
+    return torch.full((nbytes,), fill, dtype=torch.uint8, device="cuda")
+
+
+@pytest.fixture(scope="module")
+def tracers():
+    """One scene-less context per unorm_rule: the stateless steps need no scene."""
+    rts = [rvcp_amd.RayTracer(unorm_rule=rule) for rule in (abi.UNORM_DRIVER, abi.UNORM_NEAREST)]
+    yield rts
+    for rt in rts:
+        rt.close()
+
+
+def gpu_accumulate(rt, c, g, pc, pg, pl, pm, view, tp, sp, want_rgba=True):
+    """rvcp_svgf_accumulate_async on device tensors; (colour, length, moments, rgba)."""
+    H, W = c.shape[:2]
+    d_c, d_g = dev(c), dev(g)
+    d_prev = [dev(a) for a in (pc, pg, pl, pm)] if pc is not None else None
+    d_out, d_len, d_mom = blank(W * H * 12), blank(W * H * 4), blank(W * H * 8)
+    d_rgba = blank(W * H * 4, 0)
+    torch.cuda.synchronize()
+    pp = [t.data_ptr() for t in d_prev] if d_prev else [0, 0, 0, 0]
+    rt.svgf_accumulate_async(view, d_c.data_ptr(), d_g.data_ptr(), pp[0], pp[1], pp[2], pp[3], W, H,
+                             d_out.data_ptr(), d_len.data_ptr(), d_mom.data_ptr(),
+                             d_rgba.data_ptr() if want_rgba else 0, tp, sp)
+    a_ms, f_ms = rt.svgf_wait()
+    assert a_ms >= 0.0 and f_ms == 0.0
+    return (d_out.cpu().numpy().view(np.float32).reshape(H, W, 3),
+            d_len.cpu().numpy().view(np.uint32).reshape(H, W),
+            d_mom.cpu().numpy().view(np.float32).reshape(H, W, 2),
+            d_rgba.cpu().numpy().reshape(H, W, 4))
+
+
+def gpu_filter(rt, c, m, n, g, sp, want_var=True, want_fb=True, want_rgba=True):
+    """rvcp_svgf_filter_async on device tensors; (colour, variance, pass-0 colour, rgba)."""
+    H, W = n.shape
+    d_c, d_m, d_n, d_g = dev(c), dev(m), dev(n), dev(g)
+    d_out, d_var, d_fb = blank(W * H * 12), blank(W * H * 4), blank(W * H * 12)
+    d_rgba = blank(W * H * 4, 0)
+    torch.cuda.synchronize()
+    rt.svgf_filter_async(d_c.data_ptr(), d_m.data_ptr(), d_n.data_ptr(), d_g.data_ptr(), W, H,
+                         d_out.data_ptr(), d_var.data_ptr() if want_var else 0,
+                         d_fb.data_ptr() if want_fb else 0, d_rgba.data_ptr() if want_rgba else 0, sp)
+    a_ms, f_ms = rt.svgf_wait()
+    assert a_ms == 0.0 and f_ms >= 0.0
+    return (d_out.cpu().numpy().view(np.float32).reshape(H, W, 3),
+            d_var.cpu().numpy().view(np.float32).reshape(H, W),
+            d_fb.cpu().numpy().view(np.float32).reshape(H, W, 3),
+            d_rgba.cpu().numpy().reshape(H, W, 4))
+
+
+def assert_same(got, want, what):
+    diff = bits(got) != bits(want)
+    assert not diff.any(), f"{what}: {int(diff.sum())} of {diff.size} words differ"
+
+
+# ---------------------------------------------------------------------------- 1. kernel parity
+SIZES = [(67, 45), (130, 3), (70, 5), (8, 8), (5, 5), (1, 1)]
+
+
+def one_filterable_pixel(g):
+    g["face"], g["material"] = 7, g["material"] & np.uint32(3)
+
+
+@pytest.mark.parametrize("mode", ["identity", "reprojection", "no_history"])
+@pytest.mark.parametrize("W,H", SIZES)
+def test_accumulate_and_filter_match_numpy_restatement(tracers, W, H, mode):
+    """A on temporal_ref.synthetic_case extended with random history moments, then B and C at
+    three passes on what A left (lengths 1 and up: both branches of B)."""
+    tp = abi.make_temporal_params(alpha_min=0.0, max_history=40, normal_min=0.8, sigma_plane=0.25)
+    sp = abi.make_svgf_params(alpha_moments_min=0.1, sigma_luminance=2.0, sigma_plane=0.25,
+                              normal_power_log2=2)
+    c, g, pc, pg, pl, view = T.synthetic_case(W, H, seed=W * 1000 + H, identity=mode == "identity",
+                                              p=tp)
+    pm = S.synthetic_moments(pc, seed=W + H)
+    if W * H == 1:
+        one_filterable_pixel(g)
+    elif W * H >= T.MIX_MIN_PIXELS:
+        assert R.filterable(g).any() and not R.filterable(g).all()
+    if mode == "no_history":
+        pc = pg = pl = pm = None
+    v = None if mode == "identity" else view
+    want, want_len, want_m = S.accumulate(c, g, pc, pg, pl, pm, v, tp, sp)
+    t_want, t_len = T.accumulate(c, g, pc, pg, pl, v, tp)
+    assert np.array_equal(bits(want), bits(t_want)) and np.array_equal(want_len, t_len)
+    f_want, f_var, f_first, _ = S.filter_frame(want, want_m, want_len, g, sp)
+    for rule, rt in enumerate(tracers):
+        got, got_len, got_m, rgba = gpu_accumulate(rt, c, g, pc, pg, pl, pm, v, tp, sp)
+        assert_same(got, want, f"colour (rule {rule})")
+        assert_same(got_m, want_m, f"moments (rule {rule})")
+        assert np.array_equal(got_len, want_len), rule
+        assert np.array_equal(rgba, R.gamma_rgba(want, rule)), rule
+        out, var, first, rgba = gpu_filter(rt, got, got_m, got_len, g, sp)
+        assert_same(out, f_want, f"filtered colour (rule {rule})")
+        assert_same(var, f_var, f"filtered variance (rule {rule})")
+        assert_same(first, f_first, f"pass-0 colour (rule {rule})")
+        assert np.array_equal(rgba, R.gamma_rgba(f_want, rule)), rule
+
+
+def filter_case(W, H, seed):
+    """denoise_ref.synthetic_case (colours up to 10^4, MISS and EMISSIVE texels) with moments whose
+    variance holds exact zeros and history lengths from 1..6; in a frame wider than one workgroup
+    tile the pixels of the second tile in x all have lengths >= 4."""
+    c, g = R.synthetic_case(W, H, seed)
+    if W * H == 1:
+        one_filterable_pixel(g)
+    m = S.synthetic_moments(c, seed + 1)
+    m[~R.filterable(g)] = 0
+    rng = np.random.default_rng(seed + 2)
+    n = rng.integers(1, 7, (H, W)).astype(np.uint32)
+    tx = 1
+    if W > TILE_W:
+        old = (slice(0, TILE_H), slice(tx * TILE_W, (tx + 1) * TILE_W))
+        n[old] = rng.integers(4, 7, n[old].shape)
+    n[~R.filterable(g)] = 0
+    return c, m, n, g, tx
+
+
+@pytest.mark.parametrize("sigma", [2.0, float("inf")], ids=["sigma2", "sigma_inf"])
+@pytest.mark.parametrize("below", [1, 4])
+@pytest.mark.parametrize("iterations", [1, 3, 5])
+@pytest.mark.parametrize("W,H", SIZES)
+def test_filter_matches_numpy_restatement(tracers, W, H, iterations, below, sigma):
+    c, m, n, g, tx = filter_case(W, H, seed=W * 100 + H)
+    filt = R.filterable(g)
+    sp = abi.make_svgf_params(iterations=iterations, spatial_below=below, sigma_luminance=sigma,
+                              normal_power_log2=3, sigma_plane=20.0)
+    if W > TILE_W and below == 4:
+        # the mix on the input: a workgroup with both branches of B, and one with none young
+        young, old = filt & (n < below), filt & (n >= below)
+        t0 = (slice(0, TILE_H), slice(0, TILE_W))
+        t1 = (slice(0, TILE_H), slice(tx * TILE_W, (tx + 1) * TILE_W))
+        assert young[t0].any() and old[t0].any()
+        assert not young[t1].any() and old[t1].any()
+    assert c.max() > 1.0e3 or W * H < 64
+    want, want_var, want_first, v0 = S.filter_frame(c, m, n, g, sp)
+    if W * H >= 64:
+        assert (v0[filt] == 0).any() and (v0[filt] > 0).any()
+    if np.isinf(sigma):
+        assert_same(want, R.denoise(c, g, iterations, 3, float("inf"), 20.0), "restatement vs §4.9")
+    for rule, rt in enumerate(tracers):
+        out, var, first, rgba = gpu_filter(rt, c, m, n, g, sp)
+        assert_same(out, want, f"colour (rule {rule})")
+        assert_same(var, want_var, f"variance (rule {rule})")
+        assert_same(first, want_first, f"pass-0 colour (rule {rule})")
+        assert np.array_equal(rgba, R.gamma_rgba(want, rule)), rule
+
+
+def test_optional_outputs_and_default_params(tracers):
+    """params = NULL takes rvcp_svgf_params_default; the variance, feedback and RGBA8 outputs are
+    optional, separately and together."""
+    W, H = 45, 19
+    rt = tracers[0]
+    c, m, n, g, _ = filter_case(W, H, seed=77)
+    want, want_var, want_first, _ = S.filter_frame(c, m, n, g, abi.make_svgf_params())
+    for var_, fb_, rgba_ in ((False, False, False), (True, False, False), (False, True, False),
+                             (False, False, True), (True, True, True)):
+        out, var, first, rgba = gpu_filter(rt, c, m, n, g, None, var_, fb_, rgba_)
+        assert_same(out, want, (var_, fb_, rgba_))
+        if var_:
+            assert_same(var, want_var, "variance")
+        else:
+            assert (var.view(np.uint8) == 0xA5).all()
+        if fb_:
+            assert_same(first, want_first, "feedback")
+        else:
+            assert (first.view(np.uint8) == 0xA5).all()
+        assert np.array_equal(rgba, R.gamma_rgba(want)) if rgba_ else not rgba.any()
+    # one pass: pass 0 is the last one, and the feedback buffer gets the output
+    sp = abi.make_svgf_params(iterations=1)
+    want1 = S.filter_frame(c, m, n, g, sp)[0]
+    out, _, first, _ = gpu_filter(rt, c, m, n, g, sp)
+    assert_same(out, want1, "one pass")
+    assert_same(first, want1, "feedback of one pass")
+    # the accumulation with both parameter records NULL and no RGBA8 store
+    tp = abi.make_temporal_params()
+    c2, g2, pc, pg, pl, view = T.synthetic_case(33, 17, seed=11)
+    pm = S.synthetic_moments(pc, seed=12)
+    a, an, am = S.accumulate(c2, g2, pc, pg, pl, pm, view, tp, abi.make_svgf_params())
+    got, got_len, got_m, rgba = gpu_accumulate(rt, c2, g2, pc, pg, pl, pm, view, None, None, False)
+    assert_same(got, a, "colour")
+    assert_same(got_m, am, "moments")
+    assert np.array_equal(got_len, an) and not rgba.any()
+
+
+# ---------------------------------------------------------------------------- 2. stateful chain
+CHAIN_W, CHAIN_H = 37, 23
+MOVES = [(0.0, 0.0, 0.0), (0.0, 0.0, 0.0), (60.0, 20.0, 0.0), (60.0, 20.0, 0.0), (35.0, -15.0, 40.0)]
+
+
+def chain_pushes():
+    """The five frames of test_gpu_temporal.py: two static, a move, a static one, a second move."""
+    out = []
+    for i, d in enumerate(MOVES):
+        sc = rvcp_amd.Scene.default()
+        sc.camera.position = (sc.camera.position + np.asarray(d, dtype=f32)).astype(f32)
+        out.append(sc.push_constant(20.0 + i))
+    return out
+
+
+@pytest.fixture(scope="module")
+def chain(cornell):
+    """One context's own render_push frames and render_gbuffer_async texels for the five pushes."""
+    W, H = CHAIN_W, CHAIN_H
+    pushes = chain_pushes()
+    rt = rvcp_amd.RayTracer(spp=2)
+    rt.upload_scene(cornell)
+    raw, gbuf, views = [], [], []
+    d_g = torch.zeros(W * H * 32, dtype=torch.uint8, device="cuda")
+    for i, push in enumerate(pushes):
+        raw.append(rt.render_push(push, W, H, want_linear=True)[1])
+        torch.cuda.synchronize()
+        rt.render_gbuffer_async(push, W, H, d_g.data_ptr())
+        torch.cuda.synchronize()
+        gbuf.append(d_g.cpu().numpy().view(abi.GBUFFER_DTYPE).reshape(H, W).copy())
+        same = i > 0 and push["camera"].tobytes() == pushes[i - 1]["camera"].tobytes()
+        views.append(None if i == 0 or same else abi.temporal_view(pushes[i - 1], W, H))
+    yield dict(rt=rt, pushes=pushes, raw=raw, gbuf=gbuf, views=views)
+    rt.close()
+
+
+@pytest.mark.parametrize("feedback", [False, True], ids=["plain", "feedback"])
+def test_render_svgf_chain(chain, feedback):
+    rt, W, H = chain["rt"], CHAIN_W, CHAIN_H
+    tp, sp = abi.make_temporal_params(), abi.make_svgf_params()
+    ref = S.Chain(tp, sp, feedback)
+    rt.svgf_reset()
+    lens = []
+    for i, push in enumerate(chain["pushes"]):
+        want, want_var, want_len = ref.frame(chain["raw"][i], chain["gbuf"][i], chain["views"][i])
+        rgba, lin, var, hist = rt.render_svgf_push(push, W, H, tp, sp, feedback, want_linear=True,
+                                                   want_variance=True, want_history=True)
+        assert rt.last_svgf_accumulate_ms > 0.0 and rt.last_svgf_filter_ms > 0.0
+        assert int(rt.last_stats["samples"]) == W * H * 2
+        assert np.array_equal(hist, want_len), i
+        assert_same(lin, want, f"frame {i} colour")
+        assert_same(var, want_var, f"frame {i} variance")
+        assert np.array_equal(rgba, R.gamma_rgba(want)), i
+        lens.append(hist)
+    # the chain exercises what it is meant to: histories that continue, that are reprojected
+    # (with rejected taps) and that restart; young and old histories in the variance estimate
+    filt = [R.filterable(g) for g in chain["gbuf"]]
+    assert np.array_equal(lens[1], 2 * filt[1].astype(np.uint32))
+    assert (lens[2] == 3).any() and (lens[2][filt[2]] == 1).any()
+    assert (lens[4] == 5).any() and (lens[4][filt[4]] == 1).any()
+    # a plain render on the same context is untouched by the history
+    again = rt.render_push(chain["pushes"][0], W, H, want_linear=True)[1]
+    assert_same(again, chain["raw"][0], "plain render")
+
+
+def test_history_restarts_and_is_apart_from_render_temporal(chain, cornell):
+    rt, W, H = chain["rt"], CHAIN_W, CHAIN_H
+    push = chain["pushes"][0]
+    tp, sp = abi.make_temporal_params(), abi.make_svgf_params()
+    fresh = R.filterable(chain["gbuf"][0]).astype(np.uint32)
+    first = S.Chain(tp, sp).frame(chain["raw"][0], chain["gbuf"][0], None)[0]
+
+    def frame(w=W, h=H):
+        _, lin, hist = rt.render_svgf_push(push, w, h, tp, sp, want_linear=True, want_history=True)
+        return lin, hist
+
+    def temporal():
+        return rt.render_temporal_push(push, W, H, tp, want_history=True)[1]
+
+    def restarted():
+        lin, hist = frame()
+        assert np.array_equal(hist, fresh)
+        assert_same(lin, first, "first frame of a history")
+
+    rt.svgf_reset()
+    rt.temporal_reset()
+    restarted()
+    assert np.array_equal(frame()[1], 2 * fresh)
+    rt.svgf_reset()                                       # 1. rvcp_svgf_reset
+    restarted()
+    assert np.array_equal(frame()[1], 2 * fresh)
+    assert frame(W - 5, H)[1].max() == 1                  # 2. a size change, there ...
+    assert frame(W - 5, H)[1].max() == 2
+    restarted()                                           # ... and back
+    assert np.array_equal(frame()[1], 2 * fresh)
+    # 3. the two histories are apart: neither call touches the other's, nor does the other's reset
+    assert np.array_equal(temporal(), fresh)
+    assert np.array_equal(frame()[1], 3 * fresh)
+    assert np.array_equal(temporal(), 2 * fresh)
+    rt.temporal_reset()
+    assert np.array_equal(frame()[1], 4 * fresh)
+    assert np.array_equal(temporal(), fresh)
+    rt.svgf_reset()
+    assert np.array_equal(temporal(), 2 * fresh)
+    restarted()
+    rt.upload_scene(cornell)                              # 4. a scene upload
+    restarted()
+
+
+# ---------------------------------------------------------------------------- 3. quality
+def test_quality_gate_through_render_svgf(cornell):
+    """The CPU gate (test_svgf_cpu) on the GPU's own frames: static camera, Cornell 64^2, SPP = 4,
+    8 frames at the defaults against the first raw frame."""
+    W = H = 64
+    mask, ref = R.filterable(R.cornell_gbuffer(W, H)), R.cornell_reference(W, H)
+    with rvcp_amd.RayTracer(spp=4) as rt:
+        rt.upload_scene(cornell)
+        first = rt.render(W, H, S.QUALITY_SEEDS[0], want_linear=True)[1]
+        for t in S.QUALITY_SEEDS:
+            _, lin, var, hist = rt.render_svgf(W, H, t, want_linear=True, want_variance=True,
+                                               want_history=True)
+    assert np.array_equal(hist, 8 * mask.astype(np.uint32))
+    assert np.isfinite(var).all() and (var >= 0).all() and not var[~mask].any()
+    before, after = R.rmse(first, ref, mask), R.rmse(lin, ref, mask)
+    print(f"rmse first raw {before:.4f} svgf {after:.4f} ratio {after / before:.4f} "
+          f"gate {S.QUALITY_GATE:.4f}")
+    assert after <= S.QUALITY_GATE * before
+
+
+# ---------------------------------------------------------------------------- 4. API
+P = lambda a: ctypes.c_void_p(a) if a else None           # noqa: E731
+BAD_SVGF_PARAMS = (dict(iterations=0), dict(iterations=9), dict(normal_power_log2=9),
+                   dict(sigma_luminance=0.0), dict(sigma_luminance=-1.0),
+                   dict(sigma_luminance=float("nan")), dict(sigma_plane=0.0),
+                   dict(sigma_plane=float("nan")), dict(epsilon=0.0), dict(epsilon=float("nan")),
+                   dict(alpha_moments_min=-0.1), dict(alpha_moments_min=1.5),
+                   dict(alpha_moments_min=float("nan")), dict(spatial_below=0),
+                   dict(spatial_below=17))
+
+
+@pytest.fixture(scope="module")
+def api():
+    """Device buffers of a 16 x 16 case and the two entry points as keyword calls on a scene-less
+    context; every output starts zeroed, and stays so through every rejected call."""
+    L = abi.load()
+    W = H = 16
+    npx = W * H
+    c, g, pc, pg, pl, view = T.synthetic_case(W, H, seed=5)
+    pm = S.synthetic_moments(pc, seed=6)
+    tens = dict(cur=dev(c), cur_g=dev(g), prev=dev(pc), prev_g=dev(pg), prev_len=dev(pl),
+                prev_m=dev(pm))
+    outs = dict(out=torch.zeros(npx * 12 + 64, dtype=torch.uint8, device="cuda"),
+                out_len=torch.zeros(npx * 4 + 64, dtype=torch.uint8, device="cuda"),
+                out_m=torch.zeros(npx * 8 + 64, dtype=torch.uint8, device="cuda"),
+                rgba=torch.zeros(npx * 4, dtype=torch.uint8, device="cuda"),
+                var=torch.zeros(npx * 4, dtype=torch.uint8, device="cuda"),
+                fb=torch.zeros(npx * 12, dtype=torch.uint8, device="cuda"))
+    torch.cuda.synchronize()
+    rt = rvcp_amd.RayTracer(spp=2)
+    h = rt.handle
+    base = dict({k: t.data_ptr() for k, t in {**tens, **outs}.items()}, view=view, w=W, h=H,
+                tp=abi.make_temporal_params(), sp=abi.make_svgf_params())
+
+    def accumulate(**kw):
+        a = dict(base, **kw)
+        return L.rvcp_svgf_accumulate_async(
+            h, abi.ptr(a["view"]), P(a["cur"]), P(a["cur_g"]), P(a["prev"]), P(a["prev_g"]),
+            P(a["prev_len"]), P(a["prev_m"]), a["w"], a["h"], abi.ptr(a["tp"]), abi.ptr(a["sp"]),
+            P(a["out"]), P(a["out_len"]), P(a["out_m"]), P(a["rgba"]), None)
+
+    def filt(**kw):
+        # the filter's inputs: colour `cur`, moments `prev_m`, lengths `prev_len`, texels `cur_g`
+        a = dict(base, **kw)
+        return L.rvcp_svgf_filter_async(
+            h, P(a["cur"]), P(a["prev_m"]), P(a["prev_len"]), P(a["cur_g"]), a["w"], a["h"],
+            abi.ptr(a["sp"]), P(a["out"]), P(a["var"]), P(a["fb"]), P(a["rgba"]), None)
+
+    yield dict(L=L, rt=rt, h=h, base=base, npx=npx, accumulate=accumulate, filter=filt,
+               case=(c, g, pc, pg, pl, pm, view))
+    # nothing was launched by a rejected call: every output is still zero
+    torch.cuda.synchronize()
+    clean = all(not t.cpu().numpy().any() for t in outs.values())
+    rt.close()
+    assert clean
+
+
+def test_api_rejects_null_and_zero_arguments(api):
+    E = abi.RVCP_E_INVALID
+    for name in ("cur", "cur_g", "out", "out_len", "out_m", "w", "h"):
+        assert api["accumulate"](**{name: 0}) == E, name
+    for name in ("cur", "prev_m", "prev_len", "cur_g", "out", "w", "h"):
+        assert api["filter"](**{name: 0}) == E, name
+    assert api["L"].rvcp_svgf_wait(api["h"], None, None) == E          # nothing was enqueued
+    assert b"in flight" in api["L"].rvcp_last_error(api["h"])
+
+
+def test_api_rejects_a_partial_history(api):
+    E = abi.RVCP_E_INVALID
+    names = ("prev", "prev_g", "prev_len", "prev_m")
+    for name in names:
+        assert api["accumulate"](**{name: 0}) == E, name
+        assert api["accumulate"](**{k: 0 for k in names if k != name}) == E, name
+    assert b"together" in api["L"].rvcp_last_error(api["h"])
+
+
+def test_api_rejects_overlapping_buffers(api):
+    E, b, npx = abi.RVCP_E_INVALID, api["base"], api["npx"]
+    for kw in (dict(out=b["cur"]), dict(out=b["prev"] + 12), dict(out=b["cur_g"]),
+               dict(out=b["prev_m"]), dict(out_m=b["prev_m"]), dict(out_m=b["prev_m"] + 8 * npx - 4),
+               dict(out_m=b["cur"]), dict(out_len=b["prev_len"]), dict(out_len=b["prev_m"]),
+               dict(rgba=b["prev_m"]), dict(rgba=b["out_m"]), dict(out_m=b["out"] + 12 * npx - 4),
+               dict(out_len=b["out_m"] + 8 * npx - 4)):
+        assert api["accumulate"](**kw) == E, kw
+        assert b"overlap" in api["L"].rvcp_last_error(api["h"])
+    for kw in (dict(out=b["cur"]), dict(out=b["prev_m"]), dict(out=b["prev_len"]),
+               dict(out=b["cur_g"] + 32 * npx - 4), dict(var=b["cur"]), dict(var=b["prev_m"]),
+               dict(fb=b["cur"]), dict(fb=b["cur_g"]), dict(rgba=b["prev_len"]),
+               dict(var=b["out"]), dict(fb=b["out"] + 12), dict(rgba=b["fb"]), dict(fb=b["var"])):
+        assert api["filter"](**kw) == E, kw
+        assert b"overlap" in api["L"].rvcp_last_error(api["h"])
+
+
+def test_api_rejects_parameters_outside_their_ranges(api):
+    E = abi.RVCP_E_INVALID
+    for kw in BAD_SVGF_PARAMS:
+        sp = abi.make_svgf_params(**kw)
+        assert api["accumulate"](sp=sp) == E, kw
+        assert api["filter"](sp=sp) == E, kw
+    for kw in (dict(alpha_min=-0.1), dict(alpha_min=float("nan")), dict(max_history=0),
+               dict(max_history=65536), dict(sigma_plane=0.0), dict(normal_min=1.5),
+               dict(normal_min=float("nan"))):
+        assert api["accumulate"](tp=abi.make_temporal_params(**kw)) == E, kw
+
+
+def test_api_rejects_a_nonzero_pad(api):
+    sp = abi.make_svgf_params(_pad=1)
+    assert api["accumulate"](sp=sp) == abi.RVCP_E_INVALID
+    assert api["filter"](sp=sp) == abi.RVCP_E_INVALID
+    assert b"_pad" in api["L"].rvcp_last_error(api["h"])
+
+
+def test_api_render_svgf_arguments(api, cornell):
+    L, h, E = api["L"], api["h"], abi.RVCP_E_INVALID
+    W = H = 16
+    push = np.ascontiguousarray(cornell.push_constant(1.0))
+    out = np.zeros((H, W, 4), np.uint8)
+
+    def render(push_=push, w=W, hh=H, flags=0, rgba=out, sp=None):
+        return L.rvcp_render_svgf(h, abi.ptr(push_), w, hh, None, abi.ptr(sp), flags, abi.ptr(rgba),
+                                  None, None, None, None, None, None)
+    assert render(push_=None) == E and render(w=0) == E and render(hh=0) == E
+    assert render(rgba=None) == E and render(flags=2) == E
+    assert render() == abi.RVCP_E_NO_SCENE                 # the context has no scene
+    assert L.rvcp_svgf_reset(h) == abi.RVCP_OK
+    assert not out.any()
+
+
+@pytest.mark.parametrize("kw", [dict(integrator=abi.INTEGRATOR_LEGACY), dict(n_gpus=2)])
+def test_render_svgf_unsupported_contexts(cornell, kw):
+    with rvcp_amd.RayTracer(**kw) as rt:
+        rt.upload_scene(cornell)
+        with pytest.raises(abi.RvcpError) as e:
+            rt.render_svgf(16, 16, 1.0)
+        assert e.value.code == abi.RVCP_E_UNSUPPORTED
+
+
+def test_bad_parameters_midway_drop_the_history(cornell):
+    """A call that fails after the render was enqueued leaves nothing pending and no history."""
+    W = H = 16
+    with rvcp_amd.RayTracer(spp=2) as rt:
+        rt.upload_scene(cornell)
+        assert rt.render_svgf(W, H, 1.0, want_history=True)[1].max() == 1
+        assert rt.render_svgf(W, H, 2.0, want_history=True)[1].max() == 2
+        with pytest.raises(abi.RvcpError) as e:
+            rt.render_svgf(W, H, 3.0, svgf=abi.make_svgf_params(iterations=9))
+        assert e.value.code == abi.RVCP_E_INVALID
+        assert rt.render_svgf(W, H, 4.0, want_history=True)[1].max() == 1
+        rt.render(W, H, 5.0)                               # nothing is left pending
+
+
+def test_the_limits_of_the_ranges_are_inside_them(tracers):
+    W, H = 33, 9
+    c, m, n, g, _ = filter_case(W, H, seed=3)
+    sp = abi.make_svgf_params(iterations=8, normal_power_log2=8, spatial_below=16,
+                              alpha_moments_min=1.0, epsilon=1.0e-30, sigma_luminance=1.0e-3)
+    want, want_var, _, _ = S.filter_frame(c, m, n, g, sp)
+    out, var, _, _ = gpu_filter(tracers[0], c, m, n, g, sp)
+    assert_same(out, want, "colour")
+    assert_same(var, want_var, "variance")
+
+
+# ---------------------------------------------------------------------------- 5. interactive
+def test_run_headless_svgf(tmp_path, cornell):
+    """run_headless(svgf=...) over 4 frames of 32 x 32 with a scripted key event writes its frames:
+    the first is render_svgf of its seed on a fresh history, the later ones continue it."""
+    W = H = 32
+    sc = rvcp_amd.Scene.default()
+    cfg = abi.make_config(spp=2)
+    events = [(2, "key", ("W", True))]
+    seed = lambda i: 10.0 + i                              # noqa: E731
+    sp = abi.make_svgf_params()
+    with rvcp_amd.RayTracer(cfg) as rt:
+        rt.upload_scene(sc)
+        out = I.run_headless(rt, sc, 4, W, H, events=events, fixed_dt=0.05, time_seed=seed,
+                             dump_dir=str(tmp_path), on_fps=lambda n: None, svgf=sp,
+                             denoise=abi.make_denoise_params())
+        assert out["camera_moved"] == [False, False, True, True] and len(out["frame_ms"]) == 4
+        assert rt.last_svgf_accumulate_ms > 0.0 and rt.last_svgf_filter_ms > 0.0
+        frames = [I.read_ppm(str(tmp_path / f"frame_{i:05d}.ppm")) for i in range(4)]
+        # the loop's last frame continued a history: a fresh one at the same camera differs
+        rt.svgf_reset()
+        fresh3 = rt.render_svgf(W, H, seed(3))
+    with rvcp_amd.RayTracer(cfg) as rt:
+        rt.upload_scene(cornell)
+        first, hist = rt.render_svgf(W, H, seed(0), svgf=sp, want_history=True)
+        plain = rt.render(W, H, seed(0))
+    assert all(f.shape == (H, W, 3) for f in frames)
+    assert np.array_equal(frames[0], first[..., :3]) and hist.max() == 1
+    assert not np.array_equal(frames[0], plain[..., :3])   # filtered, not the raw frame
+    assert not np.array_equal(frames[3], fresh3[..., :3])
