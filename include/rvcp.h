@@ -800,6 +800,58 @@ int rvcp_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t
 /* Drop the history rvcp_render_svgf keeps on the context.  No counterpart in the reference. */
 int rvcp_svgf_reset(rvcp_ctx_t *ctx);
 
+/* ---------------------------------------------------------------------------------------
+ * Albedo demodulation: the filters above average irradiance = colour / albedo of the primary
+ * hit instead of colour, and the albedo is multiplied back inside the tone-map store (opt-in;
+ * no other entry point changes).  With the G-buffer texel's
+ *   m  = material & ~RVCP_GBUFFER_EMISSIVE
+ *   on = face != RVCP_GBUFFER_MISS and not (material & RVCP_GBUFFER_EMISSIVE) and
+ *        m < the uploaded materials' count
+ *   a  = materials[m].albedo (as uploaded), usable(a_k) = a_k > 0 and a_k < +inf
+ * a pixel that is `on` gets e_k = usable(a_k) ? c_k / a_k : 0 resp. o_k = usable(a_k) ?
+ * e_k * a_k : 0 per channel; every other pixel passes through.  float32, IEEE division.
+ * No counterpart in the reference.
+ * ------------------------------------------------------------------------------------- */
+
+/* Enqueue the demodulation of d_linear (W*H*3 floats) under d_gbuffer (W*H texels) on
+ * `stream` (NULL: the context's) into d_irradiance_out (W*H*3 floats), which may be d_linear
+ * itself.  A material id outside the uploaded table is not an error: the pixel passes
+ * through.  Ordered behind a render pending on the context and behind the context's previous
+ * SVGF accumulation and filter.  RVCP_E_INVALID: NULL / zero arguments, W*H >= 2^31, an
+ * output that overlaps an input other than d_irradiance_out == d_linear exactly;
+ * RVCP_E_NO_SCENE before an upload.  Restrictions of rvcp_render_gbuffer_async.
+ * No counterpart in the reference. */
+int rvcp_demodulate_async(rvcp_ctx_t *ctx, const void *d_linear, const void *d_gbuffer,
+                          uint32_t width, uint32_t height, void *d_irradiance_out, void *stream);
+
+/* Enqueue the remodulation of d_irradiance (W*H*3 floats) under the same d_gbuffer, fused
+ * with the store: d_linear_out (W*H*3 floats: the colour) and / or d_rgba8_out (W*H*4 bytes:
+ * pow(clamp(c), 0.6) as RGBA8 under the context's unorm_rule, exactly the render's store).
+ * Either output may be NULL, not both; neither may overlap an input or the other.  Ordering,
+ * codes and restrictions as rvcp_demodulate_async.  No counterpart in the reference. */
+int rvcp_remodulate_async(rvcp_ctx_t *ctx, const void *d_irradiance, const void *d_gbuffer,
+                          uint32_t width, uint32_t height, void *d_linear_out, void *d_rgba8_out,
+                          void *stream);
+
+/* Wait for the context's last rvcp_demodulate_async and / or rvcp_remodulate_async;
+ * *demodulate_ms / *remodulate_ms (optional) get their device times (HIP events on their
+ * streams; 0 for a step that was not enqueued since the last call).  RVCP_E_INVALID when
+ * neither was.  No counterpart in the reference. */
+int rvcp_albedo_wait(rvcp_ctx_t *ctx, float *demodulate_ms, float *remodulate_ms);
+
+/* The context's demodulation switch (default 0).  While it is 1, rvcp_render_denoised,
+ * rvcp_render_temporal and rvcp_render_svgf demodulate the raw frame right after the
+ * G-buffer, keep their histories (colour, and the moments of the irradiance's luminance) and
+ * filter in irradiance, and end with the fused remodulate + store: out_linear_rgb is the
+ * remodulated colour, out_variance the variance of the irradiance's luminance.  Changing the
+ * value drops both histories (as rvcp_temporal_reset and rvcp_svgf_reset); setting the value
+ * it has does nothing.  RVCP_E_INVALID while a frame is pending.
+ * No counterpart in the reference. */
+int rvcp_set_demodulation(rvcp_ctx_t *ctx, int on);
+
+/* *on = the context's demodulation switch.  No counterpart in the reference. */
+int rvcp_get_demodulation(rvcp_ctx_t *ctx, int *on);
+
 #ifdef __cplusplus
 }
 #endif

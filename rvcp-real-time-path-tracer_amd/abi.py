@@ -88,7 +88,9 @@ EXPORTED = ["rvcp_version", "rvcp_config_default", "rvcp_config_default_for", "r
             "rvcp_temporal_accumulate_async", "rvcp_temporal_wait", "rvcp_render_temporal",
             "rvcp_temporal_reset",
             "rvcp_svgf_params_default", "rvcp_svgf_accumulate_async", "rvcp_svgf_filter_async",
-            "rvcp_svgf_wait", "rvcp_render_svgf", "rvcp_svgf_reset"]
+            "rvcp_svgf_wait", "rvcp_render_svgf", "rvcp_svgf_reset",
+            "rvcp_demodulate_async", "rvcp_remodulate_async", "rvcp_albedo_wait",
+            "rvcp_set_demodulation", "rvcp_get_demodulation"]
 
 
 # Integrator mode 2 (ray_tracer.comp ray_trace): its own #defines (ray_tracer.comp:5-13).
@@ -247,6 +249,11 @@ def load():
     L.rvcp_svgf_wait.argtypes = [P, P, P]
     L.rvcp_render_svgf.argtypes = [P, P, u32, u32, P, P, u32, P, P, P, P, P, P, P]
     L.rvcp_svgf_reset.argtypes = [P]
+    L.rvcp_demodulate_async.argtypes = [P, P, P, u32, u32, P, P]
+    L.rvcp_remodulate_async.argtypes = [P, P, P, u32, u32, P, P, P]
+    L.rvcp_albedo_wait.argtypes = [P, P, P]
+    L.rvcp_set_demodulation.argtypes = [P, ctypes.c_int]
+    L.rvcp_get_demodulation.argtypes = [P, P]
     for name in ("rvcp_config_default", "rvcp_config_default_for", "rvcp_create", "rvcp_destroy", "rvcp_upload_scene",
                  "rvcp_render", "rvcp_render_shard_async", "rvcp_sync_stats",
                  "rvcp_assemble_frame_async", "rvcp_upload_scene_file", "rvcp_mandelbrot",
@@ -260,7 +267,8 @@ def load():
                  "rvcp_temporal_wait", "rvcp_render_temporal", "rvcp_temporal_reset",
                  "rvcp_svgf_params_default", "rvcp_svgf_accumulate_async",
                  "rvcp_svgf_filter_async", "rvcp_svgf_wait", "rvcp_render_svgf",
-                 "rvcp_svgf_reset"):
+                 "rvcp_svgf_reset", "rvcp_demodulate_async", "rvcp_remodulate_async",
+                 "rvcp_albedo_wait", "rvcp_set_demodulation", "rvcp_get_demodulation"):
         getattr(L, name).restype = ctypes.c_int
     if L.rvcp_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI revision {L.rvcp_abi_version()}, this binding "

@@ -178,6 +178,16 @@ struct rvcp_ctx {
     rvcp_camera_t sv_camera = {};       // ... rendered from this camera
     rvcp_temporal_view_t sv_view = {};  // ... whose projection this is
 
+    // albedo demodulation (rvcp_demodulate_async / rvcp_remodulate_async): the
+    // scene's albedo table (one float4 per material, made by every upload), an event pair per
+    // step, and the switch of rvcp_set_demodulation: while it is set rvcp_render_denoised,
+    // rvcp_render_temporal and rvcp_render_svgf filter irradiance
+    float *d_albedo = nullptr;
+    hipEvent_t evad0 = nullptr, evad1 = nullptr, evar0 = nullptr, evar1 = nullptr;
+    bool demod_recorded = false, demod_pending = false;
+    bool remod_recorded = false, remod_pending = false;
+    bool demodulation = false;
+
     // debug build: per-wave timeline of the path kernel appended per render
     unsigned long long *d_timeline = nullptr;
     size_t cap_timeline = 0, last_timeline_waves = 0;
@@ -373,6 +383,7 @@ void free_scene(rvcp_ctx *ctx)
     (void)hipFree(ctx->d_shade); ctx->d_shade = nullptr;
     (void)hipFree(ctx->d_lights); ctx->d_lights = nullptr;
     (void)hipFree(ctx->d_rawmats); ctx->d_rawmats = nullptr;
+    (void)hipFree(ctx->d_albedo); ctx->d_albedo = nullptr;
     (void)hipFree(ctx->d_spheres); ctx->d_spheres = nullptr;
     (void)hipFree(ctx->d_bvh_nodes); ctx->d_bvh_nodes = nullptr;
     (void)hipFree(ctx->d_bvh_tris); ctx->d_bvh_tris = nullptr;
@@ -630,6 +641,8 @@ static int impl_destroy(rvcp_ctx_t *ctx)
     if (ctx->temporal_recorded) (void)hipEventSynchronize(ctx->evt1);
     if (ctx->svgf_acc_recorded) (void)hipEventSynchronize(ctx->evsa1);
     if (ctx->svgf_flt_recorded) (void)hipEventSynchronize(ctx->evsf1);
+    if (ctx->demod_recorded) (void)hipEventSynchronize(ctx->evad1);
+    if (ctx->remod_recorded) (void)hipEventSynchronize(ctx->evar1);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm && ctx->comm_owned) (void)rccl_api().comm_destroy(ctx->comm);
     ctx->comm = nullptr;
@@ -673,6 +686,8 @@ static int impl_destroy(rvcp_ctx_t *ctx)
     (void)hipFree(ctx->d_sv_showvar);
     (void)hipFree(ctx->d_sv_fb);
     for (hipEvent_t e : {ctx->evsa0, ctx->evsa1, ctx->evsf0, ctx->evsf1})
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {ctx->evad0, ctx->evad1, ctx->evar0, ctx->evar1})
         if (e) (void)hipEventDestroy(e);
     if (ctx->evt0) (void)hipEventDestroy(ctx->evt0);
     if (ctx->evt1) (void)hipEventDestroy(ctx->evt1);
@@ -757,6 +772,14 @@ static int upload_one(rvcp_ctx_t *ctx, const rvcp_material_t *materials, uint32_
         (rc = dev_upload<rvcp_material_t>(ctx, &ctx->d_rawmats, materials, n_materials)) ||
         (rc = dev_upload<rvcp_sphere_t>(ctx, &ctx->d_spheres, spheres, n_spheres)))
         return rc;
+    {   // the albedo table of §4.12: the three floats as uploaded, 16 B per material
+        std::vector<float> alb((size_t)n_materials * 4, 0.0f);
+        for (uint32_t i = 0; i < n_materials; i++)
+            std::memcpy(&alb[(size_t)i * 4], materials[i].albedo, 12);
+        float4 *d_alb = nullptr;
+        if ((rc = dev_upload<float4>(ctx, &d_alb, alb.data(), n_materials))) return rc;
+        ctx->d_albedo = (float *)d_alb;
+    }
     ctx->n_spheres = n_spheres;
     ctx->bvh_prefix = 0;
     std::shared_ptr<JitKernels> bvh_jit;
@@ -1570,6 +1593,20 @@ static int impl_denoise_wait(rvcp_ctx_t *ctx, float *denoise_ms)
     return RVCP_OK;
 }
 
+// albedo demodulation (defined below, behind the SVGF steps they are ordered by)
+static int impl_demodulate_async(rvcp_ctx_t *ctx, const void *d_lin, const void *d_gbuffer,
+                                 uint32_t width, uint32_t height, void *d_out, void *stream);
+static int impl_remodulate_async(rvcp_ctx_t *ctx, const void *d_irr, const void *d_gbuffer,
+                                 uint32_t width, uint32_t height, void *d_lin_out,
+                                 void *d_rgba8_out, void *stream);
+static int impl_albedo_wait(rvcp_ctx_t *ctx, float *demodulate_ms, float *remodulate_ms);
+
+// the albedo steps a chain enqueued, waited for after a failure or at its end
+static void albedo_drain(rvcp_ctx_t *ctx)
+{
+    if (ctx->demod_pending || ctx->remod_pending) (void)impl_albedo_wait(ctx, nullptr, nullptr);
+}
+
 static int impl_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
                                 uint32_t height, const rvcp_denoise_params_t *params,
                                 uint8_t *out_rgba8, float *out_linear_rgb, rvcp_stats_t *stats,
@@ -1604,19 +1641,38 @@ static int impl_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
     // filter's RGBA8 store overwrites the render's
     if ((rc = rvcp_render_async(ctx, push, width, height, ctx->d_rgba, ctx->d_dn_in, ctx->stream)) != RVCP_OK)
         return rc;
-    if ((rc = impl_render_gbuffer_async(ctx, push, width, height, ctx->d_gbuf, ctx->stream)) != RVCP_OK ||
-        (rc = impl_denoise_async(ctx, ctx->d_dn_in, ctx->d_gbuf, width, height, params,
-                                 ctx->d_dn_out, ctx->d_rgba, ctx->stream)) != RVCP_OK) {
+    // With the demodulation switch set (§4.12): the raw frame is demodulated in place right after
+    // the G-buffer, the filter runs on irradiance without a store, and the fused remodulate +
+    // store writes the colour into d_dn_in (free by then) and the RGBA8 frame.
+    const bool demod = ctx->demodulation;
+    bool filter_enqueued = false;
+    rc = impl_render_gbuffer_async(ctx, push, width, height, ctx->d_gbuf, ctx->stream);
+    if (rc == RVCP_OK && demod)
+        rc = impl_demodulate_async(ctx, ctx->d_dn_in, ctx->d_gbuf, width, height, ctx->d_dn_in,
+                                   ctx->stream);
+    if (rc == RVCP_OK) {
+        rc = impl_denoise_async(ctx, ctx->d_dn_in, ctx->d_gbuf, width, height, params,
+                                ctx->d_dn_out, demod ? nullptr : ctx->d_rgba, ctx->stream);
+        filter_enqueued = rc == RVCP_OK;
+    }
+    if (rc == RVCP_OK && demod)
+        rc = impl_remodulate_async(ctx, ctx->d_dn_out, ctx->d_gbuf, width, height, ctx->d_dn_in,
+                                   ctx->d_rgba, ctx->stream);
+    if (rc != RVCP_OK) {
         const std::string why = ctx->err;
         (void)rvcp_wait(ctx, nullptr);          // the render is enqueued: leave no frame pending
+        if (filter_enqueued) (void)impl_denoise_wait(ctx, nullptr);
+        albedo_drain(ctx);
         ctx->err = why;
         return rc;
     }
     if ((rc = rvcp_wait(ctx, stats)) != RVCP_OK) return rc;
     if ((rc = impl_denoise_wait(ctx, denoise_ms)) != RVCP_OK) return rc;
+    if (demod && (rc = impl_albedo_wait(ctx, nullptr, nullptr)) != RVCP_OK) return rc;
     HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, npx * 4, hipMemcpyDeviceToHost));
     if (out_linear_rgb)
-        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, ctx->d_dn_out, npx * 12, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, demod ? ctx->d_dn_in : ctx->d_dn_out, npx * 12,
+                               hipMemcpyDeviceToHost));
     return RVCP_OK;
 }
 
@@ -1818,26 +1874,38 @@ static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
     // stream; the last RGBA8 store overwrites the render's
     if ((rc = rvcp_render_async(ctx, push, width, height, ctx->d_rgba, ctx->d_tp_cur, ctx->stream)) != RVCP_OK)
         return rc;
+    // With the demodulation switch set (§4.12): the raw frame is demodulated in place right after
+    // the G-buffer, history and filter are in irradiance and store nothing, and the fused
+    // remodulate + store writes the colour into d_tp_cur (free by then) and the RGBA8 frame.
+    const bool demod = ctx->demodulation;
     bool step_enqueued = false, filter_enqueued = false;
     rc = impl_render_gbuffer_async(ctx, push, width, height, ctx->d_tp_gbuf[cur], ctx->stream);
+    if (rc == RVCP_OK && demod)
+        rc = impl_demodulate_async(ctx, ctx->d_tp_cur, ctx->d_tp_gbuf[cur], width, height,
+                                   ctx->d_tp_cur, ctx->stream);
     if (rc == RVCP_OK) {
         rc = impl_temporal_accumulate_async(
             ctx, same_camera ? nullptr : &ctx->tp_view, ctx->d_tp_cur, ctx->d_tp_gbuf[cur],
             have ? ctx->d_tp_lin[prev] : nullptr, have ? ctx->d_tp_gbuf[prev] : nullptr,
             have ? ctx->d_tp_len[prev] : nullptr, width, height, tparams, ctx->d_tp_lin[cur],
-            ctx->d_tp_len[cur], denoise ? nullptr : ctx->d_rgba, ctx->stream);
+            ctx->d_tp_len[cur], denoise || demod ? nullptr : ctx->d_rgba, ctx->stream);
         step_enqueued = rc == RVCP_OK;
     }
     if (rc == RVCP_OK && denoise) {
         rc = impl_denoise_async(ctx, ctx->d_tp_lin[cur], ctx->d_tp_gbuf[cur], width, height, dparams,
-                                ctx->d_tp_show, ctx->d_rgba, ctx->stream);
+                                ctx->d_tp_show, demod ? nullptr : ctx->d_rgba, ctx->stream);
         filter_enqueued = rc == RVCP_OK;
     }
+    if (rc == RVCP_OK && demod)
+        rc = impl_remodulate_async(ctx, denoise ? ctx->d_tp_show : ctx->d_tp_lin[cur],
+                                   ctx->d_tp_gbuf[cur], width, height, ctx->d_tp_cur, ctx->d_rgba,
+                                   ctx->stream);
     if (rc != RVCP_OK) {
         const std::string why = ctx->err;
         (void)rvcp_wait(ctx, nullptr);          // the render is enqueued: leave nothing pending
         if (step_enqueued) (void)impl_temporal_wait(ctx, nullptr);
         if (filter_enqueued) (void)impl_denoise_wait(ctx, nullptr);
+        albedo_drain(ctx);
         ctx->err = why;
         return rc;
     }
@@ -1845,9 +1913,11 @@ static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
     if ((rc = impl_temporal_wait(ctx, temporal_ms)) != RVCP_OK) return rc;
     if (denoise_ms) *denoise_ms = 0.0f;
     if (denoise && (rc = impl_denoise_wait(ctx, denoise_ms)) != RVCP_OK) return rc;
+    if (demod && (rc = impl_albedo_wait(ctx, nullptr, nullptr)) != RVCP_OK) return rc;
     HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, npx * 4, hipMemcpyDeviceToHost));
     if (out_linear_rgb)
-        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, denoise ? ctx->d_tp_show : ctx->d_tp_lin[cur],
+        HIP_TRY(ctx, hipMemcpy(out_linear_rgb,
+                               demod ? ctx->d_tp_cur : denoise ? ctx->d_tp_show : ctx->d_tp_lin[cur],
                                npx * 12, hipMemcpyDeviceToHost));
     if (out_history_len)
         HIP_TRY(ctx, hipMemcpy(out_history_len, ctx->d_tp_len[cur], npx * 4, hipMemcpyDeviceToHost));
@@ -2115,6 +2185,132 @@ static void svgf_free_state(rvcp_ctx_t *ctx)
     ctx->cap_sv = 0;
 }
 
+// ---- albedo demodulation --------------------------------------------------
+
+// what both steps check before anything is enqueued (the restrictions of the G-buffer)
+static int albedo_checked(rvcp_ctx_t *ctx, uint32_t width, uint32_t height)
+{
+    if ((uint64_t)width * height >= (1ull << 31))
+        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
+        return fail(ctx, RVCP_E_UNSUPPORTED, "the G-buffer is implemented for the games101 integrator");
+    if (!ctx->subs.empty())
+        return fail(ctx, RVCP_E_UNSUPPORTED, "albedo demodulation drives one GPU (n_gpus = 1)");
+    if (!ctx->has_scene)
+        return fail(ctx, RVCP_E_NO_SCENE, "albedo demodulation before rvcp_upload_scene");
+    return RVCP_OK;
+}
+
+static int impl_demodulate_async(rvcp_ctx_t *ctx, const void *d_lin, const void *d_gbuffer,
+                                 uint32_t width, uint32_t height, void *d_out, void *stream)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!d_lin || !d_gbuffer || !d_out || width == 0 || height == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid demodulate arguments");
+    int rc;
+    if ((rc = albedo_checked(ctx, width, height)) != RVCP_OK) return rc;
+    const size_t npx = (size_t)width * height;
+    // a lane reads and writes its own pixel only: exactly in place is legal, a partial overlap
+    // is not
+    if (ranges_overlap(d_out, npx * 12, d_gbuffer, npx * 32) ||
+        (d_out != d_lin && ranges_overlap(d_out, npx * 12, d_lin, npx * 12)))
+        return fail(ctx, RVCP_E_INVALID, "demodulate output overlaps an input");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if (!ctx->evad0) {
+        HIP_TRY(ctx, hipEventCreate(&ctx->evad0));
+        HIP_TRY(ctx, hipEventCreate(&ctx->evad1));
+    }
+    if ((rc = svgf_order(ctx, s)) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->evad0, s));
+    if (rvcp_launch_demodulate((const float *)d_lin, d_gbuffer, ctx->d_albedo, ctx->n_mats,
+                               (float *)d_out, (uint32_t)npx, s) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string("demodulate launch failed: ") +
+                                         hipGetErrorString(hipGetLastError()));
+    HIP_TRY(ctx, hipEventRecord(ctx->evad1, s));
+    ctx->demod_recorded = true;
+    ctx->demod_pending = true;
+    return RVCP_OK;
+}
+
+static int impl_remodulate_async(rvcp_ctx_t *ctx, const void *d_irr, const void *d_gbuffer,
+                                 uint32_t width, uint32_t height, void *d_lin_out,
+                                 void *d_rgba8_out, void *stream)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!d_irr || !d_gbuffer || (!d_lin_out && !d_rgba8_out) || width == 0 || height == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid remodulate arguments");
+    int rc;
+    if ((rc = albedo_checked(ctx, width, height)) != RVCP_OK) return rc;
+    const size_t npx = (size_t)width * height;
+    {
+        const DevRange in[2] = {{d_irr, npx * 12}, {d_gbuffer, npx * 32}};
+        const DevRange out[2] = {{d_lin_out, npx * 12}, {d_rgba8_out, npx * 4}};
+        const char *what = nullptr;
+        if (outputs_overlap(in, 2, out, 2, &what))
+            return fail(ctx, RVCP_E_INVALID, std::string("remodulate ") + what);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if (!ctx->evar0) {
+        HIP_TRY(ctx, hipEventCreate(&ctx->evar0));
+        HIP_TRY(ctx, hipEventCreate(&ctx->evar1));
+    }
+    if ((rc = svgf_order(ctx, s)) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->evar0, s));
+    if (rvcp_launch_remodulate((const float *)d_irr, d_gbuffer, ctx->d_albedo, ctx->n_mats,
+                               ctx->d_gamma, (float *)d_lin_out, (uint32_t *)d_rgba8_out,
+                               (uint32_t)npx, s) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string("remodulate launch failed: ") +
+                                         hipGetErrorString(hipGetLastError()));
+    HIP_TRY(ctx, hipEventRecord(ctx->evar1, s));
+    ctx->remod_recorded = true;
+    ctx->remod_pending = true;
+    return RVCP_OK;
+}
+
+static int impl_albedo_wait(rvcp_ctx_t *ctx, float *demodulate_ms, float *remodulate_ms)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!ctx->demod_pending && !ctx->remod_pending)
+        return fail(ctx, RVCP_E_INVALID, "no albedo step in flight");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (demodulate_ms) *demodulate_ms = 0.0f;
+    if (remodulate_ms) *remodulate_ms = 0.0f;
+    if (ctx->demod_pending) {
+        HIP_TRY(ctx, hipEventSynchronize(ctx->evad1));
+        if (demodulate_ms) HIP_TRY(ctx, hipEventElapsedTime(demodulate_ms, ctx->evad0, ctx->evad1));
+        ctx->demod_pending = false;
+    }
+    if (ctx->remod_pending) {
+        HIP_TRY(ctx, hipEventSynchronize(ctx->evar1));
+        if (remodulate_ms) HIP_TRY(ctx, hipEventElapsedTime(remodulate_ms, ctx->evar0, ctx->evar1));
+        ctx->remod_pending = false;
+    }
+    return RVCP_OK;
+}
+
+static int impl_set_demodulation(rvcp_ctx_t *ctx, int on)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (ctx->pending)
+        return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    const bool want = on != 0;
+    if (want == ctx->demodulation) return RVCP_OK;
+    ctx->demodulation = want;
+    ctx->tp_valid = false;      // colour histories and irradiance histories do not mix
+    ctx->sv_valid = false;
+    return RVCP_OK;
+}
+
+static int impl_get_demodulation(rvcp_ctx_t *ctx, int *on)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!on) return fail(ctx, RVCP_E_INVALID, "invalid get_demodulation arguments");
+    *on = ctx->demodulation ? 1 : 0;
+    return RVCP_OK;
+}
+
 static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
                             uint32_t height, const rvcp_temporal_params_t *tparams,
                             const rvcp_svgf_params_t *sparams, uint32_t flags, uint8_t *out_rgba8,
@@ -2162,8 +2358,16 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
     // stream; the filter's RGBA8 store overwrites the render's
     if ((rc = rvcp_render_async(ctx, push, width, height, ctx->d_rgba, ctx->d_sv_cur, ctx->stream)) != RVCP_OK)
         return rc;
+    // With the demodulation switch set (§4.12): the raw frame is demodulated in place right after
+    // the G-buffer, colour history, moments and filter are in irradiance and store nothing, and
+    // the fused remodulate + store writes the colour into d_sv_cur (free by then) and the RGBA8
+    // frame.
+    const bool demod = ctx->demodulation;
     bool enqueued = false;
     rc = impl_render_gbuffer_async(ctx, push, width, height, ctx->d_sv_gbuf[cur], ctx->stream);
+    if (rc == RVCP_OK && demod)
+        rc = impl_demodulate_async(ctx, ctx->d_sv_cur, ctx->d_sv_gbuf[cur], width, height,
+                                   ctx->d_sv_cur, ctx->stream);
     if (rc == RVCP_OK) {
         rc = impl_svgf_accumulate_async(
             ctx, same_camera ? nullptr : &ctx->sv_view, ctx->d_sv_cur, ctx->d_sv_gbuf[cur],
@@ -2177,20 +2381,26 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
         rc = impl_svgf_filter_async(ctx, ctx->d_sv_lin[cur], ctx->d_sv_mom[cur], ctx->d_sv_len[cur],
                                     ctx->d_sv_gbuf[cur], width, height, sparams, ctx->d_sv_show,
                                     ctx->d_sv_showvar, feedback ? ctx->d_sv_fb : nullptr,
-                                    ctx->d_rgba, ctx->stream);
+                                    demod ? nullptr : ctx->d_rgba, ctx->stream);
     }
+    if (rc == RVCP_OK && demod)
+        rc = impl_remodulate_async(ctx, ctx->d_sv_show, ctx->d_sv_gbuf[cur], width, height,
+                                   ctx->d_sv_cur, ctx->d_rgba, ctx->stream);
     if (rc != RVCP_OK) {
         const std::string why = ctx->err;
         (void)rvcp_wait(ctx, nullptr);          // the render is enqueued: leave nothing pending
         if (enqueued) (void)impl_svgf_wait(ctx, nullptr, nullptr);
+        albedo_drain(ctx);
         ctx->err = why;
         return rc;
     }
     if ((rc = rvcp_wait(ctx, stats)) != RVCP_OK) return rc;
     if ((rc = impl_svgf_wait(ctx, accumulate_ms, filter_ms)) != RVCP_OK) return rc;
+    if (demod && (rc = impl_albedo_wait(ctx, nullptr, nullptr)) != RVCP_OK) return rc;
     HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, npx * 4, hipMemcpyDeviceToHost));
     if (out_linear_rgb)
-        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, ctx->d_sv_show, npx * 12, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, demod ? ctx->d_sv_cur : ctx->d_sv_show, npx * 12,
+                               hipMemcpyDeviceToHost));
     if (out_variance)
         HIP_TRY(ctx, hipMemcpy(out_variance, ctx->d_sv_showvar, npx * 4, hipMemcpyDeviceToHost));
     if (out_history_len)
@@ -2858,6 +3068,40 @@ int rvcp_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t
 int rvcp_svgf_reset(rvcp_ctx_t *ctx)
 {
     return barrier(ctx, [&] { return impl_svgf_reset(ctx); });
+}
+
+int rvcp_demodulate_async(rvcp_ctx_t *ctx, const void *d_linear, const void *d_gbuffer,
+                          uint32_t width, uint32_t height, void *d_irradiance_out, void *stream)
+{
+    return barrier(ctx, [&] {
+        return impl_demodulate_async(ctx, d_linear, d_gbuffer, width, height, d_irradiance_out,
+                                     stream);
+    });
+}
+
+int rvcp_remodulate_async(rvcp_ctx_t *ctx, const void *d_irradiance, const void *d_gbuffer,
+                          uint32_t width, uint32_t height, void *d_linear_out, void *d_rgba8_out,
+                          void *stream)
+{
+    return barrier(ctx, [&] {
+        return impl_remodulate_async(ctx, d_irradiance, d_gbuffer, width, height, d_linear_out,
+                                     d_rgba8_out, stream);
+    });
+}
+
+int rvcp_albedo_wait(rvcp_ctx_t *ctx, float *demodulate_ms, float *remodulate_ms)
+{
+    return barrier(ctx, [&] { return impl_albedo_wait(ctx, demodulate_ms, remodulate_ms); });
+}
+
+int rvcp_set_demodulation(rvcp_ctx_t *ctx, int on)
+{
+    return barrier(ctx, [&] { return impl_set_demodulation(ctx, on); });
+}
+
+int rvcp_get_demodulation(rvcp_ctx_t *ctx, int *on)
+{
+    return barrier(ctx, [&] { return impl_get_demodulation(ctx, on); });
 }
 
 }  // extern "C"

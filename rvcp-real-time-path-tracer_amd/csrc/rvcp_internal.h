@@ -362,6 +362,14 @@ int rvcp_launch_svgf_pass(const float *in_c, const float *in_v, const void *gbuf
                           float *out_v, uint32_t width, uint32_t height, uint32_t step,
                           uint32_t normal_power_log2, uint32_t use_lum, float sigma_l2,
                           float epsilon, float sigma_plane, uint32_t force_direct, void *stream);
+// Albedo demodulation (rvcp_albedo.hip) over n pixels: albedo is the context's
+// table of n_materials float4 (the albedo as uploaded); in == out is legal for the demodulation;
+// the remodulation writes out_lin and / or out_rgba (either may be null)
+int rvcp_launch_demodulate(const float *in, const void *gbuffer, const void *albedo,
+                           uint32_t n_materials, float *out, uint32_t n, void *stream);
+int rvcp_launch_remodulate(const float *in, const void *gbuffer, const void *albedo,
+                           uint32_t n_materials, const float *gamma_t, float *out_lin,
+                           uint32_t *out_rgba, uint32_t n, void *stream);
 int rvcp_launch_assemble(const uint32_t *gathered, uint32_t slot_rows, uint32_t width,
                          uint32_t height, uint32_t shard_count, uint32_t *frame, void *stream);
 int rvcp_launch_fill(uint32_t *out_rgba, float *out_lin, uint32_t n_pixels, uint32_t rgba,

@@ -31,6 +31,7 @@
 #include "rvcp_internal.h"
 #include "../../include/rvcp.h"
 #include "rvcp_sqrt.h"
+#include "rvcp_tonemap.h"
 
 namespace rvcp {
 namespace {
@@ -212,18 +213,9 @@ __device__ __forceinline__ float rcp_scan(float den) {
     return f;
 }
 
-// Tone map + UNORM8 (:498-500) by the threshold table of DESIGN.md §3.3.
-__device__ __forceinline__ uint32_t gamma_u8(float c, const float *__restrict__ T) {
-    const float x = (c > 0.0f) ? ((c < 1.0f) ? c : 1.0f) : 0.0f;
-    uint32_t lo = 0;
-#pragma unroll
-    for (uint32_t step = 128; step >= 1; step >>= 1)
-        if (x >= T[lo + step]) lo += step;
-    return lo;
-}
-
+// Tone map + UNORM8 (:498-500) by the threshold table of DESIGN.md §3.3 (rvcp_tonemap.h).
 __device__ __forceinline__ uint32_t pack_rgba(f3 c, const float *__restrict__ T) {
-    return gamma_u8(c.x, T) | (gamma_u8(c.y, T) << 8) | (gamma_u8(c.z, T) << 16) | 0xFF000000u;
+    return pack_rgb8(c.x, c.y, c.z, T);
 }
 
 __device__ __forceinline__ void store_pixel(uint32_t pix, f3 acc, const FrameArgs &A,

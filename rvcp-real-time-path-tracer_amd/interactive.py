@@ -157,7 +157,7 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
                  time_seed: Optional[Callable[[int], float]] = None,
                  dump_dir: Optional[str] = None, dump_format: str = "ppm",
                  on_fps: Optional[Callable[[int], None]] = None, denoise=None,
-                 temporal=None, svgf=None) -> dict:
+                 temporal=None, svgf=None, demodulate: Optional[bool] = None) -> dict:
     """``main_loop`` (ray_tracer.rs:22-100) without a window.
 
     Per frame: apply this frame's scripted events, count FPS (printed once a second as
@@ -173,7 +173,12 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
     (``tracer.render_svgf``: accumulation with moments, variance, variance-guided filter); it takes
     precedence over ``temporal`` (whose record, when given, supplies the accumulation's parameters)
     and ``denoise`` (ignored); None (default): unchanged behaviour.
+    ``demodulate``: True / False sets ``tracer.demodulation`` before the loop, so that the
+    ``denoise`` / ``temporal`` / ``svgf`` chains filter irradiance (colour / albedo of the primary
+    hit); None (default) leaves the tracer's switch as it is.
     Returns per-frame render times and the final camera."""
+    if demodulate is not None:
+        tracer.demodulation = bool(demodulate)
     info = RuntimeInfo(window_size=(width, height))
     by_frame: Dict[int, List[Event]] = {}
     for ev in events:

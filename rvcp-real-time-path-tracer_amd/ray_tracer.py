@@ -384,6 +384,48 @@ class RayTracer:
                                              ctypes.cast(ctypes.byref(f), ctypes.c_void_p)))
         return float(a.value), float(f.value)
 
+    # albedo demodulation
+    @property
+    def demodulation(self) -> bool:
+        """The context's demodulation switch (rvcp_get_demodulation / rvcp_set_demodulation):
+        while True, render_denoised, render_temporal and render_svgf filter irradiance (colour /
+        albedo of the primary hit) and multiply the albedo back in their store.  Changing it
+        drops both histories."""
+        on = ctypes.c_int(0)
+        self._check(self._lib.rvcp_get_demodulation(self._ctx, ctypes.cast(ctypes.byref(on),
+                                                                          ctypes.c_void_p)))
+        return bool(on.value)
+
+    @demodulation.setter
+    def demodulation(self, on: bool):
+        self._check(self._lib.rvcp_set_demodulation(self._ctx, 1 if on else 0))
+
+    def demodulate_async(self, d_linear: int, d_gbuffer: int, width, height,
+                         d_irradiance_out: int, stream: int = 0):
+        """rvcp_demodulate_async: enqueue colour / albedo of a linear-RGB frame in device memory
+        under a G-buffer; d_irradiance_out may be d_linear itself.  Wait with albedo_wait()."""
+        P = lambda a: ctypes.c_void_p(a) if a else None   # noqa: E731
+        self._check(self._lib.rvcp_demodulate_async(
+            self._ctx, P(d_linear), P(d_gbuffer), width, height, P(d_irradiance_out), P(stream)))
+
+    def remodulate_async(self, d_irradiance: int, d_gbuffer: int, width, height,
+                         d_linear_out: int = 0, d_rgba: int = 0, stream: int = 0):
+        """rvcp_remodulate_async: enqueue irradiance x albedo fused with the store: the linear
+        colour to d_linear_out and / or its gamma / UNORM8 bytes to d_rgba (one of them may be
+        0).  Wait with albedo_wait()."""
+        P = lambda a: ctypes.c_void_p(a) if a else None   # noqa: E731
+        self._check(self._lib.rvcp_remodulate_async(
+            self._ctx, P(d_irradiance), P(d_gbuffer), width, height, P(d_linear_out), P(d_rgba),
+            P(stream)))
+
+    def albedo_wait(self):
+        """rvcp_albedo_wait: block until the last demodulate_async / remodulate_async are done;
+        their device times (demodulate_ms, remodulate_ms), 0 for a step that was not enqueued."""
+        d, r = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        self._check(self._lib.rvcp_albedo_wait(self._ctx, ctypes.cast(ctypes.byref(d), ctypes.c_void_p),
+                                               ctypes.cast(ctypes.byref(r), ctypes.c_void_p)))
+        return float(d.value), float(r.value)
+
     def wait(self):
         """rvcp_wait: block until the last async render is done; returns its stats."""
         stats = np.zeros((), dtype=abi.STATS_DTYPE)

@@ -14,7 +14,7 @@ import ctypes
 import ctypes.util
 import enum
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 
@@ -339,6 +339,48 @@ def cornell_box() -> Scene:
     for base in range(28, 68, 4):   # tall box top + 4 sides, short box top + 4 sides
         qf(base, 0)
     return Scene(camera, materials, [], Mesh(V, F))
+
+
+# the checker floor's two albedos: clearly different hue (a red and a teal), nearly equal
+# luminance 0.2126 r + 0.7152 g + 0.0722 b (0.3815 and 0.3826), so a luminance weight alone does
+# not tell them apart
+CHECKER_ALBEDOS = ((0.70, 0.30, 0.25), (0.15, 0.45, 0.40))
+
+
+def checker_floor_scene(base: Optional[Scene] = None, n: int = 4,
+                        materials=CHECKER_ALBEDOS) -> Scene:
+    """The Cornell box (``base``: a scene with cornell_box()'s mesh layout; None = cornell_box())
+    with its bottom quad replaced by n x n coplanar quads of two alternating Lambertian
+    materials (``materials``: their two albedos), appended to the material list: the same plane
+    and the same normal on both sides of every material edge, which is what albedo demodulation
+    is for.  At n = 4 the box has 62 faces and still takes the
+    scene-specialised scan."""
+    if base is None:
+        base = cornell_box()
+    if n < 1 or len(materials) != 2:
+        raise ValueError("checker_floor_scene needs n >= 1 and two albedos")
+    BOTTOM = 24                                  # the bottom quad's first vertex (cornell_box)
+    W = f32(275.0)
+    V = list(base.mesh.vertices)
+    F = [f for f in base.mesh.faces if f.vertices[0] != BOTTOM]
+    if len(F) != len(base.mesh.faces) - 2:
+        raise ValueError("base does not have the Cornell box's mesh layout")
+    mats = list(base.materials)
+    ids = (len(mats), len(mats) + 1)
+    mats += [Material.new_lambertian(vec3(*materials[0])), Material.new_lambertian(vec3(*materials[1]))]
+    # grid lines: -W ... W in n steps, the ends exact
+    g = [f32(-W) if i == 0 else W if i == n else f32(f32(-W) + f32(f32(i) * f32(f32(2.0) * W / f32(n))))
+         for i in range(n + 1)]
+    up_n = vec3(0.0, 1.0, 0.0)
+    for i in range(n):
+        for j in range(n):
+            b = len(V)
+            for x, z in ((g[i], g[j]), (g[i], g[j + 1]), (g[i + 1], g[j + 1]), (g[i + 1], g[j])):
+                V.append(Vertex(vec3(x, 0.0, z), up_n))
+            m = ids[(i + j) & 1]
+            F.append(Face((b, b + 1, b + 2), m))
+            F.append(Face((b, b + 2, b + 3), m))
+    return Scene(base.camera, mats, list(base.spheres), Mesh(V, F))
 
 
 def rotated_scene(base: Scene, yaw_deg: float = 23.0, pitch_deg: float = 17.0,
