@@ -316,6 +316,20 @@ typedef struct rvcp_svgf_params {
     uint32_t _pad;                /* must be 0 */
 } rvcp_svgf_params_t;
 
+/* Temporal anti-aliasing: sub-pixel camera jitter and a clamped resolve.  No
+ * counterpart in the reference: sample_ray (ray_tracer_games101_branch.comp:217-235) sends every
+ * primary ray through the pixel centre. */
+#define RVCP_TAA_JITTER_PERIOD 16u
+
+/* Parameters of rvcp_taa_resolve_async (the rule's definition: DESIGN.md §4.13). */
+typedef struct rvcp_taa_params {
+    float alpha_min;        /* lower bound of the blend factor, 0..1 */
+    uint32_t max_history;   /* cap of the per-pixel history length, 1..65535 */
+    uint32_t clamp;         /* 1: the history is clamped into the colour box of the 3 x 3 current
+                               pixels (not on the frame's border); 0: it is not */
+    uint32_t _pad;          /* must be 0 */
+} rvcp_taa_params_t;
+
 /* Layout checks: sizes/offsets the reference's Rust structs and std140/std430 blocks imply. */
 #ifdef __cplusplus
 #define RVCP_STATIC_ASSERT(c, m) static_assert(c, m)
@@ -359,6 +373,10 @@ RVCP_STATIC_ASSERT(offsetof(rvcp_svgf_params_t, epsilon) == 16, "SvgfParams.epsi
 RVCP_STATIC_ASSERT(offsetof(rvcp_svgf_params_t, alpha_moments_min) == 20, "SvgfParams.alpha_moments_min @20");
 RVCP_STATIC_ASSERT(offsetof(rvcp_svgf_params_t, spatial_below) == 24, "SvgfParams.spatial_below @24");
 RVCP_STATIC_ASSERT(offsetof(rvcp_svgf_params_t, _pad) == 28, "SvgfParams._pad @28");
+RVCP_STATIC_ASSERT(sizeof(rvcp_taa_params_t) == 16, "TAA params are 16 B");
+RVCP_STATIC_ASSERT(offsetof(rvcp_taa_params_t, max_history) == 4, "TaaParams.max_history @4");
+RVCP_STATIC_ASSERT(offsetof(rvcp_taa_params_t, clamp) == 8, "TaaParams.clamp @8");
+RVCP_STATIC_ASSERT(offsetof(rvcp_taa_params_t, _pad) == 12, "TaaParams._pad @12");
 
 typedef struct rvcp_ctx rvcp_ctx_t;
 
@@ -851,6 +869,90 @@ int rvcp_set_demodulation(rvcp_ctx_t *ctx, int on);
 
 /* *on = the context's demodulation switch.  No counterpart in the reference. */
 int rvcp_get_demodulation(rvcp_ctx_t *ctx, int *on);
+
+/* ---------------------------------------------------------------------------------------
+ * Temporal anti-aliasing: the frame is rendered through a camera rotated by a sub-pixel jitter,
+ * another one each frame, and a resolve step accumulates the DISPLAYED colour (per channel the
+ * linear colour clamped to [0, 1], before gamma) on the unjittered pixel grid, the history
+ * clamped into the 3 x 3 neighbourhood of the current frame against ghosting (opt-in; no other
+ * entry point changes).  No counterpart in the reference.
+ * ------------------------------------------------------------------------------------- */
+
+/* The jitter of frame `frame_index`, in pixels: (halton(i, 2) - 1/2, halton(i, 3) - 1/2) with
+ * i = frame_index % RVCP_TAA_JITTER_PERIOD + 1, computed in double and rounded once.  Needs no
+ * device.  RVCP_E_INVALID: out_jitter NULL.  No counterpart in the reference. */
+int rvcp_taa_jitter(uint32_t frame_index, float out_jitter[2]);
+
+/* *out = *base with its camera's forward rotated by `jitter` pixels of a width x height frame:
+ * normalize(f^ + r^ jx / k + d^ jy / k) |forward|, with f^ = forward / |forward|, r^ =
+ * normalize(forward x up), d^ = normalize(forward x r^) and k exactly as
+ * rvcp_temporal_view_from_push has them; computed in double, each component rounded once.
+ * Position, up, fov, near / far and time are untouched, and a zero jitter returns base's bytes
+ * unchanged.  The rotation shifts the image by exactly `jitter` only at the frame's centre;
+ * towards the frame's edges the shift grows by up to 1 + tan^2 of the off-axis angle (about 1.13
+ * at the default 40 degree field of view) -- a jitter need not be uniform, and nothing in the
+ * resolve depends on it.  Needs no device.  RVCP_E_INVALID: NULL / zero arguments, a camera
+ * rvcp_temporal_view_from_push rejects, a jitter that is not finite or has a component outside
+ * [-1, 1].  No counterpart in the reference. */
+int rvcp_taa_jitter_push(const rvcp_push_constant_t *base, uint32_t width, uint32_t height,
+                         const float jitter[2], rvcp_push_constant_t *out);
+
+/* The default parameters: alpha_min 0.1, max_history 32, clamp 1.  Needs no device.
+ * No counterpart in the reference. */
+int rvcp_taa_params_default(rvcp_taa_params_t *params);
+
+/* Enqueue one resolve step on `stream` (NULL: the context's); stateless, every buffer is the
+ * caller's device memory.  d_cur_linear (W*H*3 floats) is the current frame as rendered through
+ * the jittered camera (filtered or not), d_cur_gbuffer (W*H texels) its G-buffer, of which only
+ * position and face are read; d_prev_resolved (W*H*3 floats) and d_prev_len (W*H uint32_t) the
+ * previous call's outputs -- both NULL: no history.  cur_view / prev_view are the UNJITTERED
+ * cameras of the two frames (rvcp_temporal_view_from_push); both NULL: the camera is at rest and
+ * pixel p continues the history of pixel p.  Two byte-equal records take that path too, so a
+ * camera at rest never resamples.  Written: d_out_resolved (W*H*3 floats; within [0, 1] when the
+ * history is), d_out_len (W*H uint32_t, 1 where a history starts) and, when d_rgba8_out is not
+ * NULL, pow(c, 0.6) of the result as RGBA8 under the context's unorm_rule, from the same
+ * kernel.  All arithmetic is single correctly rounded f32 operations in a fixed order
+ * (DESIGN.md §4.13), so the result is reproducible bit for bit.  params = NULL: the defaults.
+ * Needs no scene.  A render pending on the context is not an error: the step is ordered behind
+ * it, and behind the context's previous resolve.
+ * RVCP_E_INVALID: NULL / zero arguments, W*H >= 2^31, an output that overlaps an input or
+ * another output, one of d_prev_* or of the views without the other, alpha_min outside 0..1,
+ * max_history outside 1..65535, clamp not 0 or 1 (a NaN is outside every range), _pad != 0.
+ * No counterpart in the reference. */
+int rvcp_taa_resolve_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *cur_view,
+                           const rvcp_temporal_view_t *prev_view, const void *d_cur_linear,
+                           const void *d_cur_gbuffer, const void *d_prev_resolved,
+                           const void *d_prev_len, uint32_t width, uint32_t height,
+                           const rvcp_taa_params_t *params, void *d_out_resolved,
+                           void *d_out_len, void *d_rgba8_out, void *stream);
+
+/* Wait for the context's last rvcp_taa_resolve_async; *taa_ms (optional) gets its device time
+ * (HIP events on its stream).  RVCP_E_INVALID when no step was enqueued since the last call.
+ * No counterpart in the reference. */
+int rvcp_taa_wait(rvcp_ctx_t *ctx, float *taa_ms);
+
+/* The context's TAA switch (default 0).  While it is 1, rvcp_render_temporal and
+ * rvcp_render_svgf render the frame, its G-buffer and all of their own steps through
+ * rvcp_taa_jitter_push(push, W, H, rvcp_taa_jitter(counter)) -- their own histories then always
+ * reproject, through the jittered cameras -- and finish with rvcp_taa_resolve_async (default
+ * parameters) of their final linear colour (filtered as their flags say, remodulated when the
+ * demodulation switch is set) under the unjittered cameras; the resolve continues pixel by pixel
+ * when the 64 camera bytes of `push` equal the previous call's.  out_rgba8 and out_linear_rgb are
+ * the resolved frame; the other outputs are unchanged.  Each of the two keeps a TAA state of its
+ * own (resolved colour, length, unjittered camera, frame counter), dropped -- the counter
+ * restarting at 0 -- wherever its own history is dropped, and on rvcp_taa_reset.  Changing the
+ * value drops both chains' histories (as rvcp_set_demodulation); setting the value it has does
+ * nothing.  RVCP_E_INVALID while a frame is pending.  With the switch at 0 every output is what
+ * it is without this section.  rvcp_render_denoised is stateless and not affected.
+ * No counterpart in the reference. */
+int rvcp_set_taa(rvcp_ctx_t *ctx, int on);
+
+/* *on = the context's TAA switch.  No counterpart in the reference. */
+int rvcp_get_taa(rvcp_ctx_t *ctx, int *on);
+
+/* Drop the TAA states rvcp_render_temporal and rvcp_render_svgf keep on the context (their own
+ * histories stay); both frame counters restart at 0.  No counterpart in the reference. */
+int rvcp_taa_reset(rvcp_ctx_t *ctx);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,7 @@ The package directory name contains hyphens, so import it through ``rvcp_amd.py`
 repository root (``import rvcp_amd``), which loads this package under the name ``rvcp_amd``.
 """
 from . import abi, scene
+from .abi import taa_jitter, taa_jitter_push
 from .scene import (Camera, Face, Material, MaterialType, Mesh, Scene, Sphere, Vertex,
                     cornell_box, push_constant)
 from .ray_tracer import RayTracer, rccl_unique_id, shard_row_ids, shard_rows
@@ -15,4 +16,4 @@ from . import mandelbrot
 
 __all__ = ["abi", "scene", "frame", "interactive", "scene_io", "mandelbrot", "Camera", "Face", "Material", "MaterialType", "Mesh", "Scene",
            "Sphere", "Vertex", "cornell_box", "push_constant", "RayTracer", "rccl_unique_id",
-           "shard_rows", "shard_row_ids"]
+           "shard_rows", "shard_row_ids", "taa_jitter", "taa_jitter_push"]

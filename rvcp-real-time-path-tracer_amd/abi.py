@@ -52,6 +52,11 @@ SVGF_PARAMS_DTYPE = np.dtype([("iterations", "<u4"), ("normal_power_log2", "<u4"
 assert SVGF_PARAMS_DTYPE.itemsize == 32
 SVGF_MAX_ITERATIONS, SVGF_MAX_SPATIAL_BELOW = 8, 16
 SVGF_FEEDBACK = 1               # rvcp_render_svgf flags
+# rvcp_taa_params_t (temporal anti-aliasing: jitter and the clamped resolve)
+TAA_PARAMS_DTYPE = np.dtype([("alpha_min", "<f4"), ("max_history", "<u4"), ("clamp", "<u4"),
+                             ("_pad", "<u4")])
+assert TAA_PARAMS_DTYPE.itemsize == 16
+TAA_JITTER_PERIOD = 16
 # rvcp_stats_t.kernel_variant -> the dominant kernel's name as rocprofv3 reports it
 KERNEL_NAMES = {1: "games101_kernel", 2: "games101_dual_kernel", 3: "games101_path_kernel<5>",
                 4: "games101_tiled_kernel", 5: "games101_tiled_single_kernel",
@@ -90,7 +95,10 @@ EXPORTED = ["rvcp_version", "rvcp_config_default", "rvcp_config_default_for", "r
             "rvcp_svgf_params_default", "rvcp_svgf_accumulate_async", "rvcp_svgf_filter_async",
             "rvcp_svgf_wait", "rvcp_render_svgf", "rvcp_svgf_reset",
             "rvcp_demodulate_async", "rvcp_remodulate_async", "rvcp_albedo_wait",
-            "rvcp_set_demodulation", "rvcp_get_demodulation"]
+            "rvcp_set_demodulation", "rvcp_get_demodulation",
+            "rvcp_taa_jitter", "rvcp_taa_jitter_push", "rvcp_taa_params_default",
+            "rvcp_taa_resolve_async", "rvcp_taa_wait", "rvcp_set_taa", "rvcp_get_taa",
+            "rvcp_taa_reset"]
 
 
 # Integrator mode 2 (ray_tracer.comp ray_trace): its own #defines (ray_tracer.comp:5-13).
@@ -149,6 +157,41 @@ def make_svgf_params(**overrides) -> np.ndarray:
     for k, v in overrides.items():
         p[k] = v
     return p
+
+
+def make_taa_params(**overrides) -> np.ndarray:
+    """rvcp_taa_params_t with the library's defaults (rvcp_taa_params_default), overridden by the
+    keyword arguments."""
+    p = np.zeros((), dtype=TAA_PARAMS_DTYPE)
+    rc = load().rvcp_taa_params_default(ptr(p))
+    if rc != RVCP_OK:
+        raise RvcpError(rc, "rvcp_taa_params_default failed")
+    for k, v in overrides.items():
+        p[k] = v
+    return p
+
+
+def taa_jitter(frame_index: int) -> np.ndarray:
+    """rvcp_taa_jitter: the sub-pixel jitter (jx, jy) of frame `frame_index`, in pixels: the
+    Halton(2, 3) point of index frame_index % TAA_JITTER_PERIOD + 1, centred."""
+    j = np.zeros(2, dtype=np.float32)
+    rc = load().rvcp_taa_jitter(int(frame_index) & 0xFFFFFFFF, ptr(j))
+    if rc != RVCP_OK:
+        raise RvcpError(rc, "rvcp_taa_jitter failed")
+    return j
+
+
+def taa_jitter_push(push, width: int, height: int, jitter) -> np.ndarray:
+    """rvcp_taa_jitter_push: a copy of `push` whose camera looks `jitter` pixels off (forward
+    rotated towards right / down, its length kept); a zero jitter returns the same bytes."""
+    from .scene import PUSH_DTYPE
+    push = np.ascontiguousarray(push, dtype=PUSH_DTYPE)
+    j = np.ascontiguousarray(jitter, dtype=np.float32).reshape(2)
+    out = np.zeros_like(push)
+    rc = load().rvcp_taa_jitter_push(ptr(push), width, height, ptr(j), ptr(out))
+    if rc != RVCP_OK:
+        raise RvcpError(rc, "rvcp_taa_jitter_push failed")
+    return out
 
 
 def temporal_view(push, width: int, height: int) -> np.ndarray:
@@ -254,6 +297,14 @@ def load():
     L.rvcp_albedo_wait.argtypes = [P, P, P]
     L.rvcp_set_demodulation.argtypes = [P, ctypes.c_int]
     L.rvcp_get_demodulation.argtypes = [P, P]
+    L.rvcp_taa_jitter.argtypes = [u32, P]
+    L.rvcp_taa_jitter_push.argtypes = [P, u32, u32, P, P]
+    L.rvcp_taa_params_default.argtypes = [P]
+    L.rvcp_taa_resolve_async.argtypes = [P, P, P, P, P, P, P, u32, u32, P, P, P, P, P]
+    L.rvcp_taa_wait.argtypes = [P, P]
+    L.rvcp_set_taa.argtypes = [P, ctypes.c_int]
+    L.rvcp_get_taa.argtypes = [P, P]
+    L.rvcp_taa_reset.argtypes = [P]
     for name in ("rvcp_config_default", "rvcp_config_default_for", "rvcp_create", "rvcp_destroy", "rvcp_upload_scene",
                  "rvcp_render", "rvcp_render_shard_async", "rvcp_sync_stats",
                  "rvcp_assemble_frame_async", "rvcp_upload_scene_file", "rvcp_mandelbrot",
@@ -268,7 +319,10 @@ def load():
                  "rvcp_svgf_params_default", "rvcp_svgf_accumulate_async",
                  "rvcp_svgf_filter_async", "rvcp_svgf_wait", "rvcp_render_svgf",
                  "rvcp_svgf_reset", "rvcp_demodulate_async", "rvcp_remodulate_async",
-                 "rvcp_albedo_wait", "rvcp_set_demodulation", "rvcp_get_demodulation"):
+                 "rvcp_albedo_wait", "rvcp_set_demodulation", "rvcp_get_demodulation",
+                 "rvcp_taa_jitter", "rvcp_taa_jitter_push", "rvcp_taa_params_default",
+                 "rvcp_taa_resolve_async", "rvcp_taa_wait", "rvcp_set_taa", "rvcp_get_taa",
+                 "rvcp_taa_reset"):
         getattr(L, name).restype = ctypes.c_int
     if L.rvcp_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI revision {L.rvcp_abi_version()}, this binding "

@@ -188,6 +188,23 @@ struct rvcp_ctx {
     bool remod_recorded = false, remod_pending = false;
     bool demodulation = false;
 
+    // temporal anti-aliasing (rvcp_taa_resolve_async): an event pair for the
+    // step, the switch of rvcp_set_taa, and one TAA state per stateful chain: the resolved colour
+    // and its lengths ping-pong between slots `slot` (the previous frame) and slot ^ 1
+    hipEvent_t evta0 = nullptr, evta1 = nullptr;
+    bool taa_recorded = false, taa_pending = false;
+    bool taa = false;
+    struct TaaState {
+        float *d_res[2] = {nullptr, nullptr};
+        uint32_t *d_len[2] = {nullptr, nullptr};
+        size_t cap = 0;
+        uint32_t slot = 0, width = 0, height = 0;
+        bool valid = false;                 // slot `slot` holds a resolved frame of width x height
+        rvcp_camera_t camera = {};          // ... under this unjittered camera
+        rvcp_temporal_view_t view = {};     // ... whose projection this is
+        uint32_t counter = 0;               // the next frame's index into the jitter sequence
+    } taa_tp, taa_sv;                       // of rvcp_render_temporal / rvcp_render_svgf
+
     // debug build: per-wave timeline of the path kernel appended per render
     unsigned long long *d_timeline = nullptr;
     size_t cap_timeline = 0, last_timeline_waves = 0;
@@ -643,6 +660,7 @@ static int impl_destroy(rvcp_ctx_t *ctx)
     if (ctx->svgf_flt_recorded) (void)hipEventSynchronize(ctx->evsf1);
     if (ctx->demod_recorded) (void)hipEventSynchronize(ctx->evad1);
     if (ctx->remod_recorded) (void)hipEventSynchronize(ctx->evar1);
+    if (ctx->taa_recorded) (void)hipEventSynchronize(ctx->evta1);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm && ctx->comm_owned) (void)rccl_api().comm_destroy(ctx->comm);
     ctx->comm = nullptr;
@@ -685,6 +703,13 @@ static int impl_destroy(rvcp_ctx_t *ctx)
     (void)hipFree(ctx->d_sv_show);
     (void)hipFree(ctx->d_sv_showvar);
     (void)hipFree(ctx->d_sv_fb);
+    for (rvcp_ctx::TaaState *st : {&ctx->taa_tp, &ctx->taa_sv})
+        for (int i = 0; i < 2; ++i) {
+            (void)hipFree(st->d_res[i]);
+            (void)hipFree(st->d_len[i]);
+        }
+    if (ctx->evta0) (void)hipEventDestroy(ctx->evta0);
+    if (ctx->evta1) (void)hipEventDestroy(ctx->evta1);
     for (hipEvent_t e : {ctx->evsa0, ctx->evsa1, ctx->evsf0, ctx->evsf1})
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : {ctx->evad0, ctx->evad1, ctx->evar0, ctx->evar1})
@@ -1817,6 +1842,244 @@ static int impl_temporal_reset(rvcp_ctx_t *ctx)
     return RVCP_OK;
 }
 
+// ---- temporal anti-aliasing: jitter and resolve --------------------------
+
+static int impl_taa_params_default(rvcp_taa_params_t *params)
+{
+    if (!params) return RVCP_E_INVALID;
+    params->alpha_min = 0.1f;
+    params->max_history = 32;
+    params->clamp = 1;
+    params->_pad = 0;
+    return RVCP_OK;
+}
+
+// the radical inverse of i in base b (exact sums of a few negative powers in double)
+static double halton(uint32_t i, uint32_t b)
+{
+    double f = 1.0, r = 0.0;
+    while (i > 0) {
+        f /= (double)b;
+        r += f * (double)(i % b);
+        i /= b;
+    }
+    return r;
+}
+
+static int impl_taa_jitter(uint32_t frame_index, float out_jitter[2])
+{
+    if (!out_jitter) return RVCP_E_INVALID;
+    const uint32_t i = frame_index % RVCP_TAA_JITTER_PERIOD + 1u;
+    out_jitter[0] = (float)(halton(i, 2) - 0.5);
+    out_jitter[1] = (float)(halton(i, 3) - 0.5);
+    return RVCP_OK;
+}
+
+// The camera of impl_temporal_view_from_push with its forward turned by jitter / k towards right
+// and down, keeping its length.  Everything in double, each output rounded once.
+static int impl_taa_jitter_push(const rvcp_push_constant_t *base, uint32_t width, uint32_t height,
+                                const float jitter[2], rvcp_push_constant_t *out)
+{
+    if (!base || !jitter || !out || width == 0 || height == 0) return RVCP_E_INVALID;
+    // (negated compares: a NaN is rejected too)
+    if (!(jitter[0] >= -1.0f && jitter[0] <= 1.0f && jitter[1] >= -1.0f && jitter[1] <= 1.0f))
+        return RVCP_E_INVALID;
+    const rvcp_camera_t &c = base->camera;
+    const double f[3] = {c.forward[0], c.forward[1], c.forward[2]};
+    const double up[3] = {c.up[0], c.up[1], c.up[2]};
+    double r[3] = {f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]};
+    const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    const double ff = f[0] * f[0] + f[1] * f[1] + f[2] * f[2];
+    if (!(rl > 0.0) || !(ff > 0.0)) return RVCP_E_INVALID;
+    for (double &v : r) v /= rl;
+    double d[3] = {f[1] * r[2] - f[2] * r[1], f[2] * r[0] - f[0] * r[2], f[0] * r[1] - f[1] * r[0]};
+    const double dl = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    if (!(dl > 0.0)) return RVCP_E_INVALID;
+    const rvcp_push_constant_t copy = *base;        // (out may be base)
+    *out = copy;
+    if (jitter[0] == 0.0f && jitter[1] == 0.0f) return RVCP_OK;
+    const double PI = 3.1415926;      // the shader's constant (:15)
+    const double k = (double)height / (2.0 * std::tan((double)c.vertical_fov / 2.0 * PI / 180.0));
+    const double fl = std::sqrt(ff), jx = (double)jitter[0] / k, jy = (double)jitter[1] / k;
+    double n[3];
+    for (int i = 0; i < 3; ++i) n[i] = f[i] / fl + r[i] * jx + (d[i] / dl) * jy;
+    const double nl = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    for (int i = 0; i < 3; ++i) out->camera.forward[i] = (float)(n[i] / nl * fl);
+    return RVCP_OK;
+}
+
+static int impl_taa_resolve_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *cur_view,
+                                  const rvcp_temporal_view_t *prev_view, const void *d_cur,
+                                  const void *d_cur_g, const void *d_prev, const void *d_prev_len,
+                                  uint32_t width, uint32_t height, const rvcp_taa_params_t *params,
+                                  void *d_out, void *d_out_len, void *d_rgba8_out, void *stream)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!d_cur || !d_cur_g || !d_out || !d_out_len || width == 0 || height == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid TAA resolve arguments");
+    if ((uint64_t)width * height >= (1ull << 31))
+        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    if ((d_prev == nullptr) != (d_prev_len == nullptr))
+        return fail(ctx, RVCP_E_INVALID, "TAA history needs d_prev_resolved and d_prev_len together");
+    if ((cur_view == nullptr) != (prev_view == nullptr))
+        return fail(ctx, RVCP_E_INVALID, "TAA resolve needs both views or neither");
+    rvcp_taa_params_t P;
+    if (params) P = *params;
+    else (void)impl_taa_params_default(&P);
+    // (negated compares: a NaN is rejected too)
+    if (!(P.alpha_min >= 0.0f && P.alpha_min <= 1.0f))
+        return fail(ctx, RVCP_E_INVALID, "TAA alpha_min must be in 0..1");
+    if (P.max_history < 1 || P.max_history > RVCP_TEMPORAL_MAX_HISTORY)
+        return fail(ctx, RVCP_E_INVALID, "TAA max_history must be in 1..65535");
+    if (P.clamp > 1)
+        return fail(ctx, RVCP_E_INVALID, "TAA clamp must be 0 or 1");
+    if (P._pad != 0)
+        return fail(ctx, RVCP_E_INVALID, "TAA params._pad must be 0");
+    const size_t npx = (size_t)width * height;
+    {   // a lane reads its neighbours' colours and history: no output may overlap an input or
+        // another output
+        const struct { const void *p; size_t n; } in[4] = {
+            {d_cur, npx * 12}, {d_cur_g, npx * 32}, {d_prev, npx * 12}, {d_prev_len, npx * 4}};
+        const struct { const void *p; size_t n; } out[3] = {
+            {d_out, npx * 12}, {d_out_len, npx * 4}, {d_rgba8_out, npx * 4}};
+        for (int o = 0; o < 3; ++o) {
+            for (int i = 0; i < 4; ++i)
+                if (ranges_overlap(out[o].p, out[o].n, in[i].p, in[i].n))
+                    return fail(ctx, RVCP_E_INVALID, "TAA output overlaps an input");
+            for (int q = o + 1; q < 3; ++q)
+                if (ranges_overlap(out[o].p, out[o].n, out[q].p, out[q].n))
+                    return fail(ctx, RVCP_E_INVALID, "TAA outputs overlap each other");
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if (!ctx->evta0) {
+        HIP_TRY(ctx, hipEventCreate(&ctx->evta0));
+        HIP_TRY(ctx, hipEventCreate(&ctx->evta1));
+    }
+    // behind a render pending on this context (when it runs on another stream), and behind the
+    // context's previous resolve, whose outputs are usually this one's history
+    if (ctx->pending && ctx->render_stream != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev1, 0));
+    if (ctx->taa_recorded) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evta1, 0));
+    HIP_TRY(ctx, hipEventRecord(ctx->evta0, s));
+    // a camera at rest fetches q = p exactly and never resamples: byte-equal views are no views
+    const bool moved = cur_view && std::memcmp(cur_view, prev_view, sizeof(*cur_view)) != 0;
+    const uint32_t mode = !d_prev ? 0u : moved ? 2u : 1u;
+    if (rvcp_launch_taa_resolve((const float *)d_cur, d_cur_g, (const float *)d_prev,
+                                (const uint32_t *)d_prev_len, (float *)d_out, (uint32_t *)d_out_len,
+                                (uint32_t *)d_rgba8_out, ctx->d_gamma, width, height, mode, cur_view,
+                                prev_view, &P, s) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string("TAA resolve launch failed: ") +
+                                         hipGetErrorString(hipGetLastError()));
+    HIP_TRY(ctx, hipEventRecord(ctx->evta1, s));
+    ctx->taa_recorded = true;
+    ctx->taa_pending = true;
+    return RVCP_OK;
+}
+
+static int impl_taa_wait(rvcp_ctx_t *ctx, float *taa_ms)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!ctx->taa_pending) return fail(ctx, RVCP_E_INVALID, "no TAA resolve in flight");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->evta1));
+    if (taa_ms) HIP_TRY(ctx, hipEventElapsedTime(taa_ms, ctx->evta0, ctx->evta1));
+    ctx->taa_pending = false;
+    return RVCP_OK;
+}
+
+static int impl_set_taa(rvcp_ctx_t *ctx, int on)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (ctx->pending)
+        return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    const bool want = on != 0;
+    if (want == ctx->taa) return RVCP_OK;
+    ctx->taa = want;
+    ctx->tp_valid = false;      // histories of centred and of jittered frames do not mix
+    ctx->sv_valid = false;
+    ctx->taa_tp.valid = false;
+    ctx->taa_sv.valid = false;
+    return RVCP_OK;
+}
+
+static int impl_get_taa(rvcp_ctx_t *ctx, int *on)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!on) return fail(ctx, RVCP_E_INVALID, "invalid get_taa arguments");
+    *on = ctx->taa ? 1 : 0;
+    return RVCP_OK;
+}
+
+static int impl_taa_reset(rvcp_ctx_t *ctx)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    ctx->taa_tp.valid = false;
+    ctx->taa_sv.valid = false;
+    return RVCP_OK;
+}
+
+// What a stateful chain does for its TAA state `st` before it renders (the switch is on):
+// `have` says whether the chain's own history continues.  *jpush becomes the jittered push of this
+// frame, *resume whether the resolve has a history, and the state's buffers hold npx pixels.
+static int taa_chain_begin(rvcp_ctx_t *ctx, rvcp_ctx::TaaState &st, bool have,
+                           const rvcp_push_constant_t *push, uint32_t width, uint32_t height,
+                           rvcp_push_constant_t *jpush, bool *resume)
+{
+    const size_t npx = (size_t)width * height;
+    if (st.cap < npx) {
+        st.valid = false;
+        st.cap = 0;
+        for (int i = 0; i < 2; ++i) {
+            (void)hipFree(st.d_res[i]);
+            (void)hipFree(st.d_len[i]);
+            st.d_res[i] = nullptr;
+            st.d_len[i] = nullptr;
+        }
+        for (int i = 0; i < 2; ++i) {
+            HIP_TRY(ctx, hipMalloc((void **)&st.d_res[i], npx * 12));
+            HIP_TRY(ctx, hipMalloc((void **)&st.d_len[i], npx * 4));
+        }
+        st.cap = npx;
+    }
+    *resume = have && st.valid && st.width == width && st.height == height;
+    if (!*resume) st.counter = 0;       // the state is dropped with the chain's history
+    st.valid = false;                   // until this frame is complete
+    float j[2];
+    (void)impl_taa_jitter(st.counter, j);
+    if (impl_taa_jitter_push(push, width, height, j, jpush) != RVCP_OK)
+        return fail(ctx, RVCP_E_INVALID, "the camera's forward is zero or parallel to up");
+    return RVCP_OK;
+}
+
+// ... and behind its last step: the resolve of d_final under the unjittered cameras into the
+// state's free slot and d_rgba
+static int taa_chain_resolve(rvcp_ctx_t *ctx, rvcp_ctx::TaaState &st, bool resume,
+                             const rvcp_push_constant_t *push, const rvcp_temporal_view_t *base_view,
+                             const float *d_final, const void *d_gbuffer, uint32_t width,
+                             uint32_t height)
+{
+    const uint32_t prev = st.slot, cur = prev ^ 1u;
+    const bool at_rest = resume && std::memcmp(&st.camera, &push->camera, sizeof(rvcp_camera_t)) == 0;
+    return impl_taa_resolve_async(ctx, at_rest ? nullptr : base_view, at_rest ? nullptr : &st.view,
+                                  d_final, d_gbuffer, resume ? st.d_res[prev] : nullptr,
+                                  resume ? st.d_len[prev] : nullptr, width, height, nullptr,
+                                  st.d_res[cur], st.d_len[cur], ctx->d_rgba, ctx->stream);
+}
+
+// ... and once the frame is complete
+static void taa_chain_commit(rvcp_ctx::TaaState &st, const rvcp_push_constant_t *push,
+                             const rvcp_temporal_view_t *base_view, uint32_t width, uint32_t height)
+{
+    st.slot ^= 1u;
+    st.width = width;
+    st.height = height;
+    st.camera = push->camera;
+    st.view = *base_view;
+    st.counter += 1;
+    st.valid = true;
+}
+
 static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
                                 uint32_t height, const rvcp_temporal_params_t *tparams,
                                 uint32_t flags, const rvcp_denoise_params_t *dparams,
@@ -1867,7 +2130,25 @@ static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
         (rc = grow(ctx, (void **)&ctx->d_tp_show, &ctx->cap_tp_show, npx, 12)) != RVCP_OK)
         return rc;
     const bool have = ctx->tp_valid && ctx->tp_width == width && ctx->tp_height == height;
-    const bool same_camera = have && std::memcmp(&ctx->tp_camera, &push->camera, sizeof(rvcp_camera_t)) == 0;
+    // With the TAA switch set (§4.13): everything below runs through the jittered camera `jpush`,
+    // the chain's own history always reprojects (through the jittered cameras), no step stores
+    // RGBA8, and the resolve of the final linear colour under the unjittered cameras ends the frame.
+    const bool taa = ctx->taa;
+    const rvcp_push_constant_t *const base_push = push;
+    const rvcp_temporal_view_t base_view = view_now;
+    rvcp_push_constant_t jpush;
+    bool taa_resume = false;
+    if (taa) {
+        if ((rc = taa_chain_begin(ctx, ctx->taa_tp, have, base_push, width, height, &jpush,
+                                  &taa_resume)) != RVCP_OK)
+            return rc;
+        push = &jpush;
+        if (impl_temporal_view_from_push(push, width, height, &view_now) != RVCP_OK)
+            return fail(ctx, RVCP_E_INVALID, "render_temporal: the camera's forward is zero or parallel to up");
+    }
+    const bool same_camera = !taa && have &&
+                             std::memcmp(&ctx->tp_camera, &push->camera, sizeof(rvcp_camera_t)) == 0;
+    uint32_t *const store = taa ? nullptr : ctx->d_rgba;    // the chain's own RGBA8 store
     const uint32_t prev = ctx->tp_slot, cur = prev ^ 1u;
     ctx->tp_valid = false;              // until this frame is complete
     // render (raw linear frame), G-buffer, accumulation [, filter], in this order on the context's
@@ -1888,18 +2169,26 @@ static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
             ctx, same_camera ? nullptr : &ctx->tp_view, ctx->d_tp_cur, ctx->d_tp_gbuf[cur],
             have ? ctx->d_tp_lin[prev] : nullptr, have ? ctx->d_tp_gbuf[prev] : nullptr,
             have ? ctx->d_tp_len[prev] : nullptr, width, height, tparams, ctx->d_tp_lin[cur],
-            ctx->d_tp_len[cur], denoise || demod ? nullptr : ctx->d_rgba, ctx->stream);
+            ctx->d_tp_len[cur], denoise || demod ? nullptr : store, ctx->stream);
         step_enqueued = rc == RVCP_OK;
     }
     if (rc == RVCP_OK && denoise) {
         rc = impl_denoise_async(ctx, ctx->d_tp_lin[cur], ctx->d_tp_gbuf[cur], width, height, dparams,
-                                ctx->d_tp_show, demod ? nullptr : ctx->d_rgba, ctx->stream);
+                                ctx->d_tp_show, demod ? nullptr : store, ctx->stream);
         filter_enqueued = rc == RVCP_OK;
     }
     if (rc == RVCP_OK && demod)
         rc = impl_remodulate_async(ctx, denoise ? ctx->d_tp_show : ctx->d_tp_lin[cur],
-                                   ctx->d_tp_gbuf[cur], width, height, ctx->d_tp_cur, ctx->d_rgba,
+                                   ctx->d_tp_gbuf[cur], width, height, ctx->d_tp_cur, store,
                                    ctx->stream);
+    // the displayed linear frame
+    const float *d_final = demod ? ctx->d_tp_cur : denoise ? ctx->d_tp_show : ctx->d_tp_lin[cur];
+    bool resolve_enqueued = false;
+    if (rc == RVCP_OK && taa) {
+        rc = taa_chain_resolve(ctx, ctx->taa_tp, taa_resume, base_push, &base_view, d_final,
+                               ctx->d_tp_gbuf[cur], width, height);
+        resolve_enqueued = rc == RVCP_OK;
+    }
     if (rc != RVCP_OK) {
         const std::string why = ctx->err;
         (void)rvcp_wait(ctx, nullptr);          // the render is enqueued: leave nothing pending
@@ -1914,11 +2203,13 @@ static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
     if (denoise_ms) *denoise_ms = 0.0f;
     if (denoise && (rc = impl_denoise_wait(ctx, denoise_ms)) != RVCP_OK) return rc;
     if (demod && (rc = impl_albedo_wait(ctx, nullptr, nullptr)) != RVCP_OK) return rc;
+    if (resolve_enqueued) {
+        if ((rc = impl_taa_wait(ctx, nullptr)) != RVCP_OK) return rc;
+        d_final = ctx->taa_tp.d_res[ctx->taa_tp.slot ^ 1u];
+    }
     HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, npx * 4, hipMemcpyDeviceToHost));
     if (out_linear_rgb)
-        HIP_TRY(ctx, hipMemcpy(out_linear_rgb,
-                               demod ? ctx->d_tp_cur : denoise ? ctx->d_tp_show : ctx->d_tp_lin[cur],
-                               npx * 12, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, d_final, npx * 12, hipMemcpyDeviceToHost));
     if (out_history_len)
         HIP_TRY(ctx, hipMemcpy(out_history_len, ctx->d_tp_len[cur], npx * 4, hipMemcpyDeviceToHost));
     ctx->tp_slot = cur;
@@ -1927,6 +2218,7 @@ static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
     ctx->tp_camera = push->camera;
     ctx->tp_view = view_now;
     ctx->tp_valid = true;
+    if (taa) taa_chain_commit(ctx->taa_tp, base_push, &base_view, width, height);
     return RVCP_OK;
 }
 
@@ -2351,7 +2643,23 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
         ctx->cap_sv = npx;
     }
     const bool have = ctx->sv_valid && ctx->sv_width == width && ctx->sv_height == height;
-    const bool same_camera = have && std::memcmp(&ctx->sv_camera, &push->camera, sizeof(rvcp_camera_t)) == 0;
+    // With the TAA switch set (§4.13): as rvcp_render_temporal
+    const bool taa = ctx->taa;
+    const rvcp_push_constant_t *const base_push = push;
+    const rvcp_temporal_view_t base_view = view_now;
+    rvcp_push_constant_t jpush;
+    bool taa_resume = false;
+    if (taa) {
+        if ((rc = taa_chain_begin(ctx, ctx->taa_sv, have, base_push, width, height, &jpush,
+                                  &taa_resume)) != RVCP_OK)
+            return rc;
+        push = &jpush;
+        if (impl_temporal_view_from_push(push, width, height, &view_now) != RVCP_OK)
+            return fail(ctx, RVCP_E_INVALID, "render_svgf: the camera's forward is zero or parallel to up");
+    }
+    const bool same_camera = !taa && have &&
+                             std::memcmp(&ctx->sv_camera, &push->camera, sizeof(rvcp_camera_t)) == 0;
+    uint32_t *const store = taa ? nullptr : ctx->d_rgba;    // the chain's own RGBA8 store
     const uint32_t prev = ctx->sv_slot, cur = prev ^ 1u;
     ctx->sv_valid = false;              // until this frame is complete
     // render (raw linear frame), G-buffer, accumulation, filter, in this order on the context's
@@ -2381,11 +2689,18 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
         rc = impl_svgf_filter_async(ctx, ctx->d_sv_lin[cur], ctx->d_sv_mom[cur], ctx->d_sv_len[cur],
                                     ctx->d_sv_gbuf[cur], width, height, sparams, ctx->d_sv_show,
                                     ctx->d_sv_showvar, feedback ? ctx->d_sv_fb : nullptr,
-                                    demod ? nullptr : ctx->d_rgba, ctx->stream);
+                                    demod ? nullptr : store, ctx->stream);
     }
     if (rc == RVCP_OK && demod)
         rc = impl_remodulate_async(ctx, ctx->d_sv_show, ctx->d_sv_gbuf[cur], width, height,
-                                   ctx->d_sv_cur, ctx->d_rgba, ctx->stream);
+                                   ctx->d_sv_cur, store, ctx->stream);
+    const float *d_final = demod ? ctx->d_sv_cur : ctx->d_sv_show;     // the displayed linear frame
+    bool resolve_enqueued = false;
+    if (rc == RVCP_OK && taa) {
+        rc = taa_chain_resolve(ctx, ctx->taa_sv, taa_resume, base_push, &base_view, d_final,
+                               ctx->d_sv_gbuf[cur], width, height);
+        resolve_enqueued = rc == RVCP_OK;
+    }
     if (rc != RVCP_OK) {
         const std::string why = ctx->err;
         (void)rvcp_wait(ctx, nullptr);          // the render is enqueued: leave nothing pending
@@ -2397,10 +2712,13 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
     if ((rc = rvcp_wait(ctx, stats)) != RVCP_OK) return rc;
     if ((rc = impl_svgf_wait(ctx, accumulate_ms, filter_ms)) != RVCP_OK) return rc;
     if (demod && (rc = impl_albedo_wait(ctx, nullptr, nullptr)) != RVCP_OK) return rc;
+    if (resolve_enqueued) {
+        if ((rc = impl_taa_wait(ctx, nullptr)) != RVCP_OK) return rc;
+        d_final = ctx->taa_sv.d_res[ctx->taa_sv.slot ^ 1u];
+    }
     HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, npx * 4, hipMemcpyDeviceToHost));
     if (out_linear_rgb)
-        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, demod ? ctx->d_sv_cur : ctx->d_sv_show, npx * 12,
-                               hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, d_final, npx * 12, hipMemcpyDeviceToHost));
     if (out_variance)
         HIP_TRY(ctx, hipMemcpy(out_variance, ctx->d_sv_showvar, npx * 4, hipMemcpyDeviceToHost));
     if (out_history_len)
@@ -2413,6 +2731,7 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
     ctx->sv_camera = push->camera;
     ctx->sv_view = view_now;
     ctx->sv_valid = true;
+    if (taa) taa_chain_commit(ctx->taa_sv, base_push, &base_view, width, height);
     return RVCP_OK;
 }
 
@@ -3102,6 +3421,56 @@ int rvcp_set_demodulation(rvcp_ctx_t *ctx, int on)
 int rvcp_get_demodulation(rvcp_ctx_t *ctx, int *on)
 {
     return barrier(ctx, [&] { return impl_get_demodulation(ctx, on); });
+}
+
+int rvcp_taa_jitter(uint32_t frame_index, float out_jitter[2])
+{
+    return barrier(nullptr, [&] { return impl_taa_jitter(frame_index, out_jitter); });
+}
+
+int rvcp_taa_jitter_push(const rvcp_push_constant_t *base, uint32_t width, uint32_t height,
+                         const float jitter[2], rvcp_push_constant_t *out)
+{
+    return barrier(nullptr, [&] { return impl_taa_jitter_push(base, width, height, jitter, out); });
+}
+
+int rvcp_taa_params_default(rvcp_taa_params_t *params)
+{
+    return barrier(nullptr, [&] { return impl_taa_params_default(params); });
+}
+
+int rvcp_taa_resolve_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *cur_view,
+                           const rvcp_temporal_view_t *prev_view, const void *d_cur_linear,
+                           const void *d_cur_gbuffer, const void *d_prev_resolved,
+                           const void *d_prev_len, uint32_t width, uint32_t height,
+                           const rvcp_taa_params_t *params, void *d_out_resolved,
+                           void *d_out_len, void *d_rgba8_out, void *stream)
+{
+    return barrier(ctx, [&] {
+        return impl_taa_resolve_async(ctx, cur_view, prev_view, d_cur_linear, d_cur_gbuffer,
+                                      d_prev_resolved, d_prev_len, width, height, params,
+                                      d_out_resolved, d_out_len, d_rgba8_out, stream);
+    });
+}
+
+int rvcp_taa_wait(rvcp_ctx_t *ctx, float *taa_ms)
+{
+    return barrier(ctx, [&] { return impl_taa_wait(ctx, taa_ms); });
+}
+
+int rvcp_set_taa(rvcp_ctx_t *ctx, int on)
+{
+    return barrier(ctx, [&] { return impl_set_taa(ctx, on); });
+}
+
+int rvcp_get_taa(rvcp_ctx_t *ctx, int *on)
+{
+    return barrier(ctx, [&] { return impl_get_taa(ctx, on); });
+}
+
+int rvcp_taa_reset(rvcp_ctx_t *ctx)
+{
+    return barrier(ctx, [&] { return impl_taa_reset(ctx); });
 }
 
 }  // extern "C"

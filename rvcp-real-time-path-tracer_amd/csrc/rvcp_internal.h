@@ -370,6 +370,15 @@ int rvcp_launch_demodulate(const float *in, const void *gbuffer, const void *alb
 int rvcp_launch_remodulate(const float *in, const void *gbuffer, const void *albedo,
                            uint32_t n_materials, const float *gamma_t, float *out_lin,
                            uint32_t *out_rgba, uint32_t n, void *stream);
+// The TAA resolve (rvcp_taa.hip): mode 0 no history (prev_* unused), 1 the
+// identity mapping, 2 reprojection from *cur_view into *prev_view; out_rgba may be null
+int rvcp_launch_taa_resolve(const float *cur_c, const void *cur_g, const float *prev_c,
+                            const uint32_t *prev_len, float *out_c, uint32_t *out_len,
+                            uint32_t *out_rgba, const float *gamma_t, uint32_t width,
+                            uint32_t height, uint32_t mode,
+                            const struct rvcp_temporal_view *cur_view,
+                            const struct rvcp_temporal_view *prev_view,
+                            const struct rvcp_taa_params *params, void *stream);
 int rvcp_launch_assemble(const uint32_t *gathered, uint32_t slot_rows, uint32_t width,
                          uint32_t height, uint32_t shard_count, uint32_t *frame, void *stream);
 int rvcp_launch_fill(uint32_t *out_rgba, float *out_lin, uint32_t n_pixels, uint32_t rgba,

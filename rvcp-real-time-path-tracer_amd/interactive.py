@@ -157,7 +157,8 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
                  time_seed: Optional[Callable[[int], float]] = None,
                  dump_dir: Optional[str] = None, dump_format: str = "ppm",
                  on_fps: Optional[Callable[[int], None]] = None, denoise=None,
-                 temporal=None, svgf=None, demodulate: Optional[bool] = None) -> dict:
+                 temporal=None, svgf=None, demodulate: Optional[bool] = None,
+                 taa: Optional[bool] = None) -> dict:
     """``main_loop`` (ray_tracer.rs:22-100) without a window.
 
     Per frame: apply this frame's scripted events, count FPS (printed once a second as
@@ -176,9 +177,14 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
     ``demodulate``: True / False sets ``tracer.demodulation`` before the loop, so that the
     ``denoise`` / ``temporal`` / ``svgf`` chains filter irradiance (colour / albedo of the primary
     hit); None (default) leaves the tracer's switch as it is.
+    ``taa``: True / False sets ``tracer.taa`` before the loop, so that the ``temporal`` / ``svgf``
+    chains render through a jittered camera and return the anti-aliased resolve (DESIGN.md
+    §4.13); None (default) leaves the tracer's switch as it is.
     Returns per-frame render times and the final camera."""
     if demodulate is not None:
         tracer.demodulation = bool(demodulate)
+    if taa is not None:
+        tracer.taa = bool(taa)
     info = RuntimeInfo(window_size=(width, height))
     by_frame: Dict[int, List[Event]] = {}
     for ev in events:

@@ -426,6 +426,52 @@ class RayTracer:
                                                ctypes.cast(ctypes.byref(r), ctypes.c_void_p)))
         return float(d.value), float(r.value)
 
+    # temporal anti-aliasing
+    @property
+    def taa(self) -> bool:
+        """The context's TAA switch (rvcp_get_taa / rvcp_set_taa): while True, render_temporal and
+        render_svgf render through a camera jittered by abi.taa_jitter(frame counter) and return
+        the resolved frame (taa_resolve_async of their final linear colour under the unjittered
+        cameras).  Changing it drops both chains' histories."""
+        on = ctypes.c_int(0)
+        self._check(self._lib.rvcp_get_taa(self._ctx, ctypes.cast(ctypes.byref(on), ctypes.c_void_p)))
+        return bool(on.value)
+
+    @taa.setter
+    def taa(self, on: bool):
+        self._check(self._lib.rvcp_set_taa(self._ctx, 1 if on else 0))
+
+    def taa_reset(self):
+        """rvcp_taa_reset: drop the TAA states render_temporal and render_svgf keep; their jitter
+        sequences restart."""
+        self._check(self._lib.rvcp_taa_reset(self._ctx))
+
+    def taa_resolve_async(self, cur_view, prev_view, d_cur_linear: int, d_cur_gbuffer: int,
+                          d_prev_resolved: int, d_prev_len: int, width, height,
+                          d_out_resolved: int, d_out_len: int, d_rgba: int = 0, params=None,
+                          stream: int = 0):
+        """rvcp_taa_resolve_async: enqueue one resolve step on frames in device memory.  cur_view /
+        prev_view: the abi.temporal_view(...) records of the two frames' UNJITTERED cameras, or
+        both None when the camera is at rest; d_prev_* both 0: no history.  Wait with
+        taa_wait()."""
+        if cur_view is not None:
+            cur_view = np.ascontiguousarray(cur_view, dtype=abi.TEMPORAL_VIEW_DTYPE)
+        if prev_view is not None:
+            prev_view = np.ascontiguousarray(prev_view, dtype=abi.TEMPORAL_VIEW_DTYPE)
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=abi.TAA_PARAMS_DTYPE)
+        P = lambda a: ctypes.c_void_p(a) if a else None   # noqa: E731
+        self._check(self._lib.rvcp_taa_resolve_async(
+            self._ctx, abi.ptr(cur_view), abi.ptr(prev_view), P(d_cur_linear), P(d_cur_gbuffer),
+            P(d_prev_resolved), P(d_prev_len), width, height, abi.ptr(params), P(d_out_resolved),
+            P(d_out_len), P(d_rgba), P(stream)))
+
+    def taa_wait(self) -> float:
+        """rvcp_taa_wait: block until the last taa_resolve_async is done; its device time, ms."""
+        ms = ctypes.c_float(0.0)
+        self._check(self._lib.rvcp_taa_wait(self._ctx, ctypes.cast(ctypes.byref(ms), ctypes.c_void_p)))
+        return float(ms.value)
+
     def wait(self):
         """rvcp_wait: block until the last async render is done; returns its stats."""
         stats = np.zeros((), dtype=abi.STATS_DTYPE)
