@@ -173,11 +173,16 @@ typedef struct rvcp_config {
      * shader (bit-exact, the parity path).  RVCP_ACCEL_BVH (opt-in, games101 only) builds a
      * bounding-volume hierarchy at upload and tests only the triangles whose (slightly
      * enlarged) boxes the ray reaches, with the same exact triangle test and nearest-hit
-     * rule; frames match the brute-force ones except where a ray runs almost parallel to a
-     * triangle's plane.  With specialize = AUTO, a mesh whose leading faces
-     * (at most 64) are all large -- a room around many small triangles, as C5 -- keeps those
-     * faces out of the BVH and tests them first with the scene-specialised scan (the BVH
-     * hybrid; stats report RVCP_VARIANT_SPECIALIZED). */
+     * rule; frames match the brute-force ones except where the exact test itself reports a
+     * hit away from its triangle -- a ray almost parallel to the triangle's plane, or a sliver
+     * or collinear triangle -- outside every box of that triangle.  The
+     * box test of primary rays carries a relative slack for far cameras; tested: G-buffer
+     * frames equal to the brute-force ones from 10, 100 and 1000 scene diagonals away, on
+     * meshes and cameras with t_far x t_coef < 2^24 (renders: from cameras near the scene).  With
+     * specialize = AUTO, a mesh whose leading faces (at most 64) are all large -- a room
+     * around many small triangles, as C5 -- keeps those faces out of the BVH and tests them
+     * first with the scene-specialised scan (the BVH hybrid; stats report
+     * RVCP_VARIANT_SPECIALIZED). */
     int32_t accel;
     /* GPUs one context drives (0 or 1 = one).  With n_gpus = N > 1, rvcp_create opens devices
      * device, device+1, ... (mod the device count), rvcp_upload_scene uploads to all of them,

@@ -11,7 +11,15 @@
 // largest coordinate magnitude.  An exact triangle test (tri_accept) that accepts a hit on a
 // well-conditioned ray (not nearly parallel to the triangle plane) puts the hit point within a
 // few ulps of the triangle, far inside that margin, so culling never drops a hit the
-// brute-force scan would find (DESIGN.md §4.6 for the nearly-parallel exception).
+// brute-force scan would find.  Two limits (tests/bvh_adversarial.py):
+//  * the exception: where the exact test is ill-conditioned -- a ray nearly parallel to the
+//    triangle's plane, or a sliver / collinear triangle, for which every ray is -- it can accept
+//    a "hit" thousands of pads outside the triangle's box, which the traversal never visits
+//    (10 of 24 108 adversarial rays in the CPU model, all on such faces of the fuzz scenes);
+//  * the margin is absolute (relative to the scene), the rounding of t relative to t: from an
+//    origin some hundred scene diagonals away a few ulp of t exceed the margin.  That case is
+//    covered by the traversal, whose slab comparison is conservative by kBvhSlabSlack
+//    (rvcp_internal.h), not here.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -273,8 +281,9 @@ uint32_t bvh_big_prefix(const float (*pos)[3][3], uint32_t n, uint32_t cap)
 // Build over `n` faces given their three vertex positions.  Outputs the node array, the
 // leaf-ordered original face ids and the root reference; returns the tree depth.
 int bvh_build(const float (*pos)[3][3], uint32_t n, std::vector<BvhNode> &nodes,
-              std::vector<uint32_t> &order, int32_t &root)
+              std::vector<uint32_t> &order, int32_t &root, float *pad_abs)
 {
+    if (pad_abs) *pad_abs = 0.0f;
     Builder B;
     B.prims.resize(n);
     Box scene;
@@ -305,6 +314,7 @@ int bvh_build(const float (*pos)[3][3], uint32_t n, std::vector<BvhNode> &nodes,
     const float dx = scene.hi[0] - scene.lo[0], dy = scene.hi[1] - scene.lo[1],
                 dz = scene.hi[2] - scene.lo[2];
     B.pad_abs = 1e-5f * std::sqrt(dx * dx + dy * dy + dz * dz);
+    if (pad_abs) *pad_abs = B.pad_abs;
     const uint32_t np = (uint32_t)B.prims.size();     // n plus the split-clip pieces
     int median_levels = 1;
     for (uint64_t leaves = ((uint64_t)np + kBvhLeafMax - 1) / kBvhLeafMax; leaves > 1; leaves = (leaves + 1) / 2)
@@ -387,7 +397,7 @@ struct Collapser {
                 Q.hi[k][i] = used ? c[i].box[3 + k] : 3e38f;
             }
             Q.ref[i] = used ? refs[i] : ~0;
-            Q.pad[i] = 0;
+            Q.pad[i] = used ? 1 : 0;
         }
         need = push + sub;
         return self;
@@ -420,6 +430,13 @@ int bvh4_collapse(const std::vector<BvhNode> &nodes, int32_t root, std::vector<B
 // origin + q_hi * scale >= hi in exact arithmetic: every quantised box contains its float box,
 // which already carries the build's enlargement (far above the few-ulp rounding of the
 // kernel's decode), so the traversal culls nothing the float boxes keep.
+// A child slot is unused iff Bvh4Node::pad[c] == 0.  Its reference, ~0, does not say so: ~0 is
+// also the leaf at slot 0 with one triangle, the leftmost leaf of many trees, and a quantiser
+// that went by the reference took that leaf for an unused slot and inverted its box, so that
+// no ray ever reached its triangle (tests/test_bvh_adversarial_cpu.py).  An unused slot gets the
+// bytes 255 / 0 on every axis, which no used child has (qhi >= qlo); that inverted box keeps
+// near rays out, not far ones (Bvh4QNode, rvcp_internal.h), so the primary-ray traversal goes
+// by the bytes, and a ray that does enter finds ~0: the triangle at slot 0, tested again.
 void bvh4_quantize(const std::vector<Bvh4Node> &in, std::vector<Bvh4QNode> &out)
 {
     out.resize(in.size());
@@ -430,7 +447,7 @@ void bvh4_quantize(const std::vector<Bvh4Node> &in, std::vector<Bvh4QNode> &out)
             float lo = 0.0f, hi = 0.0f;
             bool any = false;
             for (int c = 0; c < 4; c++) {
-                if (N.ref[c] == ~0) continue;
+                if (!N.pad[c]) continue;
                 lo = any ? std::min(lo, N.lo[k][c]) : N.lo[k][c];
                 hi = any ? std::max(hi, N.hi[k][c]) : N.hi[k][c];
                 any = true;
@@ -443,8 +460,8 @@ void bvh4_quantize(const std::vector<Bvh4Node> &in, std::vector<Bvh4QNode> &out)
             Q.scale[k] = (float)sc;
             uint32_t wl = 0, wh = 0;
             for (int c = 0; c < 4; c++) {
-                uint32_t ql = 255, qh = 0;                     // unused: inverted, never entered
-                if (N.ref[c] != ~0) {
+                uint32_t ql = 255, qh = 0;                     // unused: inverted (ql > qh marks it)
+                if (N.pad[c]) {
                     ql = (uint32_t)std::floor(((double)N.lo[k][c] - (double)lo) / sc);
                     qh = (uint32_t)std::ceil(((double)N.hi[k][c] - (double)lo) / sc);
                     if (qh > 255) qh = 255;                    // cannot happen: ext / sc <= 255

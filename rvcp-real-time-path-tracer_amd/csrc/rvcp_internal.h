@@ -177,24 +177,46 @@ static_assert(sizeof(BvhNode) == 64, "BvhNode is 64 B");
 constexpr int kBvhLeafMax = RVCP_BVH_LEAF_MAX;
 constexpr uint32_t kBvhPadId = 0xFFFFFFFFu;   // padding slot of the leaf order (even leaf starts)
 constexpr int kBvhStack = 32;           // traversal stack entries per lane
+// Relative slack of the slab comparison in the traversal of primary rays
+// (bvh_nearest<.., PRIMARY>): a child box is entered iff tn <= tf + kBvhSlabSlack * |tf| (tf
+// already clamped to the nearest hit so far).  Shadow and path rays start on a surface, inside
+// the scene, and need none.  The slab times carry the rounding of their decode, (origin - o) *
+// inv and scale * inv with a 1-ulp reciprocal, and the nearest hit's t its own few ulp; relative
+// to t that is a few 2^-24, which from an origin some hundred scene diagonals away exceeds the
+// build's box enlargement (1e-5 of the diagonal) -- the traversal then lost hits the scan
+// keeps.  Measured on the CPU model
+// (tools/bvh4_check.cpp, tests/test_bvh_adversarial_cpu.py: 24 108 rays from up to 1000 diagonals
+// over 41 adversarial meshes): a slack of 2^-23 is the smallest power of two that loses none of
+// them (2^-24 still loses some); the device's v_rcp_f32 adds up to 2^-23 to the model's IEEE
+// reciprocal, and 2^-21 is twice that sum.  Only ever conservative: it enters more boxes.
+constexpr float kBvhSlabSlack = 0x1p-21f;
 
 // The traversed tree: up to 4 children per node, boxes stored per axis so one node is seven
 // 16-byte loads; a step tests the four boxes, pushes the hit children but the nearest (farthest
 // first) and descends into the nearest.  Unused child slots hold an unreachable box (a point
 // at 3e38) and the leaf reference ~0 (triangle 0 again: a repeated test never changes the hit).
+// ~0 is also a real leaf (slot 0, one triangle), so it is pad[child] that says which slots are
+// used.
 struct alignas(16) Bvh4Node {
     float lo[3][4];     // lo[axis][child]
     float hi[3][4];
     int32_t ref[4];
-    int32_t pad[4];
+    int32_t pad[4];     // 1: the child slot is used, 0: unused
 };
 static_assert(sizeof(Bvh4Node) == 128, "Bvh4Node is 128 B");
 
 // The same node with its child boxes quantised to bytes (bvh4_quantize): per axis the children's
 // bounds are origin + q * scale with scale a power of two, lo rounded down and hi up (so every
 // box contains its Bvh4Node box); byte c of qlo[axis] / qhi[axis] is child c.  Unused children
-// are inverted (qlo = 255, qhi = 0), which the ordered slab test never enters.  64 B: four
-// 16-B loads per traversal step instead of seven.
+// are inverted on every axis (qlo = 255 > qhi = 0, which no used child has: its qhi >= qlo) and
+// keep the reference ~0, so that whatever enters one only tests the triangle at slot 0 again,
+// inside the leaf buffer.  The inversion alone does not keep a ray out: it is 255 * scale * inv
+// in slab time, which the rounding of (origin - o) * inv swallows once the ray's origin is 2^24
+// node extents away on every axis (fma(255, a, b) == b), and an entered unused slot is a push
+// that bvh4_collapse's stack bound did not count.  The traversal of primary rays therefore
+// keys a slot with qlo > qhi +inf (bvh_nearest<.., PRIMARY>, rvcp_kernels.hip); what is left
+// for the other rays is described there.  64 B: four 16-B loads per traversal step instead of
+// seven.
 struct alignas(16) Bvh4QNode {
     float origin[3];
     float scale[3];
@@ -275,8 +297,10 @@ struct FrameArgs {
 
 #ifndef __HIPCC_RTC__
 // rvcp_bvh.cpp: build the BVH over n faces (three vertex positions each); returns the depth.
+// pad_abs, if given, receives the absolute part of the build's box enlargement (the checker's
+// classifier, tools/bvh4_check.cpp, judges a lost hit against the pad the build really used).
 int bvh_build(const float (*pos)[3][3], uint32_t n, std::vector<BvhNode> &nodes,
-              std::vector<uint32_t> &order, int32_t &root);
+              std::vector<uint32_t> &order, int32_t &root, float *pad_abs = nullptr);
 // Collapse the binary tree into the 4-wide one, keeping the traversal stack within
 // kBvhStack entries; returns that stack bound.
 int bvh4_collapse(const std::vector<BvhNode> &nodes, int32_t root, std::vector<Bvh4Node> &out,

@@ -457,10 +457,29 @@ typedef __attribute__((address_space(3))) int32_t lds_i32;
 // rule keeps a later face at equal t, so a box entered exactly at bt must still be visited.
 // Each child bound is decoded straight into slab time, t = q * (scale * inv) + (origin - o) *
 // inv, with the near and far bytes chosen by the sign of the ray's inverse direction (the
-// ordered slab test: an inverted unused child is never entered); the roundings of that form
+// ordered slab test).  An unused child's box is inverted (bytes 255 / 0), but only by 255 *
+// scale * inv: once the origin is 2^24 node extents away on every axis -- 335 scene diagonals
+// for a node two pads wide; 40 with the slack below -- fma(255, a, b) == b and the slot is
+// entered.  Its reference is ~0, so what is then tested is the triangle at slot 0 once more,
+// which changes no hit; but its push is one that the stack bound of bvh4_collapse does not
+// count.  Primary rays can start that far away, and their stack is the private array, so for
+// them (PRIMARY) a child whose x bytes are inverted is keyed +inf and never entered.  Shadow
+// and path rays keep the bare inversion, as before: the key's two instructions per child
+// measured 0.8 % of the C5 frame in bvh_pool's steps (41.83 against 41.49 ms).
+// What that leaves: such a ray starts at a hit point, normally on a face of the scene, but the
+// exact test's "hits" on sliver faces along a primary ray from 1000 diagonals land up to 300
+// diagonals outside the scene box on every axis (tests/bvh_adversarial.py's rays, CPU model),
+// the same order as the 335 above.  A shadow or path ray from such a point can enter unused
+// slots; every one is an extra entry on its LDS stack column, and a tree whose counted bound
+// plus those entries passes kBvhStack overruns the column.  The roundings of that form
 // are relative errors of a few ulp of t, far below the build's box enlargement, and a NaN from
-// it only widens a slab, so nothing a float box keeps is culled.  (The 128-B float nodes the
-// quantised ones come from measured 180 vs 151 ms per C5 frame)
+// it only widens a slab, so nothing a float box keeps is culled -- for a ray that starts in or
+// near the scene, as every shadow and path ray does (it starts on a surface).  A primary ray
+// may start many scene diagonals away, where a few ulp of t exceed the enlargement (1e-5 of
+// the diagonal); for those (PRIMARY: the pre-pass and the G-buffer) the comparison itself is
+// conservative, a child is entered iff tn <= tf + kBvhSlabSlack |tf| (rvcp_internal.h; one fma
+// per child, kept out of bvh_pool's steps, where it measured 1 % of the C5 frame).  (The 128-B
+// float nodes the quantised ones come from measured 180 vs 151 ms per C5 frame)
 // LDS = true: the stack is the caller's LDS column (stk[i * kBlock]; the lanes of a wave hit
 // distinct banks whatever their depths); LDS = false: a private array (the pre-pass kernel,
 // whose 1024-thread blocks would need 128 KiB of LDS).
@@ -476,7 +495,7 @@ __device__ __forceinline__ void bvh4_cas(float &ka, int32_t &ca, float &kb, int3
 
 __device__ __forceinline__ float ubyte_f(uint32_t w, int c) { return (float)((w >> (8 * c)) & 0xFFu); }
 
-template <bool LDS>
+template <bool LDS, bool PRIMARY = false>
 __device__ __noinline__ void bvh_nearest(const Bvh4Node *__restrict__ nodes,
                                          const TriRecord *__restrict__ btri, int32_t root,
                                          lds_i32 *stk, f3 o, f3 d, float tmin, float &bt,
@@ -530,7 +549,9 @@ __device__ __noinline__ void bvh_nearest(const Bvh4Node *__restrict__ nodes,
                     const float tf = __builtin_fminf(
                         __builtin_fminf(__builtin_fmaf(ubyte_f(fx, c), ax, bx), __builtin_fmaf(ubyte_f(fy, c), ay, by)),
                         __builtin_fminf(__builtin_fmaf(ubyte_f(fz, c), az, bz), bt));
-                    kk[c] = tn <= tf ? tn : __builtin_inff();
+                    const float tfs = PRIMARY ? __builtin_fmaf(__builtin_fabsf(tf), kBvhSlabSlack, tf) : tf;
+                    const bool slot = !PRIMARY || ubyte_f(lx, c) <= ubyte_f(hx, c);      // unused: 255 > 0
+                    kk[c] = (tn <= tfs) & slot ? tn : __builtin_inff();
                 }
                 float k0 = kk[0], k1 = kk[1], k2 = kk[2], k3 = kk[3];
                 int32_t c0 = r.x, c1 = r.y, c2 = r.z, c3 = r.w;
@@ -1654,7 +1675,7 @@ __device__ __forceinline__ void primary_body(
                     if (tri_accept(tri[i], o, d, tmin, bt, t)) { bt = t; best = (int)i; }
                 }
             }
-            bvh_nearest<false>(bvh_nodes, bvh_tris, A.bvh_root, nullptr, o, d, tmin, bt, best, A.bvh_n4, A.bvh_slots);
+            bvh_nearest<false, true>(bvh_nodes, bvh_tris, A.bvh_root, nullptr, o, d, tmin, bt, best, A.bvh_n4, A.bvh_slots);
         }
 #ifdef RVCP_SPEC_SCAN
         // the scene-specialised scan (§4.7) where every primary ray of the wave is in its range
@@ -1750,7 +1771,7 @@ __global__ __launch_bounds__(kPrimaryBlock) void games101_gbuffer_kernel(
                 float t;
                 if (tri_accept(tri[i], o, d, tmin, bt, t)) { bt = t; best = (int)i; }
             }
-            bvh_nearest<false>(bvh_nodes, bvh_tris, A.bvh_root, nullptr, o, d, tmin, bt, best, A.bvh_n4, A.bvh_slots);
+            bvh_nearest<false, true>(bvh_nodes, bvh_tris, A.bvh_root, nullptr, o, d, tmin, bt, best, A.bvh_n4, A.bvh_slots);
         } else {
 #pragma unroll 2
             for (uint32_t i = 0; i < A.n_faces; ++i) {
