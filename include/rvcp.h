@@ -335,6 +335,17 @@ typedef struct rvcp_taa_params {
     uint32_t _pad;          /* must be 0 */
 } rvcp_taa_params_t;
 
+/* Parameters of rvcp_taa_upsample_async (the rule's definition: DESIGN.md §4.14).  No
+ * counterpart in the reference. */
+typedef struct rvcp_taau_params {
+    float max_weight;       /* cap of the per-pixel sample weight, finite, > 0 */
+    float init_weight;      /* the weight of a pixel that starts a history, finite, > 0 */
+    uint32_t clamp;         /* 1: the history is clamped into the colour box of the 3 x 3 traced
+                               pixels (not where the traced pixel lies on its frame's border);
+                               0: it is not */
+    uint32_t _pad;          /* must be 0 */
+} rvcp_taau_params_t;
+
 /* Layout checks: sizes/offsets the reference's Rust structs and std140/std430 blocks imply. */
 #ifdef __cplusplus
 #define RVCP_STATIC_ASSERT(c, m) static_assert(c, m)
@@ -382,6 +393,10 @@ RVCP_STATIC_ASSERT(sizeof(rvcp_taa_params_t) == 16, "TAA params are 16 B");
 RVCP_STATIC_ASSERT(offsetof(rvcp_taa_params_t, max_history) == 4, "TaaParams.max_history @4");
 RVCP_STATIC_ASSERT(offsetof(rvcp_taa_params_t, clamp) == 8, "TaaParams.clamp @8");
 RVCP_STATIC_ASSERT(offsetof(rvcp_taa_params_t, _pad) == 12, "TaaParams._pad @12");
+RVCP_STATIC_ASSERT(sizeof(rvcp_taau_params_t) == 16, "TAA upsampling params are 16 B");
+RVCP_STATIC_ASSERT(offsetof(rvcp_taau_params_t, init_weight) == 4, "TaauParams.init_weight @4");
+RVCP_STATIC_ASSERT(offsetof(rvcp_taau_params_t, clamp) == 8, "TaauParams.clamp @8");
+RVCP_STATIC_ASSERT(offsetof(rvcp_taau_params_t, _pad) == 12, "TaauParams._pad @12");
 
 typedef struct rvcp_ctx rvcp_ctx_t;
 
@@ -958,6 +973,71 @@ int rvcp_get_taa(rvcp_ctx_t *ctx, int *on);
 /* Drop the TAA states rvcp_render_temporal and rvcp_render_svgf keep on the context (their own
  * histories stay); both frame counters restart at 0.  No counterpart in the reference. */
 int rvcp_taa_reset(rvcp_ctx_t *ctx);
+
+/* ---------------------------------------------------------------------------------------
+ * Temporal upsampling: the frame is traced at W / s x H / s through the jittered camera and a
+ * step accumulates the displayed colour and a sample weight on the W x H grid of the unjittered
+ * camera, every traced pixel dropped where its jittered centre falls (opt-in; no other entry
+ * point changes).  No counterpart in the reference.
+ * ------------------------------------------------------------------------------------- */
+
+/* The default parameters: max_weight 8, init_weight 0.1, clamp 1.  Needs no device.
+ * No counterpart in the reference. */
+int rvcp_taau_params_default(rvcp_taau_params_t *params);
+
+/* Enqueue one upsampling step on `stream` (NULL: the context's); stateless, every buffer is the
+ * caller's device memory.  The output is width x height = W x H, the traced frame w x h =
+ * W / scale x H / scale.  d_cur_linear (w*h*3 floats) is the frame rendered through the jittered
+ * low-res camera; jit_view that jittered camera for a w x h frame and cur_view the UNJITTERED
+ * camera for W x H (rvcp_temporal_view_from_push; both required: they place the samples).
+ * d_prev_resolved (W*H*3 floats) and d_prev_weight (W*H floats) are the previous call's outputs
+ * -- both NULL: no history.  prev_view is the unjittered W x H camera of the previous frame;
+ * NULL, or byte-equal to *cur_view: the camera is at rest and pixel p continues the history of
+ * pixel p.  Otherwise the history is reprojected through d_gbuffer_hi (W*H texels rendered
+ * through the UNJITTERED camera, of which only position and face are read); it is required in
+ * exactly that case and ignored in the others.  Written: d_out_resolved (W*H*3 floats, within
+ * [0, 1] when the history is), d_out_weight (W*H floats: init_weight where a history starts,
+ * never above max_weight) and, when d_rgba8_out is not NULL, pow(c, 0.6) of the result as RGBA8
+ * under the context's unorm_rule, from the same kernel.  All arithmetic is single correctly
+ * rounded f32 operations in a fixed order, so the result is reproducible bit
+ * for bit.  params = NULL: the defaults.  Needs no scene.  Ordering as rvcp_taa_resolve_async:
+ * behind a render pending on the context and behind the context's previous upsampling step.
+ * RVCP_E_INVALID: NULL / zero arguments, scale outside 2..4, a width or height that scale does
+ * not divide, W*H >= 2^31, an output that overlaps an input or another output, one of d_prev_*
+ * without the other, prev_view without a history, a moved camera without d_gbuffer_hi,
+ * max_weight or init_weight not finite or not > 0, clamp not 0 or 1, _pad != 0.
+ * No counterpart in the reference. */
+int rvcp_taa_upsample_async(rvcp_ctx_t *ctx, uint32_t scale,
+                            const rvcp_temporal_view_t *jit_view,
+                            const rvcp_temporal_view_t *cur_view,
+                            const rvcp_temporal_view_t *prev_view, const void *d_cur_linear,
+                            const void *d_gbuffer_hi, const void *d_prev_resolved,
+                            const void *d_prev_weight, uint32_t width, uint32_t height,
+                            const rvcp_taau_params_t *params, void *d_out_resolved,
+                            void *d_out_weight, void *d_rgba8_out, void *stream);
+
+/* Wait for the context's last rvcp_taa_upsample_async; *taau_ms (optional) gets its device time
+ * (HIP events on its stream).  RVCP_E_INVALID when no step was enqueued since the last call.
+ * No counterpart in the reference. */
+int rvcp_taau_wait(rvcp_ctx_t *ctx, float *taau_ms);
+
+/* The context's upsampling scale: 1 (off, the default), 2, 3 or 4.  While it is above 1 it
+ * replaces the TAA resolve, whatever rvcp_set_taa says: a W x H call of rvcp_render_temporal or
+ * rvcp_render_svgf (RVCP_E_INVALID when the scale does not divide W and H) runs its whole chain
+ * -- render, G-buffer, demodulation, accumulation, filter, remodulation -- at w x h = W / scale x
+ * H / scale through rvcp_taa_jitter_push(push, w, h, rvcp_taa_jitter(counter)), traces a W x H
+ * G-buffer through the unjittered `push` on the frames whose 64 camera bytes differ from the
+ * previous call's, and finishes with rvcp_taa_upsample_async at its defaults.  out_rgba8 and
+ * out_linear_rgb are the W x H result; EVERY OTHER optional output (history lengths, variance)
+ * keeps the traced size w x h.  Each of the two keeps an upsampling state of its own (resolved
+ * colour, weight, unjittered camera, frame counter), dropped wherever its TAA state would be,
+ * and on rvcp_taa_reset.  Changing the value drops both chains' histories; setting the value it
+ * has does nothing.  RVCP_E_INVALID: a scale outside 1..4, a frame pending.  With the scale at
+ * 1 every output is what it is without this section.  No counterpart in the reference. */
+int rvcp_set_taa_upsample(rvcp_ctx_t *ctx, uint32_t scale);
+
+/* *scale = the context's upsampling scale.  No counterpart in the reference. */
+int rvcp_get_taa_upsample(rvcp_ctx_t *ctx, uint32_t *scale);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,10 @@ TAA_PARAMS_DTYPE = np.dtype([("alpha_min", "<f4"), ("max_history", "<u4"), ("cla
                              ("_pad", "<u4")])
 assert TAA_PARAMS_DTYPE.itemsize == 16
 TAA_JITTER_PERIOD = 16
+# rvcp_taau_params_t (temporal upsampling)
+TAAU_PARAMS_DTYPE = np.dtype([("max_weight", "<f4"), ("init_weight", "<f4"), ("clamp", "<u4"),
+                              ("_pad", "<u4")])
+assert TAAU_PARAMS_DTYPE.itemsize == 16
 # rvcp_stats_t.kernel_variant -> the dominant kernel's name as rocprofv3 reports it
 KERNEL_NAMES = {1: "games101_kernel", 2: "games101_dual_kernel", 3: "games101_path_kernel<5>",
                 4: "games101_tiled_kernel", 5: "games101_tiled_single_kernel",
@@ -98,7 +102,9 @@ EXPORTED = ["rvcp_version", "rvcp_config_default", "rvcp_config_default_for", "r
             "rvcp_set_demodulation", "rvcp_get_demodulation",
             "rvcp_taa_jitter", "rvcp_taa_jitter_push", "rvcp_taa_params_default",
             "rvcp_taa_resolve_async", "rvcp_taa_wait", "rvcp_set_taa", "rvcp_get_taa",
-            "rvcp_taa_reset"]
+            "rvcp_taa_reset",
+            "rvcp_taau_params_default", "rvcp_taa_upsample_async", "rvcp_taau_wait",
+            "rvcp_set_taa_upsample", "rvcp_get_taa_upsample"]
 
 
 # Integrator mode 2 (ray_tracer.comp ray_trace): its own #defines (ray_tracer.comp:5-13).
@@ -166,6 +172,18 @@ def make_taa_params(**overrides) -> np.ndarray:
     rc = load().rvcp_taa_params_default(ptr(p))
     if rc != RVCP_OK:
         raise RvcpError(rc, "rvcp_taa_params_default failed")
+    for k, v in overrides.items():
+        p[k] = v
+    return p
+
+
+def make_taau_params(**overrides) -> np.ndarray:
+    """rvcp_taau_params_t with the library's defaults (rvcp_taau_params_default), overridden by
+    the keyword arguments."""
+    p = np.zeros((), dtype=TAAU_PARAMS_DTYPE)
+    rc = load().rvcp_taau_params_default(ptr(p))
+    if rc != RVCP_OK:
+        raise RvcpError(rc, "rvcp_taau_params_default failed")
     for k, v in overrides.items():
         p[k] = v
     return p
@@ -305,6 +323,11 @@ def load():
     L.rvcp_set_taa.argtypes = [P, ctypes.c_int]
     L.rvcp_get_taa.argtypes = [P, P]
     L.rvcp_taa_reset.argtypes = [P]
+    L.rvcp_taau_params_default.argtypes = [P]
+    L.rvcp_taa_upsample_async.argtypes = [P, u32, P, P, P, P, P, P, P, u32, u32, P, P, P, P, P]
+    L.rvcp_taau_wait.argtypes = [P, P]
+    L.rvcp_set_taa_upsample.argtypes = [P, u32]
+    L.rvcp_get_taa_upsample.argtypes = [P, P]
     for name in ("rvcp_config_default", "rvcp_config_default_for", "rvcp_create", "rvcp_destroy", "rvcp_upload_scene",
                  "rvcp_render", "rvcp_render_shard_async", "rvcp_sync_stats",
                  "rvcp_assemble_frame_async", "rvcp_upload_scene_file", "rvcp_mandelbrot",
@@ -322,7 +345,8 @@ def load():
                  "rvcp_albedo_wait", "rvcp_set_demodulation", "rvcp_get_demodulation",
                  "rvcp_taa_jitter", "rvcp_taa_jitter_push", "rvcp_taa_params_default",
                  "rvcp_taa_resolve_async", "rvcp_taa_wait", "rvcp_set_taa", "rvcp_get_taa",
-                 "rvcp_taa_reset"):
+                 "rvcp_taa_reset", "rvcp_taau_params_default", "rvcp_taa_upsample_async",
+                 "rvcp_taau_wait", "rvcp_set_taa_upsample", "rvcp_get_taa_upsample"):
         getattr(L, name).restype = ctypes.c_int
     if L.rvcp_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI revision {L.rvcp_abi_version()}, this binding "

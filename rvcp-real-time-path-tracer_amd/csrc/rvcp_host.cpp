@@ -205,6 +205,25 @@ struct rvcp_ctx {
         uint32_t counter = 0;               // the next frame's index into the jitter sequence
     } taa_tp, taa_sv;                       // of rvcp_render_temporal / rvcp_render_svgf
 
+    // temporal upsampling (rvcp_taa_upsample_async): an event pair for the step,
+    // the scale of rvcp_set_taa_upsample (1: off) and one state per stateful chain: the resolved
+    // colour and its weights at the OUTPUT size ping-pong between slots `slot` (the previous
+    // frame) and slot ^ 1; d_gbuf is the output-size G-buffer of a frame whose camera moved
+    hipEvent_t evtu0 = nullptr, evtu1 = nullptr;
+    bool taau_recorded = false, taau_pending = false;
+    uint32_t taau_scale = 1;
+    struct TaauState {
+        float *d_res[2] = {nullptr, nullptr};
+        float *d_wt[2] = {nullptr, nullptr};
+        void *d_gbuf = nullptr;
+        size_t cap = 0;
+        uint32_t slot = 0, width = 0, height = 0;
+        bool valid = false;                 // slot `slot` holds a resolved frame of width x height
+        rvcp_camera_t camera = {};          // ... under this unjittered camera
+        rvcp_temporal_view_t view = {};     // ... whose projection (at width x height) this is
+        uint32_t counter = 0;               // the next frame's index into the jitter sequence
+    } taau_tp, taau_sv;                     // of rvcp_render_temporal / rvcp_render_svgf
+
     // debug build: per-wave timeline of the path kernel appended per render
     unsigned long long *d_timeline = nullptr;
     size_t cap_timeline = 0, last_timeline_waves = 0;
@@ -661,6 +680,7 @@ static int impl_destroy(rvcp_ctx_t *ctx)
     if (ctx->demod_recorded) (void)hipEventSynchronize(ctx->evad1);
     if (ctx->remod_recorded) (void)hipEventSynchronize(ctx->evar1);
     if (ctx->taa_recorded) (void)hipEventSynchronize(ctx->evta1);
+    if (ctx->taau_recorded) (void)hipEventSynchronize(ctx->evtu1);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm && ctx->comm_owned) (void)rccl_api().comm_destroy(ctx->comm);
     ctx->comm = nullptr;
@@ -708,6 +728,15 @@ static int impl_destroy(rvcp_ctx_t *ctx)
             (void)hipFree(st->d_res[i]);
             (void)hipFree(st->d_len[i]);
         }
+    for (rvcp_ctx::TaauState *st : {&ctx->taau_tp, &ctx->taau_sv}) {
+        for (int i = 0; i < 2; ++i) {
+            (void)hipFree(st->d_res[i]);
+            (void)hipFree(st->d_wt[i]);
+        }
+        (void)hipFree(st->d_gbuf);
+    }
+    if (ctx->evtu0) (void)hipEventDestroy(ctx->evtu0);
+    if (ctx->evtu1) (void)hipEventDestroy(ctx->evtu1);
     if (ctx->evta0) (void)hipEventDestroy(ctx->evta0);
     if (ctx->evta1) (void)hipEventDestroy(ctx->evta1);
     for (hipEvent_t e : {ctx->evsa0, ctx->evsa1, ctx->evsf0, ctx->evsf1})
@@ -2016,6 +2045,8 @@ static int impl_taa_reset(rvcp_ctx_t *ctx)
     if (!ctx) return RVCP_E_INVALID;
     ctx->taa_tp.valid = false;
     ctx->taa_sv.valid = false;
+    ctx->taau_tp.valid = false;
+    ctx->taau_sv.valid = false;
     return RVCP_OK;
 }
 
@@ -2080,6 +2111,204 @@ static void taa_chain_commit(rvcp_ctx::TaaState &st, const rvcp_push_constant_t 
     st.valid = true;
 }
 
+// ---- temporal upsampling: the step and the switch -------------------------
+
+static int impl_taau_params_default(rvcp_taau_params_t *params)
+{
+    if (!params) return RVCP_E_INVALID;
+    params->max_weight = 8.0f;
+    params->init_weight = 0.1f;
+    params->clamp = 1;
+    params->_pad = 0;
+    return RVCP_OK;
+}
+
+static int impl_taa_upsample_async(rvcp_ctx_t *ctx, uint32_t scale,
+                                   const rvcp_temporal_view_t *jit_view,
+                                   const rvcp_temporal_view_t *cur_view,
+                                   const rvcp_temporal_view_t *prev_view, const void *d_cur,
+                                   const void *d_g_hi, const void *d_prev, const void *d_prev_wt,
+                                   uint32_t width, uint32_t height,
+                                   const rvcp_taau_params_t *params, void *d_out, void *d_out_wt,
+                                   void *d_rgba8_out, void *stream)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!jit_view || !cur_view || !d_cur || !d_out || !d_out_wt || width == 0 || height == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid TAA upsampling arguments");
+    if (scale < 2 || scale > 4)
+        return fail(ctx, RVCP_E_INVALID, "TAA upsampling scale must be in 2..4");
+    if (width % scale != 0 || height % scale != 0)
+        return fail(ctx, RVCP_E_INVALID, "TAA upsampling: the scale must divide width and height");
+    if ((uint64_t)width * height >= (1ull << 31))
+        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    if ((d_prev == nullptr) != (d_prev_wt == nullptr))
+        return fail(ctx, RVCP_E_INVALID,
+                    "TAA upsampling history needs d_prev_resolved and d_prev_weight together");
+    if (prev_view && !d_prev)
+        return fail(ctx, RVCP_E_INVALID, "TAA upsampling: prev_view without a history");
+    // a camera at rest fetches q = p exactly and never resamples: byte-equal views are no view
+    const bool moved = prev_view && std::memcmp(cur_view, prev_view, sizeof(*cur_view)) != 0;
+    if (moved && !d_g_hi)
+        return fail(ctx, RVCP_E_INVALID, "TAA upsampling: a moved camera needs d_gbuffer_hi");
+    rvcp_taau_params_t P;
+    if (params) P = *params;
+    else (void)impl_taau_params_default(&P);
+    // (negated compares: a NaN is rejected too)
+    if (!(P.max_weight > 0.0f && P.max_weight <= FLT_MAX))
+        return fail(ctx, RVCP_E_INVALID, "TAA upsampling max_weight must be finite and > 0");
+    if (!(P.init_weight > 0.0f && P.init_weight <= FLT_MAX))
+        return fail(ctx, RVCP_E_INVALID, "TAA upsampling init_weight must be finite and > 0");
+    if (P.clamp > 1)
+        return fail(ctx, RVCP_E_INVALID, "TAA upsampling clamp must be 0 or 1");
+    if (P._pad != 0)
+        return fail(ctx, RVCP_E_INVALID, "TAA upsampling params._pad must be 0");
+    const size_t npx = (size_t)width * height, lpx = npx / scale / scale;
+    {   // a lane reads its neighbours' colours and history: no output may overlap an input or
+        // another output
+        const struct { const void *p; size_t n; } in[4] = {
+            {d_cur, lpx * 12}, {d_g_hi, npx * 32}, {d_prev, npx * 12}, {d_prev_wt, npx * 4}};
+        const struct { const void *p; size_t n; } out[3] = {
+            {d_out, npx * 12}, {d_out_wt, npx * 4}, {d_rgba8_out, npx * 4}};
+        for (int o = 0; o < 3; ++o) {
+            for (int i = 0; i < 4; ++i)
+                if (ranges_overlap(out[o].p, out[o].n, in[i].p, in[i].n))
+                    return fail(ctx, RVCP_E_INVALID, "TAA upsampling output overlaps an input");
+            for (int q = o + 1; q < 3; ++q)
+                if (ranges_overlap(out[o].p, out[o].n, out[q].p, out[q].n))
+                    return fail(ctx, RVCP_E_INVALID, "TAA upsampling outputs overlap each other");
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if (!ctx->evtu0) {
+        HIP_TRY(ctx, hipEventCreate(&ctx->evtu0));
+        HIP_TRY(ctx, hipEventCreate(&ctx->evtu1));
+    }
+    // behind a render pending on this context (when it runs on another stream), and behind the
+    // context's previous step, whose outputs are usually this one's history
+    if (ctx->pending && ctx->render_stream != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev1, 0));
+    if (ctx->taau_recorded) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evtu1, 0));
+    HIP_TRY(ctx, hipEventRecord(ctx->evtu0, s));
+    const uint32_t mode = !d_prev ? 0u : moved ? 2u : 1u;
+    if (rvcp_launch_taa_upsample((const float *)d_cur, d_g_hi, (const float *)d_prev,
+                                 (const float *)d_prev_wt, (float *)d_out, (float *)d_out_wt,
+                                 (uint32_t *)d_rgba8_out, ctx->d_gamma, width, height, scale, mode,
+                                 jit_view, cur_view, prev_view, &P, 0u, s) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string("TAA upsampling launch failed: ") +
+                                         hipGetErrorString(hipGetLastError()));
+    HIP_TRY(ctx, hipEventRecord(ctx->evtu1, s));
+    ctx->taau_recorded = true;
+    ctx->taau_pending = true;
+    return RVCP_OK;
+}
+
+static int impl_taau_wait(rvcp_ctx_t *ctx, float *taau_ms)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!ctx->taau_pending) return fail(ctx, RVCP_E_INVALID, "no TAA upsampling step in flight");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->evtu1));
+    if (taau_ms) HIP_TRY(ctx, hipEventElapsedTime(taau_ms, ctx->evtu0, ctx->evtu1));
+    ctx->taau_pending = false;
+    return RVCP_OK;
+}
+
+static int impl_set_taa_upsample(rvcp_ctx_t *ctx, uint32_t scale)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (scale < 1 || scale > 4)
+        return fail(ctx, RVCP_E_INVALID, "the TAA upsampling scale must be in 1..4");
+    if (ctx->pending)
+        return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    if (scale == ctx->taau_scale) return RVCP_OK;
+    ctx->taau_scale = scale;
+    ctx->tp_valid = false;      // histories of frames traced at different sizes do not mix
+    ctx->sv_valid = false;
+    ctx->taa_tp.valid = false;
+    ctx->taa_sv.valid = false;
+    ctx->taau_tp.valid = false;
+    ctx->taau_sv.valid = false;
+    return RVCP_OK;
+}
+
+static int impl_get_taa_upsample(rvcp_ctx_t *ctx, uint32_t *scale)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!scale) return fail(ctx, RVCP_E_INVALID, "invalid get_taa_upsample arguments");
+    *scale = ctx->taau_scale;
+    return RVCP_OK;
+}
+
+// What a stateful chain does for its upsampling state `st` before it renders (the scale is above
+// 1; width x height is the OUTPUT frame): as taa_chain_begin, the jitter being that of the traced
+// lw x lh frame
+static int taau_chain_begin(rvcp_ctx_t *ctx, rvcp_ctx::TaauState &st, bool have,
+                            const rvcp_push_constant_t *push, uint32_t width, uint32_t height,
+                            uint32_t lw, uint32_t lh, rvcp_push_constant_t *jpush, bool *resume)
+{
+    const size_t npx = (size_t)width * height;
+    if (st.cap < npx) {
+        st.valid = false;
+        st.cap = 0;
+        for (int i = 0; i < 2; ++i) {
+            (void)hipFree(st.d_res[i]);
+            (void)hipFree(st.d_wt[i]);
+            st.d_res[i] = nullptr;
+            st.d_wt[i] = nullptr;
+        }
+        (void)hipFree(st.d_gbuf);
+        st.d_gbuf = nullptr;
+        for (int i = 0; i < 2; ++i) {
+            HIP_TRY(ctx, hipMalloc((void **)&st.d_res[i], npx * 12));
+            HIP_TRY(ctx, hipMalloc((void **)&st.d_wt[i], npx * 4));
+        }
+        HIP_TRY(ctx, hipMalloc(&st.d_gbuf, npx * sizeof(rvcp_gbuffer_texel_t)));
+        st.cap = npx;
+    }
+    *resume = have && st.valid && st.width == width && st.height == height;
+    if (!*resume) st.counter = 0;       // the state is dropped with the chain's history
+    st.valid = false;                   // until this frame is complete
+    float j[2];
+    (void)impl_taa_jitter(st.counter, j);
+    if (impl_taa_jitter_push(push, lw, lh, j, jpush) != RVCP_OK)
+        return fail(ctx, RVCP_E_INVALID, "the camera's forward is zero or parallel to up");
+    return RVCP_OK;
+}
+
+// ... and behind its last step: the output-size G-buffer through the unjittered camera when it
+// moved, and the upsampling of d_final (traced through jit_view) into the state's free slot and
+// d_rgba
+static int taau_chain_resolve(rvcp_ctx_t *ctx, rvcp_ctx::TaauState &st, bool resume,
+                              const rvcp_push_constant_t *push, const rvcp_temporal_view_t *base_view,
+                              const rvcp_temporal_view_t *jit_view, const float *d_final,
+                              uint32_t width, uint32_t height)
+{
+    const uint32_t prev = st.slot, cur = prev ^ 1u;
+    const bool moved = resume && std::memcmp(&st.camera, &push->camera, sizeof(rvcp_camera_t)) != 0;
+    if (moved) {
+        const int rc = impl_render_gbuffer_async(ctx, push, width, height, st.d_gbuf, ctx->stream);
+        if (rc != RVCP_OK) return rc;
+    }
+    return impl_taa_upsample_async(ctx, ctx->taau_scale, jit_view, base_view,
+                                   moved ? &st.view : nullptr, d_final, moved ? st.d_gbuf : nullptr,
+                                   resume ? st.d_res[prev] : nullptr,
+                                   resume ? st.d_wt[prev] : nullptr, width, height, nullptr,
+                                   st.d_res[cur], st.d_wt[cur], ctx->d_rgba, ctx->stream);
+}
+
+// ... and once the frame is complete
+static void taau_chain_commit(rvcp_ctx::TaauState &st, const rvcp_push_constant_t *push,
+                              const rvcp_temporal_view_t *base_view, uint32_t width, uint32_t height)
+{
+    st.slot ^= 1u;
+    st.width = width;
+    st.height = height;
+    st.camera = push->camera;
+    st.view = *base_view;
+    st.counter += 1;
+    st.valid = true;
+}
+
 static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
                                 uint32_t height, const rvcp_temporal_params_t *tparams,
                                 uint32_t flags, const rvcp_denoise_params_t *dparams,
@@ -2097,14 +2326,23 @@ static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
         return fail(ctx, RVCP_E_UNSUPPORTED, "render_temporal drives one GPU (n_gpus = 1)");
     if (ctx->pending)
         return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    // With the upsampling scale above 1 (§4.14): width x height below is the TRACED frame, the
+    // whole chain runs at that size, and out_w x out_h is what the last step writes
+    const uint32_t up = ctx->taau_scale, out_w = width, out_h = height;
+    if (up > 1) {
+        if (width % up != 0 || height % up != 0)
+            return fail(ctx, RVCP_E_INVALID, "render_temporal: the TAA upsampling scale must divide width and height");
+        width /= up;
+        height /= up;
+    }
     rvcp_temporal_view_t view_now;
     if (impl_temporal_view_from_push(push, width, height, &view_now) != RVCP_OK)
         return fail(ctx, RVCP_E_INVALID, "render_temporal: the camera's forward is zero or parallel to up");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool denoise = (flags & RVCP_TEMPORAL_DENOISE) != 0;
-    const size_t npx = (size_t)width * height;
+    const size_t npx = (size_t)width * height, out_npx = (size_t)out_w * out_h;
     int rc;
-    if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, npx, 4)) != RVCP_OK) return rc;
+    if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, out_npx, 4)) != RVCP_OK) return rc;
     if (ctx->cap_tp < npx) {            // (a larger frame: the history is dropped with its buffers)
         ctx->tp_valid = false;
         ctx->cap_tp = 0;
@@ -2133,14 +2371,21 @@ static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
     // With the TAA switch set (§4.13): everything below runs through the jittered camera `jpush`,
     // the chain's own history always reprojects (through the jittered cameras), no step stores
     // RGBA8, and the resolve of the final linear colour under the unjittered cameras ends the frame.
-    const bool taa = ctx->taa;
+    // With the upsampling scale above 1 (§4.14) the upsampling step takes the resolve's place:
+    // base_view is then the unjittered camera at the output size
+    const bool taa = ctx->taa || up > 1;
     const rvcp_push_constant_t *const base_push = push;
-    const rvcp_temporal_view_t base_view = view_now;
+    rvcp_temporal_view_t base_view = view_now;
+    if (up > 1 && impl_temporal_view_from_push(push, out_w, out_h, &base_view) != RVCP_OK)
+        return fail(ctx, RVCP_E_INVALID, "render_temporal: the camera's forward is zero or parallel to up");
     rvcp_push_constant_t jpush;
     bool taa_resume = false;
     if (taa) {
-        if ((rc = taa_chain_begin(ctx, ctx->taa_tp, have, base_push, width, height, &jpush,
-                                  &taa_resume)) != RVCP_OK)
+        rc = up > 1 ? taau_chain_begin(ctx, ctx->taau_tp, have, base_push, out_w, out_h, width,
+                                       height, &jpush, &taa_resume)
+                    : taa_chain_begin(ctx, ctx->taa_tp, have, base_push, width, height, &jpush,
+                                      &taa_resume);
+        if (rc != RVCP_OK)
             return rc;
         push = &jpush;
         if (impl_temporal_view_from_push(push, width, height, &view_now) != RVCP_OK)
@@ -2185,8 +2430,10 @@ static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
     const float *d_final = demod ? ctx->d_tp_cur : denoise ? ctx->d_tp_show : ctx->d_tp_lin[cur];
     bool resolve_enqueued = false;
     if (rc == RVCP_OK && taa) {
-        rc = taa_chain_resolve(ctx, ctx->taa_tp, taa_resume, base_push, &base_view, d_final,
-                               ctx->d_tp_gbuf[cur], width, height);
+        rc = up > 1 ? taau_chain_resolve(ctx, ctx->taau_tp, taa_resume, base_push, &base_view,
+                                         &view_now, d_final, out_w, out_h)
+                    : taa_chain_resolve(ctx, ctx->taa_tp, taa_resume, base_push, &base_view, d_final,
+                                        ctx->d_tp_gbuf[cur], width, height);
         resolve_enqueued = rc == RVCP_OK;
     }
     if (rc != RVCP_OK) {
@@ -2204,12 +2451,14 @@ static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
     if (denoise && (rc = impl_denoise_wait(ctx, denoise_ms)) != RVCP_OK) return rc;
     if (demod && (rc = impl_albedo_wait(ctx, nullptr, nullptr)) != RVCP_OK) return rc;
     if (resolve_enqueued) {
-        if ((rc = impl_taa_wait(ctx, nullptr)) != RVCP_OK) return rc;
-        d_final = ctx->taa_tp.d_res[ctx->taa_tp.slot ^ 1u];
+        if ((rc = up > 1 ? impl_taau_wait(ctx, nullptr) : impl_taa_wait(ctx, nullptr)) != RVCP_OK)
+            return rc;
+        d_final = up > 1 ? ctx->taau_tp.d_res[ctx->taau_tp.slot ^ 1u]
+                         : ctx->taa_tp.d_res[ctx->taa_tp.slot ^ 1u];
     }
-    HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, npx * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, out_npx * 4, hipMemcpyDeviceToHost));
     if (out_linear_rgb)
-        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, d_final, npx * 12, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, d_final, out_npx * 12, hipMemcpyDeviceToHost));
     if (out_history_len)
         HIP_TRY(ctx, hipMemcpy(out_history_len, ctx->d_tp_len[cur], npx * 4, hipMemcpyDeviceToHost));
     ctx->tp_slot = cur;
@@ -2218,7 +2467,8 @@ static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
     ctx->tp_camera = push->camera;
     ctx->tp_view = view_now;
     ctx->tp_valid = true;
-    if (taa) taa_chain_commit(ctx->taa_tp, base_push, &base_view, width, height);
+    if (up > 1) taau_chain_commit(ctx->taau_tp, base_push, &base_view, out_w, out_h);
+    else if (taa) taa_chain_commit(ctx->taa_tp, base_push, &base_view, width, height);
     return RVCP_OK;
 }
 
@@ -2619,14 +2869,23 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
         return fail(ctx, RVCP_E_UNSUPPORTED, "render_svgf drives one GPU (n_gpus = 1)");
     if (ctx->pending)
         return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    // With the upsampling scale above 1 (§4.14): width x height below is the TRACED frame, the
+    // whole chain runs at that size, and out_w x out_h is what the last step writes
+    const uint32_t up = ctx->taau_scale, out_w = width, out_h = height;
+    if (up > 1) {
+        if (width % up != 0 || height % up != 0)
+            return fail(ctx, RVCP_E_INVALID, "render_svgf: the TAA upsampling scale must divide width and height");
+        width /= up;
+        height /= up;
+    }
     rvcp_temporal_view_t view_now;
     if (impl_temporal_view_from_push(push, width, height, &view_now) != RVCP_OK)
         return fail(ctx, RVCP_E_INVALID, "render_svgf: the camera's forward is zero or parallel to up");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool feedback = (flags & RVCP_SVGF_FEEDBACK) != 0;
-    const size_t npx = (size_t)width * height;
+    const size_t npx = (size_t)width * height, out_npx = (size_t)out_w * out_h;
     int rc;
-    if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, npx, 4)) != RVCP_OK) return rc;
+    if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, out_npx, 4)) != RVCP_OK) return rc;
     if (ctx->cap_sv < npx) {            // (a larger frame: the history is dropped with its buffers)
         ctx->sv_valid = false;
         svgf_free_state(ctx);
@@ -2644,14 +2903,21 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
     }
     const bool have = ctx->sv_valid && ctx->sv_width == width && ctx->sv_height == height;
     // With the TAA switch set (§4.13): as rvcp_render_temporal
-    const bool taa = ctx->taa;
+    // With the upsampling scale above 1 (§4.14) the upsampling step takes the resolve's place:
+    // base_view is then the unjittered camera at the output size
+    const bool taa = ctx->taa || up > 1;
     const rvcp_push_constant_t *const base_push = push;
-    const rvcp_temporal_view_t base_view = view_now;
+    rvcp_temporal_view_t base_view = view_now;
+    if (up > 1 && impl_temporal_view_from_push(push, out_w, out_h, &base_view) != RVCP_OK)
+        return fail(ctx, RVCP_E_INVALID, "render_svgf: the camera's forward is zero or parallel to up");
     rvcp_push_constant_t jpush;
     bool taa_resume = false;
     if (taa) {
-        if ((rc = taa_chain_begin(ctx, ctx->taa_sv, have, base_push, width, height, &jpush,
-                                  &taa_resume)) != RVCP_OK)
+        rc = up > 1 ? taau_chain_begin(ctx, ctx->taau_sv, have, base_push, out_w, out_h, width,
+                                       height, &jpush, &taa_resume)
+                    : taa_chain_begin(ctx, ctx->taa_sv, have, base_push, width, height, &jpush,
+                                      &taa_resume);
+        if (rc != RVCP_OK)
             return rc;
         push = &jpush;
         if (impl_temporal_view_from_push(push, width, height, &view_now) != RVCP_OK)
@@ -2697,8 +2963,10 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
     const float *d_final = demod ? ctx->d_sv_cur : ctx->d_sv_show;     // the displayed linear frame
     bool resolve_enqueued = false;
     if (rc == RVCP_OK && taa) {
-        rc = taa_chain_resolve(ctx, ctx->taa_sv, taa_resume, base_push, &base_view, d_final,
-                               ctx->d_sv_gbuf[cur], width, height);
+        rc = up > 1 ? taau_chain_resolve(ctx, ctx->taau_sv, taa_resume, base_push, &base_view,
+                                         &view_now, d_final, out_w, out_h)
+                    : taa_chain_resolve(ctx, ctx->taa_sv, taa_resume, base_push, &base_view, d_final,
+                                        ctx->d_sv_gbuf[cur], width, height);
         resolve_enqueued = rc == RVCP_OK;
     }
     if (rc != RVCP_OK) {
@@ -2713,12 +2981,14 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
     if ((rc = impl_svgf_wait(ctx, accumulate_ms, filter_ms)) != RVCP_OK) return rc;
     if (demod && (rc = impl_albedo_wait(ctx, nullptr, nullptr)) != RVCP_OK) return rc;
     if (resolve_enqueued) {
-        if ((rc = impl_taa_wait(ctx, nullptr)) != RVCP_OK) return rc;
-        d_final = ctx->taa_sv.d_res[ctx->taa_sv.slot ^ 1u];
+        if ((rc = up > 1 ? impl_taau_wait(ctx, nullptr) : impl_taa_wait(ctx, nullptr)) != RVCP_OK)
+            return rc;
+        d_final = up > 1 ? ctx->taau_sv.d_res[ctx->taau_sv.slot ^ 1u]
+                         : ctx->taa_sv.d_res[ctx->taa_sv.slot ^ 1u];
     }
-    HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, npx * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, out_npx * 4, hipMemcpyDeviceToHost));
     if (out_linear_rgb)
-        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, d_final, npx * 12, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, d_final, out_npx * 12, hipMemcpyDeviceToHost));
     if (out_variance)
         HIP_TRY(ctx, hipMemcpy(out_variance, ctx->d_sv_showvar, npx * 4, hipMemcpyDeviceToHost));
     if (out_history_len)
@@ -2731,7 +3001,8 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
     ctx->sv_camera = push->camera;
     ctx->sv_view = view_now;
     ctx->sv_valid = true;
-    if (taa) taa_chain_commit(ctx->taa_sv, base_push, &base_view, width, height);
+    if (up > 1) taau_chain_commit(ctx->taau_sv, base_push, &base_view, out_w, out_h);
+    else if (taa) taa_chain_commit(ctx->taa_sv, base_push, &base_view, width, height);
     return RVCP_OK;
 }
 
@@ -3471,6 +3742,41 @@ int rvcp_get_taa(rvcp_ctx_t *ctx, int *on)
 int rvcp_taa_reset(rvcp_ctx_t *ctx)
 {
     return barrier(ctx, [&] { return impl_taa_reset(ctx); });
+}
+
+int rvcp_taau_params_default(rvcp_taau_params_t *params)
+{
+    return barrier(nullptr, [&] { return impl_taau_params_default(params); });
+}
+
+int rvcp_taa_upsample_async(rvcp_ctx_t *ctx, uint32_t scale, const rvcp_temporal_view_t *jit_view,
+                            const rvcp_temporal_view_t *cur_view,
+                            const rvcp_temporal_view_t *prev_view, const void *d_cur_linear,
+                            const void *d_gbuffer_hi, const void *d_prev_resolved,
+                            const void *d_prev_weight, uint32_t width, uint32_t height,
+                            const rvcp_taau_params_t *params, void *d_out_resolved,
+                            void *d_out_weight, void *d_rgba8_out, void *stream)
+{
+    return barrier(ctx, [&] {
+        return impl_taa_upsample_async(ctx, scale, jit_view, cur_view, prev_view, d_cur_linear,
+                                       d_gbuffer_hi, d_prev_resolved, d_prev_weight, width, height,
+                                       params, d_out_resolved, d_out_weight, d_rgba8_out, stream);
+    });
+}
+
+int rvcp_taau_wait(rvcp_ctx_t *ctx, float *taau_ms)
+{
+    return barrier(ctx, [&] { return impl_taau_wait(ctx, taau_ms); });
+}
+
+int rvcp_set_taa_upsample(rvcp_ctx_t *ctx, uint32_t scale)
+{
+    return barrier(ctx, [&] { return impl_set_taa_upsample(ctx, scale); });
+}
+
+int rvcp_get_taa_upsample(rvcp_ctx_t *ctx, uint32_t *scale)
+{
+    return barrier(ctx, [&] { return impl_get_taa_upsample(ctx, scale); });
 }
 
 }  // extern "C"

@@ -403,6 +403,18 @@ int rvcp_launch_taa_resolve(const float *cur_c, const void *cur_g, const float *
                             const struct rvcp_temporal_view *cur_view,
                             const struct rvcp_temporal_view *prev_view,
                             const struct rvcp_taa_params *params, void *stream);
+// The temporal upsampling step (rvcp_taau.hip) of a width x height OUTPUT frame
+// from a frame traced at width / scale x height / scale: modes as the TAA resolve's (g_hi is read
+// in mode 2 only, prev_* in modes 1 and 2); out_rgba and prev_view may be null; force_direct: the
+// form without LDS staging (tools/taau_time.py's comparison)
+int rvcp_launch_taa_upsample(const float *cur_c, const void *g_hi, const float *prev_c,
+                             const float *prev_w, float *out_c, float *out_w, uint32_t *out_rgba,
+                             const float *gamma_t, uint32_t width, uint32_t height, uint32_t scale,
+                             uint32_t mode, const struct rvcp_temporal_view *jit_view,
+                             const struct rvcp_temporal_view *cur_view,
+                             const struct rvcp_temporal_view *prev_view,
+                             const struct rvcp_taau_params *params, uint32_t force_direct,
+                             void *stream);
 int rvcp_launch_assemble(const uint32_t *gathered, uint32_t slot_rows, uint32_t width,
                          uint32_t height, uint32_t shard_count, uint32_t *frame, void *stream);
 int rvcp_launch_fill(uint32_t *out_rgba, float *out_lin, uint32_t n_pixels, uint32_t rgba,

@@ -166,7 +166,8 @@ class RayTracer:
             denoise = np.ascontiguousarray(denoise, dtype=abi.DENOISE_PARAMS_DTYPE)
         rgba = np.empty((height, width, 4), dtype=np.uint8)
         lin = np.empty((height, width, 3), dtype=np.float32) if want_linear else None
-        hist = np.empty((height, width), dtype=np.uint32) if want_history else None
+        th, tw = self._traced_size(width, height)
+        hist = np.empty((th, tw), dtype=np.uint32) if want_history else None
         stats = np.zeros((), dtype=abi.STATS_DTYPE)
         t_ms, d_ms = ctypes.c_float(0.0), ctypes.c_float(0.0)
         self._check(self._lib.rvcp_render_temporal(
@@ -211,8 +212,9 @@ class RayTracer:
             svgf = np.ascontiguousarray(svgf, dtype=abi.SVGF_PARAMS_DTYPE)
         rgba = np.empty((height, width, 4), dtype=np.uint8)
         lin = np.empty((height, width, 3), dtype=np.float32) if want_linear else None
-        var = np.empty((height, width), dtype=np.float32) if want_variance else None
-        hist = np.empty((height, width), dtype=np.uint32) if want_history else None
+        th, tw = self._traced_size(width, height)
+        var = np.empty((th, tw), dtype=np.float32) if want_variance else None
+        hist = np.empty((th, tw), dtype=np.uint32) if want_history else None
         stats = np.zeros((), dtype=abi.STATS_DTYPE)
         a_ms, f_ms = ctypes.c_float(0.0), ctypes.c_float(0.0)
         self._check(self._lib.rvcp_render_svgf(
@@ -470,6 +472,57 @@ class RayTracer:
         """rvcp_taa_wait: block until the last taa_resolve_async is done; its device time, ms."""
         ms = ctypes.c_float(0.0)
         self._check(self._lib.rvcp_taa_wait(self._ctx, ctypes.cast(ctypes.byref(ms), ctypes.c_void_p)))
+        return float(ms.value)
+
+    # temporal upsampling (DESIGN.md §4.14)
+    @property
+    def taa_upsample(self) -> int:
+        """The context's upsampling scale (rvcp_get_taa_upsample / rvcp_set_taa_upsample): 1 (off),
+        2, 3 or 4.  While it is above 1, render_temporal and render_svgf trace width / scale x
+        height / scale pixels through the jittered camera and return the width x height frame
+        that taa_upsample_async accumulates (it replaces the TAA resolve); the history lengths and
+        the variance keep the traced size.  Changing it drops both chains' histories."""
+        scale = ctypes.c_uint32(0)
+        self._check(self._lib.rvcp_get_taa_upsample(self._ctx, ctypes.cast(ctypes.byref(scale),
+                                                                          ctypes.c_void_p)))
+        return int(scale.value)
+
+    @taa_upsample.setter
+    def taa_upsample(self, scale: int):
+        self._check(self._lib.rvcp_set_taa_upsample(self._ctx, int(scale)))
+
+    def _traced_size(self, width, height):
+        """(rows, columns) of the frame render_temporal / render_svgf trace for a width x height
+        call: the optional outputs other than the frame itself have this size."""
+        s = self.taa_upsample
+        if s > 1 and width % s == 0 and height % s == 0:
+            return height // s, width // s
+        return height, width
+
+    def taa_upsample_async(self, scale: int, jit_view, cur_view, prev_view, d_cur_linear: int,
+                           d_gbuffer_hi: int, d_prev_resolved: int, d_prev_weight: int, width,
+                           height, d_out_resolved: int, d_out_weight: int, d_rgba: int = 0,
+                           params=None, stream: int = 0):
+        """rvcp_taa_upsample_async: enqueue one upsampling step of a width x height frame from a
+        frame traced at width / scale x height / scale in device memory.  jit_view: the
+        abi.temporal_view(...) record of the jittered camera at the traced size; cur_view /
+        prev_view: those of the UNJITTERED cameras at width x height (prev_view None: the camera is
+        at rest); d_gbuffer_hi: the width x height G-buffer through the unjittered camera, needed
+        when the camera moved, else 0; d_prev_* both 0: no history.  Wait with taau_wait()."""
+        views = [None if v is None else np.ascontiguousarray(v, dtype=abi.TEMPORAL_VIEW_DTYPE)
+                 for v in (jit_view, cur_view, prev_view)]
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=abi.TAAU_PARAMS_DTYPE)
+        P = lambda a: ctypes.c_void_p(a) if a else None   # noqa: E731
+        self._check(self._lib.rvcp_taa_upsample_async(
+            self._ctx, scale, abi.ptr(views[0]), abi.ptr(views[1]), abi.ptr(views[2]),
+            P(d_cur_linear), P(d_gbuffer_hi), P(d_prev_resolved), P(d_prev_weight), width, height,
+            abi.ptr(params), P(d_out_resolved), P(d_out_weight), P(d_rgba), P(stream)))
+
+    def taau_wait(self) -> float:
+        """rvcp_taau_wait: block until the last taa_upsample_async is done; its device time, ms."""
+        ms = ctypes.c_float(0.0)
+        self._check(self._lib.rvcp_taau_wait(self._ctx, ctypes.cast(ctypes.byref(ms), ctypes.c_void_p)))
         return float(ms.value)
 
     def wait(self):

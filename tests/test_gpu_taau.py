@@ -1,0 +1,453 @@
+"""Temporal upsampling on the GPU: rvcp_taa_upsample_async bit-identical to the
+numpy restatement (tests/taau_ref.py) with no pixel excluded, the fused store equal to
+oracle.gamma_u8 of the result under both unorm_rules, the argument checks (every rejected call is
+rejected on the host before any launch), rvcp_render_temporal and rvcp_render_svgf with the scale
+above 1 against the library's own stateless composition and against the restatements, the
+restarts, scale 1 against a context that never heard of upsampling, and the path-traced gate."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import denoise_ref as R
+import taa_ref as A
+import taau_ref as U
+import temporal_ref as T
+import rvcp_amd
+from rvcp_amd import abi
+from test_gpu_albedo import (assert_same, bits, blank, dev, floats, gpu_demodulate, gpu_remodulate,
+                             gpu_svgf, gpu_temporal)
+from test_gpu_taa import Composition, chain_frame, chain_pushes, gpu_gbuffer
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+f32 = np.float32
+SEED = 5            # a seed at which the generators hold their mixes at every size used here
+
+
+@pytest.fixture(scope="module")
+def tracers():
+    """One scene-less context per unorm_rule: the step needs no scene."""
+    rts = [rvcp_amd.RayTracer(unorm_rule=rule) for rule in (abi.UNORM_DRIVER, abi.UNORM_NEAREST)]
+    yield rts
+    for rt in rts:
+        rt.close()
+
+
+def gpu_upsample(rt, c, s, jv, cv, pv, g_hi, pr, pw, params, want_rgba=True):
+    """rvcp_taa_upsample_async on device tensors (the context's own stream); (floats, weights,
+    rgba).  The outputs start from a pattern no result has."""
+    h, w = c.shape[:2]
+    H, W = h * s, w * s
+    d_c = dev(c)
+    d_g = dev(g_hi) if g_hi is not None else None
+    d_prev = [dev(pr), dev(pw)] if pr is not None else None
+    d_out, d_wt, d_rgba = blank(W * H * 12), blank(W * H * 4), blank(W * H * 4, 0)
+    torch.cuda.synchronize()
+    pp = [t.data_ptr() for t in d_prev] if d_prev else [0, 0]
+    rt.taa_upsample_async(s, jv, cv, pv, d_c.data_ptr(), d_g.data_ptr() if d_g is not None else 0,
+                          pp[0], pp[1], W, H, d_out.data_ptr(), d_wt.data_ptr(),
+                          d_rgba.data_ptr() if want_rgba else 0, params)
+    assert rt.taau_wait() >= 0.0
+    return floats(d_out, H, W, 3), floats(d_wt, H, W), d_rgba.cpu().numpy().reshape(H, W, 4)
+
+
+# ---------------------------------------------------------------------------- 1. kernel parity
+# a ragged last wave and last row of blocks; three waves by one block of two traced rows; scale 3
+# with ragged edges; scale 4; one wave; every traced pixel on the border; one traced pixel
+SIZES = [(66, 46, 2), (130, 4, 2), (69, 45, 3), (12, 8, 4), (8, 8, 2), (4, 4, 2), (2, 2, 2)]
+PARAM_SETS = {"defaults": dict(), "clamp_0": dict(clamp=0),
+              "max_weight_is_init_weight": dict(max_weight=0.1, init_weight=0.1)}
+
+
+@pytest.mark.parametrize("mode", ["no_history", "identity", "reprojection"])
+@pytest.mark.parametrize("W,H,s", SIZES)
+def test_upsample_matches_numpy_restatement(tracers, W, H, s, mode):
+    """Every parameter set through the generator's zoomed and jittered traced camera, and the
+    defaults through the output camera itself (zero jitter) and through a camera that looks
+    backwards (every sample behind the output camera: no tap at all)."""
+    for pname, kw in PARAM_SETS.items():
+        params = abi.make_taau_params(**kw)
+        c, jv, cv, pv, g, pr, pw = U.synthetic_case(W, H, s, SEED, params)
+        if mode == "no_history":
+            pr = pw = pv = None
+        if mode == "identity":
+            pv = None
+        jits = {"jittered": jv}
+        if pname == "defaults":
+            jits["zero"] = U.derived_view(cv, s)
+            jits["behind"] = U.derived_view(cv, s, flip=True)
+        for jname, j in jits.items():
+            want, want_wt = U.upsample(c, s, j, cv, pv, g, pr, pw, params)
+            for rule, rt in enumerate(tracers):
+                what = f"{pname} {jname} rule {rule}"
+                got, got_wt, rgba = gpu_upsample(rt, c, s, j, cv, pv, g if mode == "reprojection"
+                                                 else None, pr, pw, params)
+                diff = np.any(bits(got) != bits(want), axis=-1)
+                assert not diff.any(), f"{int(diff.sum())} of {diff.size} pixels differ ({what})"
+                assert_same(got_wt, want_wt, what + ": weights")
+                assert np.array_equal(rgba, R.gamma_rgba(want, rule)), what
+
+
+def test_upsample_default_params_no_rgba_and_equal_views(tracers):
+    """params = NULL takes rvcp_taau_params_default; d_rgba8_out is optional; a prev_view
+    byte-equal to cur_view is the identity path (q = p, no resampling, no G-buffer needed)."""
+    W, H, s = 32, 16, 2
+    c, jv, cv, pv, g, pr, pw = U.synthetic_case(W, H, s, SEED)
+    want, want_wt = U.upsample(c, s, jv, cv, pv, g, pr, pw, U.params())
+    got, got_wt, rgba = gpu_upsample(tracers[0], c, s, jv, cv, pv, g, pr, pw, None, want_rgba=False)
+    assert_same(got, want, "default parameters")
+    assert_same(got_wt, want_wt, "default parameters: weights")
+    assert not rgba.any()
+    ident, ident_wt = U.upsample(c, s, jv, cv, None, None, pr, pw, U.params())
+    got, got_wt, _ = gpu_upsample(tracers[0], c, s, jv, cv, cv.copy(), None, pr, pw, None)
+    assert_same(got, ident, "byte-equal views")
+    assert_same(got_wt, ident_wt, "byte-equal views: weights")
+    assert np.any(bits(ident) != bits(want))
+
+
+@pytest.mark.parametrize("W,H,s", [(66, 46, 2), (69, 45, 3), (12, 8, 4)])
+def test_direct_form_of_the_kernel_matches_too(W, H, s):
+    """The form without LDS staging, which only tools/taau_time.py launches (through the
+    library's internal launcher, on the default stream, without the RGBA8 store)."""
+    L = abi.load()
+    P, u32 = ctypes.c_void_p, ctypes.c_uint32
+    L.rvcp_launch_taa_upsample.argtypes = [P] * 8 + [u32] * 4 + [P] * 4 + [u32, P]
+    L.rvcp_launch_taa_upsample.restype = ctypes.c_int
+    params = abi.make_taau_params()
+    c, jv, cv, pv, g, pr, pw = U.synthetic_case(W, H, s, SEED, params)
+    want, want_wt = U.upsample(c, s, jv, cv, pv, g, pr, pw, params)
+    d_c, d_g, d_pr, d_pw = dev(c), dev(g), dev(pr), dev(pw)
+    d_out, d_wt = blank(W * H * 12), blank(W * H * 4)
+    torch.cuda.synchronize()
+    assert L.rvcp_launch_taa_upsample(d_c.data_ptr(), d_g.data_ptr(), d_pr.data_ptr(),
+                                      d_pw.data_ptr(), d_out.data_ptr(), d_wt.data_ptr(), None, None,
+                                      W, H, s, 2, abi.ptr(jv), abi.ptr(cv), abi.ptr(pv),
+                                      abi.ptr(params), 1, None) == 0
+    torch.cuda.synchronize()
+    assert_same(floats(d_out, H, W, 3), want, "direct form")
+    assert_same(floats(d_wt, H, W), want_wt, "direct form: weights")
+
+
+# ---------------------------------------------------------------------------- 2. API
+def test_api_argument_checks(cornell):
+    L = abi.load()
+    W, H, s = 16, 16, 2
+    c, jv, cv, pv, g, pr, pw = U.synthetic_case(W, H, s, SEED)
+    npx = W * H
+    d_c, d_g, d_pr, d_pw = dev(c), dev(g), dev(pr), dev(pw)
+    d_out, d_wt, d_rgba = blank(npx * 12 + 64), blank(npx * 4 + 64), blank(npx * 4)
+    torch.cuda.synchronize()
+    P = lambda a: ctypes.c_void_p(a) if a else None       # noqa: E731
+    E = abi.RVCP_E_INVALID
+    with rvcp_amd.RayTracer(spp=2) as rt:                 # no scene uploaded
+        h = rt.handle
+        base = dict(s=s, jv=jv, cv=cv, pv=pv, cur=d_c.data_ptr(), g=d_g.data_ptr(),
+                    prev=d_pr.data_ptr(), prev_wt=d_pw.data_ptr(), w=W, h=H,
+                    params=abi.make_taau_params(), out=d_out.data_ptr(), out_wt=d_wt.data_ptr(),
+                    rgba=d_rgba.data_ptr())
+
+        def call(**kw):
+            a = dict(base, **kw)
+            return L.rvcp_taa_upsample_async(
+                h, a["s"], abi.ptr(a["jv"]), abi.ptr(a["cv"]), abi.ptr(a["pv"]), P(a["cur"]),
+                P(a["g"]), P(a["prev"]), P(a["prev_wt"]), a["w"], a["h"], abi.ptr(a["params"]),
+                P(a["out"]), P(a["out_wt"]), P(a["rgba"]), None)
+        for name in ("cur", "out", "out_wt", "w", "h"):                   # NULL or zero
+            assert call(**{name: 0}) == E, name
+        for name in ("jv", "cv"):                                         # both views are required
+            assert call(**{name: None}) == E, name
+        for bad in (0, 1, 5, 1 << 31):                                    # scale outside 2..4
+            assert call(s=bad) == E, bad
+        for kw in (dict(s=3), dict(w=15), dict(h=18, s=4)):               # sizes it does not divide
+            assert call(**kw) == E, kw
+            assert b"divide" in L.rvcp_last_error(h)
+        assert call(w=1 << 16, h=1 << 15) == E                            # W * H = 2^31
+        for name in ("prev", "prev_wt"):                                  # a partial history
+            assert call(**{name: 0}) == E, name
+            assert b"together" in L.rvcp_last_error(h)
+        assert call(prev=0, prev_wt=0) == E                               # prev_view without a history
+        assert b"without a history" in L.rvcp_last_error(h)
+        assert call(g=0) == E and b"d_gbuffer_hi" in L.rvcp_last_error(h)  # a moved camera
+        # outputs over inputs (taps and the box read neighbours) and over each other
+        for kw in (dict(out=base["cur"]), dict(out=base["prev"]), dict(out=base["prev"] + 12),
+                   dict(out=base["g"]), dict(out=base["g"] + 32 * npx - 4),
+                   dict(out_wt=base["prev_wt"]), dict(out_wt=base["prev_wt"] + 4 * npx - 4),
+                   dict(out_wt=base["cur"] + 3 * npx - 4), dict(rgba=base["g"]),
+                   dict(rgba=base["prev"]), dict(rgba=base["out"]),
+                   dict(out_wt=base["out"] + 12 * npx - 4)):
+            assert call(**kw) == E, kw
+            assert b"overlap" in L.rvcp_last_error(h)
+        for kw in (dict(max_weight=0.0), dict(max_weight=-1.0), dict(max_weight=float("nan")),
+                   dict(max_weight=float("inf")), dict(init_weight=0.0),
+                   dict(init_weight=float("nan")), dict(init_weight=float("inf")), dict(clamp=2),
+                   dict(_pad=1)):
+            assert call(params=abi.make_taau_params(**kw)) == E, kw
+        assert L.rvcp_taau_wait(h, None) == E              # nothing was enqueued
+        for t in (d_out, d_wt, d_rgba):                    # ... and nothing was written
+            assert np.all(t.cpu().numpy() == 0xA5)
+        # no scene is needed; a G-buffer that is not needed is ignored
+        assert call(pv=None) == abi.RVCP_OK
+        assert rt.taau_wait() >= 0.0
+        want, want_wt = U.upsample(c, s, jv, cv, None, None, pr, pw, U.params())
+        assert_same(floats(d_out[:npx * 12], H, W, 3), want, "identity with a G-buffer given")
+        assert_same(floats(d_wt[:npx * 4], H, W), want_wt, "its weights")
+        # the switch: 1 by default, its range, refused while a frame is pending
+        assert rt.taa_upsample == 1
+        for bad in (0, 5):
+            assert L.rvcp_set_taa_upsample(h, bad) == E
+        rt.upload_scene(cornell)
+        d_f = blank(npx * 4)
+        rt.render_async(cornell.push_constant(1.0), W, H, d_f.data_ptr())
+        assert L.rvcp_set_taa_upsample(h, 2) == E and b"in flight" in L.rvcp_last_error(h)
+        rt.wait()
+        for scale in (2, 3, 4, 1):
+            rt.taa_upsample = scale
+            assert rt.taa_upsample == scale
+        assert L.rvcp_get_taa_upsample(h, None) == E
+        # a size the scale does not divide
+        rt.taa_upsample = 2
+        push = np.ascontiguousarray(cornell.push_constant(1.0))
+        out = np.zeros((24, 37, 4), dtype=np.uint8)
+        for fn, args in ((L.rvcp_render_temporal, (None, 0, None, abi.ptr(out), None, None, None,
+                                                   None, None)),
+                         (L.rvcp_render_svgf, (None, None, 0, abi.ptr(out), None, None, None, None,
+                                               None, None))):
+            assert fn(h, abi.ptr(push), 37, 24, *args) == E
+            assert b"divide" in L.rvcp_last_error(h)
+            assert fn(h, abi.ptr(push), 36, 25, *args) == E
+        assert not out.any()
+        rt.taa_upsample = 1
+
+
+# ---------------------------------------------------------------------------- 3. stateful chains
+CW, CH, CS = 36, 24, 2
+
+
+@pytest.fixture(scope="module")
+def pair(cornell):
+    """Two contexts with the Cornell box: `rt` runs the stateful chains, `rs` the stateless
+    steps of the composition."""
+    import albedo_ref as AL
+    rt, rs = rvcp_amd.RayTracer(spp=2), rvcp_amd.RayTracer(spp=2)
+    rt.upload_scene(cornell)
+    rs.upload_scene(cornell)
+    yield dict(rt=rt, rs=rs, table=AL.albedo_table(cornell.aligned_materials()))
+    rt.close()
+    rs.close()
+
+
+class UpComposition(Composition):
+    """The library's own stateless composition of one chain with the upsampling scale above 1,
+    next to the restatements': test_gpu_taa's composition up to the chain's final colour, at the
+    traced size, then the upsampling step in the resolve's place."""
+
+    def __init__(self, rs, table, svgf, demod, scale):
+        self.scale = scale
+        super().__init__(rs, table, svgf, demod)
+
+    def restart(self):
+        super().restart()
+        self.wt = None
+        self.ref_up = U.Chain(self.scale)
+
+    def taa_restart(self):
+        super().taa_restart()
+        self.ref_up = U.Chain(self.scale)
+
+    def frame(self, push, W=CW, H=CH):
+        """(upsampled colour, its RGBA8, history length of the chain at the traced size)."""
+        rs, s = self.rs, self.scale
+        w, h = W // s, H // s
+        jp = rvcp_amd.taa_jitter_push(push, w, h, rvcp_amd.taa_jitter(self.counter))
+        raw = rs.render_push(jp, w, h, want_linear=True)[1]
+        g = gpu_gbuffer(rs, jp, w, h)
+        c = gpu_demodulate(rs, raw, g) if self.demod else raw
+        if self.svgf:
+            out, _, a, n, m = gpu_svgf(rs, c, g, self.hist, self.jview, self.tp, self.sp)
+            self.hist = (a, g, n, m)
+            want = self.ref.frame(raw if self.demod else c, g, self.jview)
+            want_final, want_n = want[0], want[2]
+        else:
+            out, n = gpu_temporal(rs, c, g, self.hist, self.jview, self.tp)
+            self.hist = (out, g, n)
+            if self.demod:
+                want_final, want_n = self.ref.frame(raw, g, self.jview)
+            else:
+                pc, pg, pl = self.ref_hist if self.ref_hist else (None, None, None)
+                want_final, want_n = T.accumulate(c, g, pc, pg, pl, self.jview if pc is not None
+                                                  else None, self.tp)
+                self.ref_hist = (want_final, g, want_n)
+        final = gpu_remodulate(rs, out, g)[0] if self.demod else out
+        assert_same(final, want_final, "the chain's final colour vs restatement")
+        assert np.array_equal(n, want_n)
+        self.jview = abi.temporal_view(jp, w, h)        # the chain's own history always reprojects
+        view = abi.temporal_view(push, W, H)
+        # the output-size G-buffer only when the 64 camera bytes differ from the previous frame's
+        moved = self.res is not None and push["camera"].tobytes() != self.push["camera"].tobytes()
+        g_hi = gpu_gbuffer(rs, push, W, H) if moved else None
+        pr, pw = (self.res, self.wt) if self.res is not None else (None, None)
+        res, wt, rgba = gpu_upsample(rs, final, s, self.jview, view, self.view if moved else None,
+                                     g_hi, pr, pw, None)
+        assert self.ref_up.moved(push) == moved
+        want_res, want_wt = self.ref_up.step(final, self.jview, push, g_hi)
+        assert_same(res, want_res, "the upsampling step vs restatement")
+        assert_same(wt, want_wt, "its weights vs restatement")
+        assert np.array_equal(rgba, R.gamma_rgba(want_res))
+        self.res, self.wt, self.push, self.view = res, wt, push, view
+        self.counter += 1
+        return res, rgba, n
+
+
+@pytest.mark.parametrize("demod", [False, True], ids=["colour", "demodulated"])
+@pytest.mark.parametrize("svgf", [False, True], ids=["temporal", "svgf"])
+def test_chains_with_the_scale_equal_the_stateless_composition(pair, cornell, svgf, demod):
+    rt = pair["rt"]
+    comp = UpComposition(pair["rs"], pair["table"], svgf, demod, CS)
+    pushes = chain_pushes()
+    rt.demodulation = demod
+    rt.taa_upsample = CS
+    try:
+        rt.temporal_reset()
+        rt.svgf_reset()
+
+        def same(push, what, W=CW, H=CH):
+            lin, rgba, n = chain_frame(rt, svgf, push, W, H)
+            want, want_rgba, want_n = comp.frame(push, W, H)
+            assert lin.shape == (H, W, 3) and rgba.shape == (H, W, 4), what
+            assert n.shape == (H // comp.scale, W // comp.scale), what     # the traced size
+            assert_same(lin, want, what)
+            assert np.array_equal(rgba, want_rgba) and np.array_equal(n, want_n), what
+            return lin, n
+
+        for i, push in enumerate(pushes):
+            lin, n = same(push, f"frame {i}")
+        assert (n >= 4).any()                             # histories survive the moves
+        assert comp.counter == 5 and lin.min() >= 0.0 and lin.max() <= 1.0
+        assert comp.wt.max() > 0.2                        # ... and so do the weights
+        # the restarts: rvcp_taa_reset keeps the chain's own history, the others drop both
+        rt.taa_reset()
+        comp.taa_restart()
+        _, n = same(pushes[4], "after taa_reset")
+        assert n.max() >= 5
+        (rt.svgf_reset if svgf else rt.temporal_reset)()
+        comp.restart()
+        _, n = same(pushes[4], "after the chain's reset")
+        assert n.max() == 1
+        same(pushes[4], "second frame after the reset")
+        comp.restart()
+        same(pushes[4], "a size change", CW - 4, CH)
+        same(pushes[4], "second frame at the new size", CW - 4, CH)
+        rt.upload_scene(cornell)
+        comp.restart()
+        same(pushes[0], "after an upload")
+        same(pushes[0], "second frame after the upload")
+        rt.taa_upsample = CS                               # the value it has: nothing happens
+        _, n = same(pushes[0], "third frame, the scale set again")
+        assert n.max() == 3
+        rt.taa_upsample = 3                                # changed: both histories are dropped
+        comp = UpComposition(pair["rs"], pair["table"], svgf, demod, 3)
+        _, n = same(pushes[0], "after changing the scale")
+        assert n.max() == 1
+        same(pushes[2], "a move at scale 3")
+    finally:
+        rt.taa_upsample = 1
+        rt.demodulation = False
+
+
+def test_the_scale_replaces_the_taa_resolve(pair):
+    """With the scale above 1 the frames are the same bytes whatever rvcp_set_taa says."""
+    rt = pair["rt"]
+    pushes = chain_pushes()
+    frames = {}
+    try:
+        for taa in (False, True):
+            rt.taa_upsample = 1
+            rt.taa = taa
+            rt.taa_upsample = CS
+            frames[taa] = [rt.render_svgf_push(p, CW, CH, want_linear=True) for p in pushes[1:4]]
+    finally:
+        rt.taa_upsample = 1
+        rt.taa = False
+    for (a_rgba, a_lin), (b_rgba, b_lin) in zip(frames[False], frames[True]):
+        assert a_rgba.tobytes() == b_rgba.tobytes() and a_lin.tobytes() == b_lin.tobytes()
+
+
+def test_scale_1_equals_a_context_that_never_heard_of_upsampling(pair, cornell):
+    """Every byte of every output of the three chains and of the plain render, after the scale
+    has been 2 and 1 again, against a fresh context -- with the TAA switch off and on."""
+    rt = pair["rt"]
+    pushes = chain_pushes()
+    rt.taa_upsample = 2
+    rt.render_temporal_push(pushes[0], CW, CH)
+    rt.render_svgf_push(pushes[2], CW, CH)
+    rt.taa_upsample = 1
+    dp = abi.make_denoise_params()
+
+    def everything(t):
+        out = []
+        for taa in (False, True):
+            t.taa = taa
+            for push in pushes[1:4]:
+                out += list(t.render_temporal_push(push, CW, CH, None, dp, want_linear=True,
+                                                   want_history=True))
+                out += list(t.render_temporal_push(push, CW, CH, want_linear=True, want_history=True))
+                out += list(t.render_svgf_push(push, CW, CH, want_linear=True, want_variance=True,
+                                               want_history=True))
+                out += list(t.render_push(push, CW, CH, want_linear=True))
+        t.taa = False
+        return out
+
+    with rvcp_amd.RayTracer(spp=2) as fresh:
+        fresh.upload_scene(cornell)
+        want = everything(fresh)
+    got = everything(rt)
+    assert len(got) == len(want)
+    for k, (a, b) in enumerate(zip(got, want)):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), k
+
+
+# ---------------------------------------------------------------------------- 4. quality
+def path_gate_measure(cornell):
+    """RMSEs against box4 of the clamped plain render at 512 x 512, SPP 128, after 16 frames of
+    rvcp_render_svgf at SPP 4 (time seeds 5.0 + i): `on` at output 128 x 128, scale 2; `comp` at
+    64 x 64 with both switches off, upscaled by the restatement's wide tent; `full` at 128 x 128
+    with TAA on and scale 1 (reported only).  A dict of (all-pixel rmse, edge rmse) and n_edge."""
+    W = H = 128
+    s = 2
+    base = np.ascontiguousarray(cornell.push_constant(0.0)).reshape(())
+    with rvcp_amd.RayTracer(spp=128) as hi:
+        hi.upload_scene(cornell)
+        truth = A.box4(A.sat(hi.render(4 * W, 4 * H, 77.0, want_linear=True)[1]))
+        g_hi = gpu_gbuffer(hi, cornell.push_constant(0.0), 4 * W, 4 * H)
+    edge = A.edge_pixels(g_hi["face"])
+    out = dict(n_edge=int(edge.sum()))
+    with rvcp_amd.RayTracer(spp=4) as rt:
+        rt.upload_scene(cornell)
+        for name, scale, taa, size in (("comp", 1, False, W // s), ("on", s, False, W),
+                                       ("full", 1, True, W)):
+            rt.taa_upsample = scale
+            rt.taa = taa
+            for i in range(U.GATE_FRAMES):
+                lin = rt.render_svgf(size, size, 5.0 + i, want_linear=True)[1]
+            if name == "comp":
+                lin = U.wide_tent(lin, s, base)
+            out[name] = (U.rmse(A.sat(lin), truth), U.rmse(A.sat(lin), truth, edge))
+    return out
+
+
+def test_path_traced_gate_render_svgf_128sq_from_64sq(cornell):
+    """Scale 2 against the wide-tent upscaling of the plain 64 x 64 chain (the same rays): the
+    all-pixel and the edge RMSE to the supersampled truth must each fall to PATH_MEASURED's ratio
+    plus a quarter of the distance to 1.  The 128 x 128 chain with TAA at four times the rays is
+    reported, not asserted."""
+    r = path_gate_measure(cornell)
+    print(f"\nTAAU path-traced gate: {r['n_edge']} edge pixels of {128 * 128}; (all, edge) rmse: "
+          f"comparator {r['comp'][0]:.4f} {r['comp'][1]:.4f}, scale 2 {r['on'][0]:.4f} "
+          f"{r['on'][1]:.4f}, TAA at full size {r['full'][0]:.4f} {r['full'][1]:.4f}; ratios "
+          f"{r['on'][0] / r['comp'][0]:.4f} {r['on'][1] / r['comp'][1]:.4f}")
+    m_all_c, m_all_on, m_edge_c, m_edge_on = U.PATH_MEASURED
+    assert r["n_edge"] >= 1000
+    assert r["on"][0] / r["comp"][0] <= A.gate(m_all_on / m_all_c)
+    assert r["on"][1] / r["comp"][1] <= A.gate(m_edge_on / m_edge_c)
