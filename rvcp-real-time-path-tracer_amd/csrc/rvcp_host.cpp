@@ -21,6 +21,7 @@
 #include <cstring>
 #include <memory>
 #include <exception>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <string>
@@ -58,6 +59,62 @@ static bool jit_spec_prepass()
 // "forever", which is what a blocking ncclCommInitRank or an unbounded event wait gives when a
 // peer never arrives
 constexpr uint32_t kDefaultCommTimeoutMs = 60000;
+
+// One post-process step's bracket on its stream: ev0 / ev1 are recorded around the work of the
+// step's last call (each created on first use).  recorded: ev1 has been recorded at least once
+// (steps are ordered behind it, rvcp_destroy synchronises it); pending: ... and not yet waited for.
+struct Stage {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool recorded = false, pending = false;
+};
+
+enum StageId {
+    ST_DENOISE, ST_TEMPORAL, ST_SVGF_ACC, ST_SVGF_FLT, ST_DEMOD, ST_REMOD, ST_TAA, ST_TAAU, N_STAGES
+};
+
+constexpr uint32_t stage_bit(StageId id) { return 1u << id; }
+
+// The steps each step is ordered behind, besides a render pending on another stream: the denoiser,
+// the temporal step, the TAA resolve and the upsampling step reuse what their own previous call
+// wrote (intermediates, or the history); the SVGF and the albedo steps share buffers from call to
+// call, so each waits for the context's previous SVGF accumulation and filter.  (In StageId order.)
+constexpr uint32_t kSvgfSteps = stage_bit(ST_SVGF_ACC) | stage_bit(ST_SVGF_FLT);
+constexpr uint32_t kStageBehind[N_STAGES] = {
+    stage_bit(ST_DENOISE), stage_bit(ST_TEMPORAL), kSvgfSteps, kSvgfSteps, kSvgfSteps, kSvgfSteps,
+    stage_bit(ST_TAA), stage_bit(ST_TAAU)};
+
+// A history a stateful chain keeps from call to call, ping-ponging between slots `slot` (the
+// previous frame) and slot ^ 1
+struct History {
+    uint32_t slot = 0, width = 0, height = 0;
+    bool valid = false;                 // slot `slot` holds a frame of width x height
+    rvcp_camera_t camera = {};          // ... rendered from this camera
+    rvcp_temporal_view_t view = {};     // ... whose projection (at width x height) this is
+
+    bool continues_at(uint32_t w, uint32_t h) const { return valid && width == w && height == h; }
+    void commit(uint32_t w, uint32_t h, const rvcp_camera_t &c, const rvcp_temporal_view_t &v)
+    {
+        slot ^= 1u;
+        width = w;
+        height = h;
+        camera = c;
+        view = v;
+        valid = true;
+    }
+};
+
+// What a stateful chain keeps for the step that ends its frames with the TAA switch set (the
+// resolve) or the upsampling scale above 1 (§4.14): the resolved colour and a
+// 4-byte plane (the resolve's history lengths, the upsampling's weights) under the unjittered
+// camera, and for the upsampling the output-size G-buffer of a frame whose camera moved
+struct ResolveState {
+    History hist;
+    float *d_res[2] = {nullptr, nullptr};
+    void *d_aux[2] = {nullptr, nullptr};
+    void *d_gbuf = nullptr;
+    size_t cap = 0;
+    uint32_t counter = 0;               // the next frame's index into the jitter sequence
+};
 
 
 struct rvcp_ctx {
@@ -128,44 +185,34 @@ struct rvcp_ctx {
     float *d_pack_lin = nullptr;
     size_t cap_surf_pack = 0;
 
+    // the event brackets of the post-process steps (rvcp_*_async / rvcp_*_wait), by StageId
+    Stage stage[N_STAGES];
+
     // denoiser (rvcp_denoise_async): the passes between the first and the last ping-pong
-    // between d_dn[0] and d_dn[1]; evd0 / evd1 bracket the last filter on its stream (created
-    // by the first call).  rvcp_render_denoised keeps its G-buffer and linear frames here too.
+    // between d_dn[0] and d_dn[1].  rvcp_render_denoised keeps its G-buffer and linear frames
+    // here too.
     float *d_dn[2] = {nullptr, nullptr};
     size_t cap_dn[2] = {0, 0};
-    hipEvent_t evd0 = nullptr, evd1 = nullptr;
-    bool denoise_recorded = false;      // evd1 has been recorded at least once
-    bool denoise_pending = false;       // ... and not yet waited for with rvcp_denoise_wait
     void *d_gbuf = nullptr;
     float *d_dn_in = nullptr, *d_dn_out = nullptr;
     size_t cap_gbuf = 0, cap_dn_io = 0;
 
-    // temporal accumulation (rvcp_temporal_accumulate_async): evt0 / evt1 bracket the last step
-    // on its stream (created by the first call).  rvcp_render_temporal keeps its history here:
-    // accumulated colour, history length and G-buffer ping-pong between slots tp_slot (the
-    // previous frame) and tp_slot ^ 1; d_tp_cur is the raw frame, d_tp_show the filtered one.
-    hipEvent_t evt0 = nullptr, evt1 = nullptr;
-    bool temporal_recorded = false;     // evt1 has been recorded at least once
-    bool temporal_pending = false;      // ... and not yet waited for with rvcp_temporal_wait
+    // rvcp_render_temporal keeps its history here: accumulated colour, history length and
+    // G-buffer ping-pong between the slots of tp_hist; d_tp_cur is the raw frame, d_tp_show the
+    // filtered one.
     float *d_tp_lin[2] = {nullptr, nullptr};
     uint32_t *d_tp_len[2] = {nullptr, nullptr};
     void *d_tp_gbuf[2] = {nullptr, nullptr};
     float *d_tp_cur = nullptr, *d_tp_show = nullptr;
     size_t cap_tp = 0, cap_tp_show = 0;
-    uint32_t tp_slot = 0, tp_width = 0, tp_height = 0;
-    bool tp_valid = false;              // slot tp_slot holds a frame of tp_width x tp_height
-    rvcp_camera_t tp_camera = {};       // ... rendered from this camera
-    rvcp_temporal_view_t tp_view = {};  // ... whose projection this is
+    History tp_hist;
 
-    // SVGF (rvcp_svgf_accumulate_async / rvcp_svgf_filter_async): an event pair
-    // per step; the filter's variance planes (d_sv_var: the estimate and the passes' ping-pong)
-    // and colour intermediates.  rvcp_render_svgf keeps a history of its own, apart from
-    // rvcp_render_temporal's: colour, moments, length and G-buffer ping-pong between slots
-    // sv_slot (the previous frame) and sv_slot ^ 1; d_sv_cur is the raw frame, d_sv_show and
-    // d_sv_showvar the filtered one and its variance, d_sv_fb pass 0's colour (feedback).
-    hipEvent_t evsa0 = nullptr, evsa1 = nullptr, evsf0 = nullptr, evsf1 = nullptr;
-    bool svgf_acc_recorded = false, svgf_acc_pending = false;
-    bool svgf_flt_recorded = false, svgf_flt_pending = false;
+    // SVGF (rvcp_svgf_accumulate_async / rvcp_svgf_filter_async): the filter's
+    // variance planes (d_sv_var: the estimate and the passes' ping-pong) and colour intermediates.
+    // rvcp_render_svgf keeps a history of its own, apart from rvcp_render_temporal's: colour,
+    // moments, length and G-buffer ping-pong between the slots of sv_hist; d_sv_cur is the raw
+    // frame, d_sv_show and d_sv_showvar the filtered one and its variance, d_sv_fb pass 0's colour
+    // (feedback).
     float *d_sv_var[2] = {nullptr, nullptr}, *d_sv_tmp[2] = {nullptr, nullptr};
     size_t cap_sv_var[2] = {0, 0}, cap_sv_tmp[2] = {0, 0};
     float *d_sv_lin[2] = {nullptr, nullptr}, *d_sv_mom[2] = {nullptr, nullptr};
@@ -173,56 +220,22 @@ struct rvcp_ctx {
     void *d_sv_gbuf[2] = {nullptr, nullptr};
     float *d_sv_cur = nullptr, *d_sv_show = nullptr, *d_sv_showvar = nullptr, *d_sv_fb = nullptr;
     size_t cap_sv = 0;
-    uint32_t sv_slot = 0, sv_width = 0, sv_height = 0;
-    bool sv_valid = false;              // slot sv_slot holds a frame of sv_width x sv_height
-    rvcp_camera_t sv_camera = {};       // ... rendered from this camera
-    rvcp_temporal_view_t sv_view = {};  // ... whose projection this is
+    History sv_hist;
 
     // albedo demodulation (rvcp_demodulate_async / rvcp_remodulate_async): the
-    // scene's albedo table (one float4 per material, made by every upload), an event pair per
-    // step, and the switch of rvcp_set_demodulation: while it is set rvcp_render_denoised,
-    // rvcp_render_temporal and rvcp_render_svgf filter irradiance
+    // scene's albedo table (one float4 per material, made by every upload) and the switch of
+    // rvcp_set_demodulation: while it is set rvcp_render_denoised, rvcp_render_temporal and
+    // rvcp_render_svgf filter irradiance
     float *d_albedo = nullptr;
-    hipEvent_t evad0 = nullptr, evad1 = nullptr, evar0 = nullptr, evar1 = nullptr;
-    bool demod_recorded = false, demod_pending = false;
-    bool remod_recorded = false, remod_pending = false;
     bool demodulation = false;
 
-    // temporal anti-aliasing (rvcp_taa_resolve_async): an event pair for the
-    // step, the switch of rvcp_set_taa, and one TAA state per stateful chain: the resolved colour
-    // and its lengths ping-pong between slots `slot` (the previous frame) and slot ^ 1
-    hipEvent_t evta0 = nullptr, evta1 = nullptr;
-    bool taa_recorded = false, taa_pending = false;
+    // temporal anti-aliasing and temporal upsampling (§4.14): the switch of
+    // rvcp_set_taa, the scale of rvcp_set_taa_upsample (1: off), and for each of the two one
+    // state per stateful chain (of rvcp_render_temporal / rvcp_render_svgf); the upsampling's is
+    // at the OUTPUT size
     bool taa = false;
-    struct TaaState {
-        float *d_res[2] = {nullptr, nullptr};
-        uint32_t *d_len[2] = {nullptr, nullptr};
-        size_t cap = 0;
-        uint32_t slot = 0, width = 0, height = 0;
-        bool valid = false;                 // slot `slot` holds a resolved frame of width x height
-        rvcp_camera_t camera = {};          // ... under this unjittered camera
-        rvcp_temporal_view_t view = {};     // ... whose projection this is
-        uint32_t counter = 0;               // the next frame's index into the jitter sequence
-    } taa_tp, taa_sv;                       // of rvcp_render_temporal / rvcp_render_svgf
-
-    // temporal upsampling (rvcp_taa_upsample_async): an event pair for the step,
-    // the scale of rvcp_set_taa_upsample (1: off) and one state per stateful chain: the resolved
-    // colour and its weights at the OUTPUT size ping-pong between slots `slot` (the previous
-    // frame) and slot ^ 1; d_gbuf is the output-size G-buffer of a frame whose camera moved
-    hipEvent_t evtu0 = nullptr, evtu1 = nullptr;
-    bool taau_recorded = false, taau_pending = false;
     uint32_t taau_scale = 1;
-    struct TaauState {
-        float *d_res[2] = {nullptr, nullptr};
-        float *d_wt[2] = {nullptr, nullptr};
-        void *d_gbuf = nullptr;
-        size_t cap = 0;
-        uint32_t slot = 0, width = 0, height = 0;
-        bool valid = false;                 // slot `slot` holds a resolved frame of width x height
-        rvcp_camera_t camera = {};          // ... under this unjittered camera
-        rvcp_temporal_view_t view = {};     // ... whose projection (at width x height) this is
-        uint32_t counter = 0;               // the next frame's index into the jitter sequence
-    } taau_tp, taau_sv;                     // of rvcp_render_temporal / rvcp_render_svgf
+    ResolveState taa_tp, taa_sv, taau_tp, taau_sv;
 
     // debug build: per-wave timeline of the path kernel appended per render
     unsigned long long *d_timeline = nullptr;
@@ -425,6 +438,100 @@ void free_scene(rvcp_ctx *ctx)
     (void)hipFree(ctx->d_bvh_tris); ctx->d_bvh_tris = nullptr;
     ctx->jit.reset();
     ctx->has_scene = false;
+}
+
+// The buffer groups of the stateful chains.  Each has one function that frees it and one that
+// makes it hold npx pixels: a larger frame drops the history with its buffers.
+template <typename T>
+void dev_free(T *&p)
+{
+    (void)hipFree(p);
+    p = nullptr;
+}
+
+void free_temporal_state(rvcp_ctx *ctx)
+{
+    for (int i = 0; i < 2; ++i) {
+        dev_free(ctx->d_tp_lin[i]);
+        dev_free(ctx->d_tp_len[i]);
+        dev_free(ctx->d_tp_gbuf[i]);
+    }
+    dev_free(ctx->d_tp_cur);
+    ctx->cap_tp = 0;
+}
+
+int reserve_temporal_state(rvcp_ctx *ctx, size_t npx)
+{
+    if (ctx->cap_tp >= npx) return RVCP_OK;
+    ctx->tp_hist.valid = false;
+    free_temporal_state(ctx);
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_tp_lin[i], npx * 12));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_tp_len[i], npx * 4));
+        HIP_TRY(ctx, hipMalloc(&ctx->d_tp_gbuf[i], npx * sizeof(rvcp_gbuffer_texel_t)));
+    }
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_tp_cur, npx * 12));
+    ctx->cap_tp = npx;
+    return RVCP_OK;
+}
+
+void free_svgf_state(rvcp_ctx *ctx)
+{
+    for (int i = 0; i < 2; ++i) {
+        dev_free(ctx->d_sv_lin[i]);
+        dev_free(ctx->d_sv_mom[i]);
+        dev_free(ctx->d_sv_len[i]);
+        dev_free(ctx->d_sv_gbuf[i]);
+    }
+    dev_free(ctx->d_sv_cur);
+    dev_free(ctx->d_sv_show);
+    dev_free(ctx->d_sv_showvar);
+    dev_free(ctx->d_sv_fb);
+    ctx->cap_sv = 0;
+}
+
+int reserve_svgf_state(rvcp_ctx *ctx, size_t npx)
+{
+    if (ctx->cap_sv >= npx) return RVCP_OK;
+    ctx->sv_hist.valid = false;
+    free_svgf_state(ctx);
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_lin[i], npx * 12));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_mom[i], npx * 8));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_len[i], npx * 4));
+        HIP_TRY(ctx, hipMalloc(&ctx->d_sv_gbuf[i], npx * sizeof(rvcp_gbuffer_texel_t)));
+    }
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_cur, npx * 12));
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_show, npx * 12));
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_showvar, npx * 4));
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_fb, npx * 12));
+    ctx->cap_sv = npx;
+    return RVCP_OK;
+}
+
+void free_resolve_state(ResolveState &st)
+{
+    for (int i = 0; i < 2; ++i) {
+        dev_free(st.d_res[i]);
+        dev_free(st.d_aux[i]);
+    }
+    dev_free(st.d_gbuf);
+    st.cap = 0;
+}
+
+// (with_gbuf: the upsampling's output-size G-buffer)
+int reserve_resolve_state(rvcp_ctx *ctx, ResolveState &st, size_t npx, bool with_gbuf)
+{
+    if (st.cap >= npx) return RVCP_OK;
+    st.hist.valid = false;
+    free_resolve_state(st);
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(ctx, hipMalloc((void **)&st.d_res[i], npx * 12));
+        HIP_TRY(ctx, hipMalloc(&st.d_aux[i], npx * 4));
+    }
+    if (with_gbuf) HIP_TRY(ctx, hipMalloc(&st.d_gbuf, npx * sizeof(rvcp_gbuffer_texel_t)));
+    st.cap = npx;
+    return RVCP_OK;
 }
 
 }  // namespace
@@ -673,14 +780,8 @@ static int impl_destroy(rvcp_ctx_t *ctx)
         return RVCP_E_TIMEOUT;
     }
     // a filter still in flight (possibly on the caller's stream) reads the buffers freed below
-    if (ctx->denoise_recorded) (void)hipEventSynchronize(ctx->evd1);
-    if (ctx->temporal_recorded) (void)hipEventSynchronize(ctx->evt1);
-    if (ctx->svgf_acc_recorded) (void)hipEventSynchronize(ctx->evsa1);
-    if (ctx->svgf_flt_recorded) (void)hipEventSynchronize(ctx->evsf1);
-    if (ctx->demod_recorded) (void)hipEventSynchronize(ctx->evad1);
-    if (ctx->remod_recorded) (void)hipEventSynchronize(ctx->evar1);
-    if (ctx->taa_recorded) (void)hipEventSynchronize(ctx->evta1);
-    if (ctx->taau_recorded) (void)hipEventSynchronize(ctx->evtu1);
+    for (const Stage &st : ctx->stage)
+        if (st.recorded) (void)hipEventSynchronize(st.ev1);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm && ctx->comm_owned) (void)rccl_api().comm_destroy(ctx->comm);
     ctx->comm = nullptr;
@@ -704,49 +805,19 @@ static int impl_destroy(rvcp_ctx_t *ctx)
     (void)hipFree(ctx->d_gbuf);
     (void)hipFree(ctx->d_dn_in);
     (void)hipFree(ctx->d_dn_out);
-    for (int i = 0; i < 2; ++i) {
-        (void)hipFree(ctx->d_tp_lin[i]);
-        (void)hipFree(ctx->d_tp_len[i]);
-        (void)hipFree(ctx->d_tp_gbuf[i]);
-    }
-    (void)hipFree(ctx->d_tp_cur);
+    free_temporal_state(ctx);
     (void)hipFree(ctx->d_tp_show);
     for (int i = 0; i < 2; ++i) {
         (void)hipFree(ctx->d_sv_var[i]);
         (void)hipFree(ctx->d_sv_tmp[i]);
-        (void)hipFree(ctx->d_sv_lin[i]);
-        (void)hipFree(ctx->d_sv_mom[i]);
-        (void)hipFree(ctx->d_sv_len[i]);
-        (void)hipFree(ctx->d_sv_gbuf[i]);
     }
-    (void)hipFree(ctx->d_sv_cur);
-    (void)hipFree(ctx->d_sv_show);
-    (void)hipFree(ctx->d_sv_showvar);
-    (void)hipFree(ctx->d_sv_fb);
-    for (rvcp_ctx::TaaState *st : {&ctx->taa_tp, &ctx->taa_sv})
-        for (int i = 0; i < 2; ++i) {
-            (void)hipFree(st->d_res[i]);
-            (void)hipFree(st->d_len[i]);
-        }
-    for (rvcp_ctx::TaauState *st : {&ctx->taau_tp, &ctx->taau_sv}) {
-        for (int i = 0; i < 2; ++i) {
-            (void)hipFree(st->d_res[i]);
-            (void)hipFree(st->d_wt[i]);
-        }
-        (void)hipFree(st->d_gbuf);
+    free_svgf_state(ctx);
+    for (ResolveState *st : {&ctx->taa_tp, &ctx->taa_sv, &ctx->taau_tp, &ctx->taau_sv})
+        free_resolve_state(*st);
+    for (const Stage &st : ctx->stage) {
+        if (st.ev0) (void)hipEventDestroy(st.ev0);
+        if (st.ev1) (void)hipEventDestroy(st.ev1);
     }
-    if (ctx->evtu0) (void)hipEventDestroy(ctx->evtu0);
-    if (ctx->evtu1) (void)hipEventDestroy(ctx->evtu1);
-    if (ctx->evta0) (void)hipEventDestroy(ctx->evta0);
-    if (ctx->evta1) (void)hipEventDestroy(ctx->evta1);
-    for (hipEvent_t e : {ctx->evsa0, ctx->evsa1, ctx->evsf0, ctx->evsf1})
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {ctx->evad0, ctx->evad1, ctx->evar0, ctx->evar1})
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->evt0) (void)hipEventDestroy(ctx->evt0);
-    if (ctx->evt1) (void)hipEventDestroy(ctx->evt1);
-    if (ctx->evd0) (void)hipEventDestroy(ctx->evd0);
-    if (ctx->evd1) (void)hipEventDestroy(ctx->evd1);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->evm) (void)hipEventDestroy(ctx->evm);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -774,8 +845,8 @@ static int impl_upload_scene(rvcp_ctx_t *ctx, const rvcp_material_t *materials, 
                       const uint32_t *lum_sphere_ids, uint32_t n_lum_sphere_ids)
 {
     if (!ctx) return RVCP_E_INVALID;
-    ctx->tp_valid = false;      // rvcp_render_temporal: another scene, no history
-    ctx->sv_valid = false;      // rvcp_render_svgf likewise
+    ctx->tp_hist.valid = false;     // rvcp_render_temporal: another scene, no history
+    ctx->sv_hist.valid = false;     // rvcp_render_svgf likewise
     int rc = upload_one(ctx, materials, n_materials, vertices, n_vertices, faces, n_faces,
                         spheres, n_spheres, lum_face_ids, n_lum_face_ids, lum_sphere_ids,
                         n_lum_sphere_ids);
@@ -1500,6 +1571,119 @@ static int impl_mandelbrot(rvcp_ctx_t *ctx, const rvcp_mandelbrot_push_t *push, 
     return RVCP_OK;
 }
 
+// ---- what the post-process steps share --------------------------------------------------
+
+// Opens step `id` on stream s: its events exist, s waits for a render pending on this context
+// (when it runs on another stream) and for the steps of kStageBehind[id], and the start event is
+// recorded.  Each event is created if it is missing, so a creation that failed is tried again.
+static int stage_begin(rvcp_ctx_t *ctx, StageId id, hipStream_t s)
+{
+    Stage &st = ctx->stage[id];
+    if (!st.ev0) HIP_TRY(ctx, hipEventCreate(&st.ev0));
+    if (!st.ev1) HIP_TRY(ctx, hipEventCreate(&st.ev1));
+    if (ctx->pending && ctx->render_stream != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev1, 0));
+    for (int k = 0; k < N_STAGES; ++k)
+        if ((kStageBehind[id] >> k & 1u) && ctx->stage[k].recorded)
+            HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->stage[k].ev1, 0));
+    HIP_TRY(ctx, hipEventRecord(st.ev0, s));
+    return RVCP_OK;
+}
+
+static int stage_end(rvcp_ctx_t *ctx, StageId id, hipStream_t s)
+{
+    Stage &st = ctx->stage[id];
+    HIP_TRY(ctx, hipEventRecord(st.ev1, s));
+    st.recorded = true;
+    st.pending = true;
+    return RVCP_OK;
+}
+
+static int stage_sync(rvcp_ctx_t *ctx, StageId id, float *ms)
+{
+    Stage &st = ctx->stage[id];
+    HIP_TRY(ctx, hipEventSynchronize(st.ev1));
+    if (ms) HIP_TRY(ctx, hipEventElapsedTime(ms, st.ev0, st.ev1));
+    st.pending = false;
+    return RVCP_OK;
+}
+
+// rvcp_*_wait of one step; `none` is its "no ... in flight" text
+static int stage_wait(rvcp_ctx_t *ctx, StageId id, const char *none, float *ms)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!ctx->stage[id].pending) return fail(ctx, RVCP_E_INVALID, none);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return stage_sync(ctx, id, ms);
+}
+
+// ... and of a pair of steps: whichever of the two are pending (0 ms for the other)
+static int stage_wait2(rvcp_ctx_t *ctx, StageId a, StageId b, const char *none, float *a_ms,
+                       float *b_ms)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!ctx->stage[a].pending && !ctx->stage[b].pending) return fail(ctx, RVCP_E_INVALID, none);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (a_ms) *a_ms = 0.0f;
+    if (b_ms) *b_ms = 0.0f;
+    int rc;
+    if (ctx->stage[a].pending && (rc = stage_sync(ctx, a, a_ms)) != RVCP_OK) return rc;
+    if (ctx->stage[b].pending && (rc = stage_sync(ctx, b, b_ms)) != RVCP_OK) return rc;
+    return RVCP_OK;
+}
+
+static int frame_size_checked(rvcp_ctx_t *ctx, uint32_t width, uint32_t height)
+{
+    if ((uint64_t)width * height >= (1ull << 31))
+        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    return RVCP_OK;
+}
+
+struct DevRange { const void *p; size_t n; };
+
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && x < y + nb && y < x + na;
+}
+
+// A lane of these steps reads its neighbours' pixels, and the frames are not the caller's to
+// lose: no output of `step` may overlap an input or another output (NULL ranges overlap nothing)
+static int overlap_checked(rvcp_ctx_t *ctx, const char *step, std::initializer_list<DevRange> in,
+                           std::initializer_list<DevRange> out)
+{
+    for (const DevRange *o = out.begin(); o != out.end(); ++o) {
+        for (const DevRange &i : in)
+            if (ranges_overlap(o->p, o->n, i.p, i.n))
+                return fail(ctx, RVCP_E_INVALID, std::string(step) + " output overlaps an input");
+        for (const DevRange *q = o + 1; q != out.end(); ++q)
+            if (ranges_overlap(o->p, o->n, q->p, q->n))
+                return fail(ctx, RVCP_E_INVALID, std::string(step) + " outputs overlap each other");
+    }
+    return RVCP_OK;
+}
+
+// the optional last launch of a step: its linear output as gamma / UNORM8 bytes
+static int tonemap_tail(rvcp_ctx_t *ctx, const char *step, const void *d_lin, size_t npx,
+                        void *d_rgba8_out, hipStream_t s)
+{
+    if (d_rgba8_out &&
+        rvcp_launch_tonemap((const float *)d_lin, (uint32_t)npx, ctx->d_gamma,
+                            (uint32_t *)d_rgba8_out, s) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string(step) + " tone-map launch failed");
+    return RVCP_OK;
+}
+
+static int grow(rvcp_ctx_t *ctx, void **buf, size_t *cap, size_t n, size_t elem)
+{
+    if (*cap >= n) return RVCP_OK;
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    HIP_TRY(ctx, hipMalloc(buf, n * elem));
+    *cap = n;
+    return RVCP_OK;
+}
+
 // ---- G-buffer and denoiser ---------------------------------------------
 
 static int impl_render_gbuffer_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push,
@@ -1508,8 +1692,8 @@ static int impl_render_gbuffer_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t
     if (!ctx) return RVCP_E_INVALID;
     if (!push || !d_gbuffer || width == 0 || height == 0)
         return fail(ctx, RVCP_E_INVALID, "invalid G-buffer arguments");
-    if ((uint64_t)width * height >= (1ull << 31))
-        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    int rc;
+    if ((rc = frame_size_checked(ctx, width, height)) != RVCP_OK) return rc;
     if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
         return fail(ctx, RVCP_E_UNSUPPORTED, "the G-buffer is implemented for the games101 integrator");
     if (!ctx->subs.empty())
@@ -1560,17 +1744,6 @@ static float denoise_color_s2(float sigma_color, uint32_t i)
     return sig * sig;
 }
 
-static int grow(rvcp_ctx_t *ctx, void **buf, size_t *cap, size_t n, size_t elem)
-{
-    if (*cap >= n) return RVCP_OK;
-    (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    HIP_TRY(ctx, hipMalloc(buf, n * elem));
-    *cap = n;
-    return RVCP_OK;
-}
-
 static int impl_denoise_async(rvcp_ctx_t *ctx, const void *d_in, const void *d_gbuffer,
                               uint32_t width, uint32_t height, const rvcp_denoise_params_t *params,
                               void *d_out, void *d_rgba8_out, void *stream)
@@ -1578,8 +1751,8 @@ static int impl_denoise_async(rvcp_ctx_t *ctx, const void *d_in, const void *d_g
     if (!ctx) return RVCP_E_INVALID;
     if (!d_in || !d_gbuffer || !d_out || width == 0 || height == 0)
         return fail(ctx, RVCP_E_INVALID, "invalid denoise arguments");
-    if ((uint64_t)width * height >= (1ull << 31))
-        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    int rc;
+    if ((rc = frame_size_checked(ctx, width, height)) != RVCP_OK) return rc;
     rvcp_denoise_params_t P;
     if (params) P = *params;
     else (void)impl_denoise_params_default(&P);
@@ -1595,26 +1768,16 @@ static int impl_denoise_async(rvcp_ctx_t *ctx, const void *d_in, const void *d_g
     if (use_color && !(denoise_color_s2(P.sigma_color, P.iterations - 1) >= FLT_MIN))
         return fail(ctx, RVCP_E_INVALID, "denoise sigma_color is too small (sigma_i^2 underflows)");
     const size_t npx = (size_t)width * height;
-    {   // the output must not overlap the input: a pass reads neighbours it would have overwritten
-        const uintptr_t a = (uintptr_t)d_in, b = (uintptr_t)d_out, n = npx * 12;
-        if (a < b + n && b < a + n)
-            return fail(ctx, RVCP_E_INVALID, "denoise output overlaps the input");
-    }
+    // the output must not overlap the input: a pass reads neighbours it would have overwritten
+    // (a text of its own, older than overlap_checked's)
+    if (ranges_overlap(d_out, npx * 12, d_in, npx * 12))
+        return fail(ctx, RVCP_E_INVALID, "denoise output overlaps the input");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    if (!ctx->evd0) {
-        HIP_TRY(ctx, hipEventCreate(&ctx->evd0));
-        HIP_TRY(ctx, hipEventCreate(&ctx->evd1));
-    }
     // intermediates: none for one pass, one buffer for two, both from three passes on
-    int rc;
     for (uint32_t b = 0; b < 2 && b + 1 < P.iterations; ++b)
         if ((rc = grow(ctx, (void **)&ctx->d_dn[b], &ctx->cap_dn[b], npx, 12)) != RVCP_OK) return rc;
-    // behind a render pending on this context (when it runs on another stream), and behind the
-    // context's previous filter, which used the same intermediates
-    if (ctx->pending && ctx->render_stream != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev1, 0));
-    if (ctx->denoise_recorded) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evd1, 0));
-    HIP_TRY(ctx, hipEventRecord(ctx->evd0, s));
+    if ((rc = stage_begin(ctx, ST_DENOISE, s)) != RVCP_OK) return rc;
     const float *src = (const float *)d_in;
     for (uint32_t i = 0; i < P.iterations; ++i) {
         float *dst = i + 1 == P.iterations ? (float *)d_out : ctx->d_dn[i & 1u];
@@ -1626,108 +1789,13 @@ static int impl_denoise_async(rvcp_ctx_t *ctx, const void *d_in, const void *d_g
                                              hipGetErrorString(hipGetLastError()));
         src = dst;
     }
-    if (d_rgba8_out &&
-        rvcp_launch_tonemap((const float *)d_out, (uint32_t)npx, ctx->d_gamma,
-                            (uint32_t *)d_rgba8_out, s) != 0)
-        return fail(ctx, RVCP_E_HIP, "denoise tone-map launch failed");
-    HIP_TRY(ctx, hipEventRecord(ctx->evd1, s));
-    ctx->denoise_recorded = true;
-    ctx->denoise_pending = true;
-    return RVCP_OK;
+    if ((rc = tonemap_tail(ctx, "denoise", d_out, npx, d_rgba8_out, s)) != RVCP_OK) return rc;
+    return stage_end(ctx, ST_DENOISE, s);
 }
 
 static int impl_denoise_wait(rvcp_ctx_t *ctx, float *denoise_ms)
 {
-    if (!ctx) return RVCP_E_INVALID;
-    if (!ctx->denoise_pending) return fail(ctx, RVCP_E_INVALID, "no denoise in flight");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->evd1));
-    if (denoise_ms) HIP_TRY(ctx, hipEventElapsedTime(denoise_ms, ctx->evd0, ctx->evd1));
-    ctx->denoise_pending = false;
-    return RVCP_OK;
-}
-
-// albedo demodulation (defined below, behind the SVGF steps they are ordered by)
-static int impl_demodulate_async(rvcp_ctx_t *ctx, const void *d_lin, const void *d_gbuffer,
-                                 uint32_t width, uint32_t height, void *d_out, void *stream);
-static int impl_remodulate_async(rvcp_ctx_t *ctx, const void *d_irr, const void *d_gbuffer,
-                                 uint32_t width, uint32_t height, void *d_lin_out,
-                                 void *d_rgba8_out, void *stream);
-static int impl_albedo_wait(rvcp_ctx_t *ctx, float *demodulate_ms, float *remodulate_ms);
-
-// the albedo steps a chain enqueued, waited for after a failure or at its end
-static void albedo_drain(rvcp_ctx_t *ctx)
-{
-    if (ctx->demod_pending || ctx->remod_pending) (void)impl_albedo_wait(ctx, nullptr, nullptr);
-}
-
-static int impl_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
-                                uint32_t height, const rvcp_denoise_params_t *params,
-                                uint8_t *out_rgba8, float *out_linear_rgb, rvcp_stats_t *stats,
-                                float *denoise_ms)
-{
-    if (!ctx) return RVCP_E_INVALID;
-    if (!push || !out_rgba8 || width == 0 || height == 0 ||
-        (uint64_t)width * height >= (1ull << 31))
-        return fail(ctx, RVCP_E_INVALID, "invalid render_denoised arguments");
-    if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
-        return fail(ctx, RVCP_E_UNSUPPORTED, "the G-buffer is implemented for the games101 integrator");
-    if (!ctx->subs.empty())
-        return fail(ctx, RVCP_E_UNSUPPORTED, "render_denoised drives one GPU (n_gpus = 1)");
-    if (ctx->pending)
-        return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t npx = (size_t)width * height;
-    int rc;
-    if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, npx, 4)) != RVCP_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_gbuf, &ctx->cap_gbuf, npx, sizeof(rvcp_gbuffer_texel_t))) != RVCP_OK)
-        return rc;
-    if (ctx->cap_dn_io < npx) {
-        (void)hipFree(ctx->d_dn_in);
-        (void)hipFree(ctx->d_dn_out);
-        ctx->d_dn_in = ctx->d_dn_out = nullptr;
-        ctx->cap_dn_io = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_dn_in, npx * 12));
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_dn_out, npx * 12));
-        ctx->cap_dn_io = npx;
-    }
-    // render (raw linear frame), G-buffer and filter, in this order on the context's stream; the
-    // filter's RGBA8 store overwrites the render's
-    if ((rc = rvcp_render_async(ctx, push, width, height, ctx->d_rgba, ctx->d_dn_in, ctx->stream)) != RVCP_OK)
-        return rc;
-    // With the demodulation switch set (§4.12): the raw frame is demodulated in place right after
-    // the G-buffer, the filter runs on irradiance without a store, and the fused remodulate +
-    // store writes the colour into d_dn_in (free by then) and the RGBA8 frame.
-    const bool demod = ctx->demodulation;
-    bool filter_enqueued = false;
-    rc = impl_render_gbuffer_async(ctx, push, width, height, ctx->d_gbuf, ctx->stream);
-    if (rc == RVCP_OK && demod)
-        rc = impl_demodulate_async(ctx, ctx->d_dn_in, ctx->d_gbuf, width, height, ctx->d_dn_in,
-                                   ctx->stream);
-    if (rc == RVCP_OK) {
-        rc = impl_denoise_async(ctx, ctx->d_dn_in, ctx->d_gbuf, width, height, params,
-                                ctx->d_dn_out, demod ? nullptr : ctx->d_rgba, ctx->stream);
-        filter_enqueued = rc == RVCP_OK;
-    }
-    if (rc == RVCP_OK && demod)
-        rc = impl_remodulate_async(ctx, ctx->d_dn_out, ctx->d_gbuf, width, height, ctx->d_dn_in,
-                                   ctx->d_rgba, ctx->stream);
-    if (rc != RVCP_OK) {
-        const std::string why = ctx->err;
-        (void)rvcp_wait(ctx, nullptr);          // the render is enqueued: leave no frame pending
-        if (filter_enqueued) (void)impl_denoise_wait(ctx, nullptr);
-        albedo_drain(ctx);
-        ctx->err = why;
-        return rc;
-    }
-    if ((rc = rvcp_wait(ctx, stats)) != RVCP_OK) return rc;
-    if ((rc = impl_denoise_wait(ctx, denoise_ms)) != RVCP_OK) return rc;
-    if (demod && (rc = impl_albedo_wait(ctx, nullptr, nullptr)) != RVCP_OK) return rc;
-    HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, npx * 4, hipMemcpyDeviceToHost));
-    if (out_linear_rgb)
-        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, demod ? ctx->d_dn_in : ctx->d_dn_out, npx * 12,
-                               hipMemcpyDeviceToHost));
-    return RVCP_OK;
+    return stage_wait(ctx, ST_DENOISE, "no denoise in flight", denoise_ms);
 }
 
 // ---- temporal reprojection and accumulation -----------------------------
@@ -1742,43 +1810,70 @@ static int impl_temporal_params_default(rvcp_temporal_params_t *params)
     return RVCP_OK;
 }
 
-// The camera of `push` as the kernel projects through it: the inverse of sample_ray
-// (ray_tracer_games101_branch.comp:217-235).  Its u points along normalize(forward x up), its v
-// along normalize(forward x u) (down the image), and a pixel centre lies at slope
-// (px + 1/2 - W/2) / k, k = H / (2 tan(vfov/2 * PI/180)), in both directions (w = h W / H).
-// Everything in double, each output rounded once.
+// *out = *params or the defaults, validated (negated compares: a NaN is rejected too)
+static int temporal_params_checked(rvcp_ctx_t *ctx, const rvcp_temporal_params_t *params,
+                                   rvcp_temporal_params_t *out)
+{
+    if (params) *out = *params;
+    else (void)impl_temporal_params_default(out);
+    if (!(out->alpha_min >= 0.0f && out->alpha_min <= 1.0f))
+        return fail(ctx, RVCP_E_INVALID, "temporal alpha_min must be in 0..1");
+    if (out->max_history < 1 || out->max_history > RVCP_TEMPORAL_MAX_HISTORY)
+        return fail(ctx, RVCP_E_INVALID, "temporal max_history must be in 1..65535");
+    if (!(out->sigma_plane > 0.0f))
+        return fail(ctx, RVCP_E_INVALID, "temporal sigma_plane must be > 0");
+    if (!(out->normal_min >= -1.0f && out->normal_min <= 1.0f))
+        return fail(ctx, RVCP_E_INVALID, "temporal normal_min must be in -1..1");
+    return RVCP_OK;
+}
+
+// The camera as the kernel projects through it, the inverse of sample_ray
+// (ray_tracer_games101_branch.comp:217-235), in double: f = forward (ff = |f|^2), r =
+// normalize(forward x up) (its u), d = forward x r of length dl (its v: down the image), and a
+// pixel centre lies at slope (px + 1/2 - W/2) / k, k = H / (2 tan(vfov/2 * PI/180)), in both
+// directions (w = h W / H).  rvcp_temporal_view_from_push and rvcp_taa_jitter_push must agree on
+// it bit for bit.
+struct CameraBasis { double f[3], r[3], d[3], dl, ff, k; };
+
+// false: forward is zero or parallel to up
+static bool camera_basis(const rvcp_camera_t &c, uint32_t height, CameraBasis *b)
+{
+    const double up[3] = {c.up[0], c.up[1], c.up[2]};
+    double *f = b->f, *r = b->r, *d = b->d;
+    for (int i = 0; i < 3; ++i) f[i] = c.forward[i];
+    r[0] = f[1] * up[2] - f[2] * up[1];
+    r[1] = f[2] * up[0] - f[0] * up[2];
+    r[2] = f[0] * up[1] - f[1] * up[0];
+    const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    b->ff = f[0] * f[0] + f[1] * f[1] + f[2] * f[2];
+    if (!(rl > 0.0) || !(b->ff > 0.0)) return false;
+    for (int i = 0; i < 3; ++i) r[i] /= rl;
+    d[0] = f[1] * r[2] - f[2] * r[1];
+    d[1] = f[2] * r[0] - f[0] * r[2];
+    d[2] = f[0] * r[1] - f[1] * r[0];
+    b->dl = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    if (!(b->dl > 0.0)) return false;
+    const double PI = 3.1415926;      // the shader's constant (:15)
+    b->k = (double)height / (2.0 * std::tan((double)c.vertical_fov / 2.0 * PI / 180.0));
+    return true;
+}
+
+// The camera of `push` as a view record: each output rounded once.
 static int impl_temporal_view_from_push(const rvcp_push_constant_t *push, uint32_t width,
                                         uint32_t height, rvcp_temporal_view_t *out)
 {
     if (!push || !out || width == 0 || height == 0) return RVCP_E_INVALID;
-    const rvcp_camera_t &c = push->camera;
-    const double f[3] = {c.forward[0], c.forward[1], c.forward[2]};
-    const double up[3] = {c.up[0], c.up[1], c.up[2]};
-    double r[3] = {f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]};
-    const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-    const double ff = f[0] * f[0] + f[1] * f[1] + f[2] * f[2];
-    if (!(rl > 0.0) || !(ff > 0.0)) return RVCP_E_INVALID;
-    for (double &v : r) v /= rl;
-    double d[3] = {f[1] * r[2] - f[2] * r[1], f[2] * r[0] - f[0] * r[2], f[0] * r[1] - f[1] * r[0]};
-    const double dl = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    if (!(dl > 0.0)) return RVCP_E_INVALID;
-    const double PI = 3.1415926;      // the shader's constant (:15)
-    const double k = (double)height / (2.0 * std::tan((double)c.vertical_fov / 2.0 * PI / 180.0));
+    CameraBasis b;
+    if (!camera_basis(push->camera, height, &b)) return RVCP_E_INVALID;
     std::memset(out, 0, sizeof(*out));
     for (int i = 0; i < 3; ++i) {
-        out->position[i] = c.position[i];
-        out->right[i] = (float)r[i];
-        out->down[i] = (float)(d[i] / dl);
-        out->forward[i] = (float)(f[i] / ff);
+        out->position[i] = push->camera.position[i];
+        out->right[i] = (float)b.r[i];
+        out->down[i] = (float)(b.d[i] / b.dl);
+        out->forward[i] = (float)(b.f[i] / b.ff);
     }
-    out->k = (float)k;
+    out->k = (float)b.k;
     return RVCP_OK;
-}
-
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + nb && y < x + na;
 }
 
 static int impl_temporal_accumulate_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *view,
@@ -1791,83 +1886,42 @@ static int impl_temporal_accumulate_async(rvcp_ctx_t *ctx, const rvcp_temporal_v
     if (!ctx) return RVCP_E_INVALID;
     if (!d_cur || !d_cur_g || !d_out || !d_out_len || width == 0 || height == 0)
         return fail(ctx, RVCP_E_INVALID, "invalid temporal arguments");
-    if ((uint64_t)width * height >= (1ull << 31))
-        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    int rc;
+    if ((rc = frame_size_checked(ctx, width, height)) != RVCP_OK) return rc;
     const int n_prev = (d_prev ? 1 : 0) + (d_prev_g ? 1 : 0) + (d_prev_len ? 1 : 0);
     if (n_prev != 0 && n_prev != 3)
         return fail(ctx, RVCP_E_INVALID, "temporal history needs d_prev_linear, d_prev_gbuffer "
                     "and d_prev_len together");
     rvcp_temporal_params_t P;
-    if (params) P = *params;
-    else (void)impl_temporal_params_default(&P);
-    // (negated compares: a NaN is rejected too)
-    if (!(P.alpha_min >= 0.0f && P.alpha_min <= 1.0f))
-        return fail(ctx, RVCP_E_INVALID, "temporal alpha_min must be in 0..1");
-    if (P.max_history < 1 || P.max_history > RVCP_TEMPORAL_MAX_HISTORY)
-        return fail(ctx, RVCP_E_INVALID, "temporal max_history must be in 1..65535");
-    if (!(P.sigma_plane > 0.0f))
-        return fail(ctx, RVCP_E_INVALID, "temporal sigma_plane must be > 0");
-    if (!(P.normal_min >= -1.0f && P.normal_min <= 1.0f))
-        return fail(ctx, RVCP_E_INVALID, "temporal normal_min must be in -1..1");
+    if ((rc = temporal_params_checked(ctx, params, &P)) != RVCP_OK) return rc;
     const size_t npx = (size_t)width * height;
-    {   // a lane reads its neighbours' history, and the frames are not the caller's to lose: no
-        // output may overlap an input or another output
-        const struct { const void *p; size_t n; } in[5] = {
-            {d_cur, npx * 12}, {d_cur_g, npx * 32}, {d_prev, npx * 12}, {d_prev_g, npx * 32},
-            {d_prev_len, npx * 4}};
-        const struct { const void *p; size_t n; } out[3] = {
-            {d_out, npx * 12}, {d_out_len, npx * 4}, {d_rgba8_out, npx * 4}};
-        for (int o = 0; o < 3; ++o) {
-            for (int i = 0; i < 5; ++i)
-                if (ranges_overlap(out[o].p, out[o].n, in[i].p, in[i].n))
-                    return fail(ctx, RVCP_E_INVALID, "temporal output overlaps an input");
-            for (int q = o + 1; q < 3; ++q)
-                if (ranges_overlap(out[o].p, out[o].n, out[q].p, out[q].n))
-                    return fail(ctx, RVCP_E_INVALID, "temporal outputs overlap each other");
-        }
-    }
+    if ((rc = overlap_checked(ctx, "temporal",
+                              {{d_cur, npx * 12}, {d_cur_g, npx * 32}, {d_prev, npx * 12},
+                               {d_prev_g, npx * 32}, {d_prev_len, npx * 4}},
+                              {{d_out, npx * 12}, {d_out_len, npx * 4}, {d_rgba8_out, npx * 4}})) != RVCP_OK)
+        return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    if (!ctx->evt0) {
-        HIP_TRY(ctx, hipEventCreate(&ctx->evt0));
-        HIP_TRY(ctx, hipEventCreate(&ctx->evt1));
-    }
-    // behind a render pending on this context (when it runs on another stream), and behind the
-    // context's previous step, whose outputs are usually this one's history
-    if (ctx->pending && ctx->render_stream != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev1, 0));
-    if (ctx->temporal_recorded) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evt1, 0));
-    HIP_TRY(ctx, hipEventRecord(ctx->evt0, s));
+    if ((rc = stage_begin(ctx, ST_TEMPORAL, s)) != RVCP_OK) return rc;
     const uint32_t mode = n_prev == 0 ? 0u : view ? 2u : 1u;
     if (rvcp_launch_temporal((const float *)d_cur, d_cur_g, (const float *)d_prev, d_prev_g,
                              (const uint32_t *)d_prev_len, (float *)d_out, (uint32_t *)d_out_len,
                              width, height, mode, view, &P, s) != 0)
         return fail(ctx, RVCP_E_HIP, std::string("temporal launch failed: ") +
                                          hipGetErrorString(hipGetLastError()));
-    if (d_rgba8_out &&
-        rvcp_launch_tonemap((const float *)d_out, (uint32_t)npx, ctx->d_gamma,
-                            (uint32_t *)d_rgba8_out, s) != 0)
-        return fail(ctx, RVCP_E_HIP, "temporal tone-map launch failed");
-    HIP_TRY(ctx, hipEventRecord(ctx->evt1, s));
-    ctx->temporal_recorded = true;
-    ctx->temporal_pending = true;
-    return RVCP_OK;
+    if ((rc = tonemap_tail(ctx, "temporal", d_out, npx, d_rgba8_out, s)) != RVCP_OK) return rc;
+    return stage_end(ctx, ST_TEMPORAL, s);
 }
 
 static int impl_temporal_wait(rvcp_ctx_t *ctx, float *temporal_ms)
 {
-    if (!ctx) return RVCP_E_INVALID;
-    if (!ctx->temporal_pending) return fail(ctx, RVCP_E_INVALID, "no temporal step in flight");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->evt1));
-    if (temporal_ms) HIP_TRY(ctx, hipEventElapsedTime(temporal_ms, ctx->evt0, ctx->evt1));
-    ctx->temporal_pending = false;
-    return RVCP_OK;
+    return stage_wait(ctx, ST_TEMPORAL, "no temporal step in flight", temporal_ms);
 }
 
 static int impl_temporal_reset(rvcp_ctx_t *ctx)
 {
     if (!ctx) return RVCP_E_INVALID;
-    ctx->tp_valid = false;
+    ctx->tp_hist.valid = false;
     return RVCP_OK;
 }
 
@@ -1913,25 +1967,14 @@ static int impl_taa_jitter_push(const rvcp_push_constant_t *base, uint32_t width
     // (negated compares: a NaN is rejected too)
     if (!(jitter[0] >= -1.0f && jitter[0] <= 1.0f && jitter[1] >= -1.0f && jitter[1] <= 1.0f))
         return RVCP_E_INVALID;
-    const rvcp_camera_t &c = base->camera;
-    const double f[3] = {c.forward[0], c.forward[1], c.forward[2]};
-    const double up[3] = {c.up[0], c.up[1], c.up[2]};
-    double r[3] = {f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]};
-    const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-    const double ff = f[0] * f[0] + f[1] * f[1] + f[2] * f[2];
-    if (!(rl > 0.0) || !(ff > 0.0)) return RVCP_E_INVALID;
-    for (double &v : r) v /= rl;
-    double d[3] = {f[1] * r[2] - f[2] * r[1], f[2] * r[0] - f[0] * r[2], f[0] * r[1] - f[1] * r[0]};
-    const double dl = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    if (!(dl > 0.0)) return RVCP_E_INVALID;
+    CameraBasis b;
+    if (!camera_basis(base->camera, height, &b)) return RVCP_E_INVALID;
     const rvcp_push_constant_t copy = *base;        // (out may be base)
     *out = copy;
     if (jitter[0] == 0.0f && jitter[1] == 0.0f) return RVCP_OK;
-    const double PI = 3.1415926;      // the shader's constant (:15)
-    const double k = (double)height / (2.0 * std::tan((double)c.vertical_fov / 2.0 * PI / 180.0));
-    const double fl = std::sqrt(ff), jx = (double)jitter[0] / k, jy = (double)jitter[1] / k;
+    const double fl = std::sqrt(b.ff), jx = (double)jitter[0] / b.k, jy = (double)jitter[1] / b.k;
     double n[3];
-    for (int i = 0; i < 3; ++i) n[i] = f[i] / fl + r[i] * jx + (d[i] / dl) * jy;
+    for (int i = 0; i < 3; ++i) n[i] = b.f[i] / fl + b.r[i] * jx + (b.d[i] / b.dl) * jy;
     const double nl = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
     for (int i = 0; i < 3; ++i) out->camera.forward[i] = (float)(n[i] / nl * fl);
     return RVCP_OK;
@@ -1946,8 +1989,8 @@ static int impl_taa_resolve_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *c
     if (!ctx) return RVCP_E_INVALID;
     if (!d_cur || !d_cur_g || !d_out || !d_out_len || width == 0 || height == 0)
         return fail(ctx, RVCP_E_INVALID, "invalid TAA resolve arguments");
-    if ((uint64_t)width * height >= (1ull << 31))
-        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    int rc;
+    if ((rc = frame_size_checked(ctx, width, height)) != RVCP_OK) return rc;
     if ((d_prev == nullptr) != (d_prev_len == nullptr))
         return fail(ctx, RVCP_E_INVALID, "TAA history needs d_prev_resolved and d_prev_len together");
     if ((cur_view == nullptr) != (prev_view == nullptr))
@@ -1965,32 +2008,14 @@ static int impl_taa_resolve_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *c
     if (P._pad != 0)
         return fail(ctx, RVCP_E_INVALID, "TAA params._pad must be 0");
     const size_t npx = (size_t)width * height;
-    {   // a lane reads its neighbours' colours and history: no output may overlap an input or
-        // another output
-        const struct { const void *p; size_t n; } in[4] = {
-            {d_cur, npx * 12}, {d_cur_g, npx * 32}, {d_prev, npx * 12}, {d_prev_len, npx * 4}};
-        const struct { const void *p; size_t n; } out[3] = {
-            {d_out, npx * 12}, {d_out_len, npx * 4}, {d_rgba8_out, npx * 4}};
-        for (int o = 0; o < 3; ++o) {
-            for (int i = 0; i < 4; ++i)
-                if (ranges_overlap(out[o].p, out[o].n, in[i].p, in[i].n))
-                    return fail(ctx, RVCP_E_INVALID, "TAA output overlaps an input");
-            for (int q = o + 1; q < 3; ++q)
-                if (ranges_overlap(out[o].p, out[o].n, out[q].p, out[q].n))
-                    return fail(ctx, RVCP_E_INVALID, "TAA outputs overlap each other");
-        }
-    }
+    if ((rc = overlap_checked(ctx, "TAA",
+                              {{d_cur, npx * 12}, {d_cur_g, npx * 32}, {d_prev, npx * 12},
+                               {d_prev_len, npx * 4}},
+                              {{d_out, npx * 12}, {d_out_len, npx * 4}, {d_rgba8_out, npx * 4}})) != RVCP_OK)
+        return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    if (!ctx->evta0) {
-        HIP_TRY(ctx, hipEventCreate(&ctx->evta0));
-        HIP_TRY(ctx, hipEventCreate(&ctx->evta1));
-    }
-    // behind a render pending on this context (when it runs on another stream), and behind the
-    // context's previous resolve, whose outputs are usually this one's history
-    if (ctx->pending && ctx->render_stream != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev1, 0));
-    if (ctx->taa_recorded) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evta1, 0));
-    HIP_TRY(ctx, hipEventRecord(ctx->evta0, s));
+    if ((rc = stage_begin(ctx, ST_TAA, s)) != RVCP_OK) return rc;
     // a camera at rest fetches q = p exactly and never resamples: byte-equal views are no views
     const bool moved = cur_view && std::memcmp(cur_view, prev_view, sizeof(*cur_view)) != 0;
     const uint32_t mode = !d_prev ? 0u : moved ? 2u : 1u;
@@ -2000,21 +2025,12 @@ static int impl_taa_resolve_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *c
                                 prev_view, &P, s) != 0)
         return fail(ctx, RVCP_E_HIP, std::string("TAA resolve launch failed: ") +
                                          hipGetErrorString(hipGetLastError()));
-    HIP_TRY(ctx, hipEventRecord(ctx->evta1, s));
-    ctx->taa_recorded = true;
-    ctx->taa_pending = true;
-    return RVCP_OK;
+    return stage_end(ctx, ST_TAA, s);
 }
 
 static int impl_taa_wait(rvcp_ctx_t *ctx, float *taa_ms)
 {
-    if (!ctx) return RVCP_E_INVALID;
-    if (!ctx->taa_pending) return fail(ctx, RVCP_E_INVALID, "no TAA resolve in flight");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->evta1));
-    if (taa_ms) HIP_TRY(ctx, hipEventElapsedTime(taa_ms, ctx->evta0, ctx->evta1));
-    ctx->taa_pending = false;
-    return RVCP_OK;
+    return stage_wait(ctx, ST_TAA, "no TAA resolve in flight", taa_ms);
 }
 
 static int impl_set_taa(rvcp_ctx_t *ctx, int on)
@@ -2025,10 +2041,9 @@ static int impl_set_taa(rvcp_ctx_t *ctx, int on)
     const bool want = on != 0;
     if (want == ctx->taa) return RVCP_OK;
     ctx->taa = want;
-    ctx->tp_valid = false;      // histories of centred and of jittered frames do not mix
-    ctx->sv_valid = false;
-    ctx->taa_tp.valid = false;
-    ctx->taa_sv.valid = false;
+    // histories of centred and of jittered frames do not mix
+    ctx->tp_hist.valid = ctx->sv_hist.valid = false;
+    ctx->taa_tp.hist.valid = ctx->taa_sv.hist.valid = false;
     return RVCP_OK;
 }
 
@@ -2043,72 +2058,9 @@ static int impl_get_taa(rvcp_ctx_t *ctx, int *on)
 static int impl_taa_reset(rvcp_ctx_t *ctx)
 {
     if (!ctx) return RVCP_E_INVALID;
-    ctx->taa_tp.valid = false;
-    ctx->taa_sv.valid = false;
-    ctx->taau_tp.valid = false;
-    ctx->taau_sv.valid = false;
+    ctx->taa_tp.hist.valid = ctx->taa_sv.hist.valid = false;
+    ctx->taau_tp.hist.valid = ctx->taau_sv.hist.valid = false;
     return RVCP_OK;
-}
-
-// What a stateful chain does for its TAA state `st` before it renders (the switch is on):
-// `have` says whether the chain's own history continues.  *jpush becomes the jittered push of this
-// frame, *resume whether the resolve has a history, and the state's buffers hold npx pixels.
-static int taa_chain_begin(rvcp_ctx_t *ctx, rvcp_ctx::TaaState &st, bool have,
-                           const rvcp_push_constant_t *push, uint32_t width, uint32_t height,
-                           rvcp_push_constant_t *jpush, bool *resume)
-{
-    const size_t npx = (size_t)width * height;
-    if (st.cap < npx) {
-        st.valid = false;
-        st.cap = 0;
-        for (int i = 0; i < 2; ++i) {
-            (void)hipFree(st.d_res[i]);
-            (void)hipFree(st.d_len[i]);
-            st.d_res[i] = nullptr;
-            st.d_len[i] = nullptr;
-        }
-        for (int i = 0; i < 2; ++i) {
-            HIP_TRY(ctx, hipMalloc((void **)&st.d_res[i], npx * 12));
-            HIP_TRY(ctx, hipMalloc((void **)&st.d_len[i], npx * 4));
-        }
-        st.cap = npx;
-    }
-    *resume = have && st.valid && st.width == width && st.height == height;
-    if (!*resume) st.counter = 0;       // the state is dropped with the chain's history
-    st.valid = false;                   // until this frame is complete
-    float j[2];
-    (void)impl_taa_jitter(st.counter, j);
-    if (impl_taa_jitter_push(push, width, height, j, jpush) != RVCP_OK)
-        return fail(ctx, RVCP_E_INVALID, "the camera's forward is zero or parallel to up");
-    return RVCP_OK;
-}
-
-// ... and behind its last step: the resolve of d_final under the unjittered cameras into the
-// state's free slot and d_rgba
-static int taa_chain_resolve(rvcp_ctx_t *ctx, rvcp_ctx::TaaState &st, bool resume,
-                             const rvcp_push_constant_t *push, const rvcp_temporal_view_t *base_view,
-                             const float *d_final, const void *d_gbuffer, uint32_t width,
-                             uint32_t height)
-{
-    const uint32_t prev = st.slot, cur = prev ^ 1u;
-    const bool at_rest = resume && std::memcmp(&st.camera, &push->camera, sizeof(rvcp_camera_t)) == 0;
-    return impl_taa_resolve_async(ctx, at_rest ? nullptr : base_view, at_rest ? nullptr : &st.view,
-                                  d_final, d_gbuffer, resume ? st.d_res[prev] : nullptr,
-                                  resume ? st.d_len[prev] : nullptr, width, height, nullptr,
-                                  st.d_res[cur], st.d_len[cur], ctx->d_rgba, ctx->stream);
-}
-
-// ... and once the frame is complete
-static void taa_chain_commit(rvcp_ctx::TaaState &st, const rvcp_push_constant_t *push,
-                             const rvcp_temporal_view_t *base_view, uint32_t width, uint32_t height)
-{
-    st.slot ^= 1u;
-    st.width = width;
-    st.height = height;
-    st.camera = push->camera;
-    st.view = *base_view;
-    st.counter += 1;
-    st.valid = true;
 }
 
 // ---- temporal upsampling: the step and the switch -------------------------
@@ -2139,8 +2091,8 @@ static int impl_taa_upsample_async(rvcp_ctx_t *ctx, uint32_t scale,
         return fail(ctx, RVCP_E_INVALID, "TAA upsampling scale must be in 2..4");
     if (width % scale != 0 || height % scale != 0)
         return fail(ctx, RVCP_E_INVALID, "TAA upsampling: the scale must divide width and height");
-    if ((uint64_t)width * height >= (1ull << 31))
-        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    int rc;
+    if ((rc = frame_size_checked(ctx, width, height)) != RVCP_OK) return rc;
     if ((d_prev == nullptr) != (d_prev_wt == nullptr))
         return fail(ctx, RVCP_E_INVALID,
                     "TAA upsampling history needs d_prev_resolved and d_prev_weight together");
@@ -2163,32 +2115,14 @@ static int impl_taa_upsample_async(rvcp_ctx_t *ctx, uint32_t scale,
     if (P._pad != 0)
         return fail(ctx, RVCP_E_INVALID, "TAA upsampling params._pad must be 0");
     const size_t npx = (size_t)width * height, lpx = npx / scale / scale;
-    {   // a lane reads its neighbours' colours and history: no output may overlap an input or
-        // another output
-        const struct { const void *p; size_t n; } in[4] = {
-            {d_cur, lpx * 12}, {d_g_hi, npx * 32}, {d_prev, npx * 12}, {d_prev_wt, npx * 4}};
-        const struct { const void *p; size_t n; } out[3] = {
-            {d_out, npx * 12}, {d_out_wt, npx * 4}, {d_rgba8_out, npx * 4}};
-        for (int o = 0; o < 3; ++o) {
-            for (int i = 0; i < 4; ++i)
-                if (ranges_overlap(out[o].p, out[o].n, in[i].p, in[i].n))
-                    return fail(ctx, RVCP_E_INVALID, "TAA upsampling output overlaps an input");
-            for (int q = o + 1; q < 3; ++q)
-                if (ranges_overlap(out[o].p, out[o].n, out[q].p, out[q].n))
-                    return fail(ctx, RVCP_E_INVALID, "TAA upsampling outputs overlap each other");
-        }
-    }
+    if ((rc = overlap_checked(ctx, "TAA upsampling",
+                              {{d_cur, lpx * 12}, {d_g_hi, npx * 32}, {d_prev, npx * 12},
+                               {d_prev_wt, npx * 4}},
+                              {{d_out, npx * 12}, {d_out_wt, npx * 4}, {d_rgba8_out, npx * 4}})) != RVCP_OK)
+        return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    if (!ctx->evtu0) {
-        HIP_TRY(ctx, hipEventCreate(&ctx->evtu0));
-        HIP_TRY(ctx, hipEventCreate(&ctx->evtu1));
-    }
-    // behind a render pending on this context (when it runs on another stream), and behind the
-    // context's previous step, whose outputs are usually this one's history
-    if (ctx->pending && ctx->render_stream != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev1, 0));
-    if (ctx->taau_recorded) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evtu1, 0));
-    HIP_TRY(ctx, hipEventRecord(ctx->evtu0, s));
+    if ((rc = stage_begin(ctx, ST_TAAU, s)) != RVCP_OK) return rc;
     const uint32_t mode = !d_prev ? 0u : moved ? 2u : 1u;
     if (rvcp_launch_taa_upsample((const float *)d_cur, d_g_hi, (const float *)d_prev,
                                  (const float *)d_prev_wt, (float *)d_out, (float *)d_out_wt,
@@ -2196,21 +2130,12 @@ static int impl_taa_upsample_async(rvcp_ctx_t *ctx, uint32_t scale,
                                  jit_view, cur_view, prev_view, &P, 0u, s) != 0)
         return fail(ctx, RVCP_E_HIP, std::string("TAA upsampling launch failed: ") +
                                          hipGetErrorString(hipGetLastError()));
-    HIP_TRY(ctx, hipEventRecord(ctx->evtu1, s));
-    ctx->taau_recorded = true;
-    ctx->taau_pending = true;
-    return RVCP_OK;
+    return stage_end(ctx, ST_TAAU, s);
 }
 
 static int impl_taau_wait(rvcp_ctx_t *ctx, float *taau_ms)
 {
-    if (!ctx) return RVCP_E_INVALID;
-    if (!ctx->taau_pending) return fail(ctx, RVCP_E_INVALID, "no TAA upsampling step in flight");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->evtu1));
-    if (taau_ms) HIP_TRY(ctx, hipEventElapsedTime(taau_ms, ctx->evtu0, ctx->evtu1));
-    ctx->taau_pending = false;
-    return RVCP_OK;
+    return stage_wait(ctx, ST_TAAU, "no TAA upsampling step in flight", taau_ms);
 }
 
 static int impl_set_taa_upsample(rvcp_ctx_t *ctx, uint32_t scale)
@@ -2222,12 +2147,10 @@ static int impl_set_taa_upsample(rvcp_ctx_t *ctx, uint32_t scale)
         return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
     if (scale == ctx->taau_scale) return RVCP_OK;
     ctx->taau_scale = scale;
-    ctx->tp_valid = false;      // histories of frames traced at different sizes do not mix
-    ctx->sv_valid = false;
-    ctx->taa_tp.valid = false;
-    ctx->taa_sv.valid = false;
-    ctx->taau_tp.valid = false;
-    ctx->taau_sv.valid = false;
+    // histories of frames traced at different sizes do not mix
+    ctx->tp_hist.valid = ctx->sv_hist.valid = false;
+    ctx->taa_tp.hist.valid = ctx->taa_sv.hist.valid = false;
+    ctx->taau_tp.hist.valid = ctx->taau_sv.hist.valid = false;
     return RVCP_OK;
 }
 
@@ -2236,239 +2159,6 @@ static int impl_get_taa_upsample(rvcp_ctx_t *ctx, uint32_t *scale)
     if (!ctx) return RVCP_E_INVALID;
     if (!scale) return fail(ctx, RVCP_E_INVALID, "invalid get_taa_upsample arguments");
     *scale = ctx->taau_scale;
-    return RVCP_OK;
-}
-
-// What a stateful chain does for its upsampling state `st` before it renders (the scale is above
-// 1; width x height is the OUTPUT frame): as taa_chain_begin, the jitter being that of the traced
-// lw x lh frame
-static int taau_chain_begin(rvcp_ctx_t *ctx, rvcp_ctx::TaauState &st, bool have,
-                            const rvcp_push_constant_t *push, uint32_t width, uint32_t height,
-                            uint32_t lw, uint32_t lh, rvcp_push_constant_t *jpush, bool *resume)
-{
-    const size_t npx = (size_t)width * height;
-    if (st.cap < npx) {
-        st.valid = false;
-        st.cap = 0;
-        for (int i = 0; i < 2; ++i) {
-            (void)hipFree(st.d_res[i]);
-            (void)hipFree(st.d_wt[i]);
-            st.d_res[i] = nullptr;
-            st.d_wt[i] = nullptr;
-        }
-        (void)hipFree(st.d_gbuf);
-        st.d_gbuf = nullptr;
-        for (int i = 0; i < 2; ++i) {
-            HIP_TRY(ctx, hipMalloc((void **)&st.d_res[i], npx * 12));
-            HIP_TRY(ctx, hipMalloc((void **)&st.d_wt[i], npx * 4));
-        }
-        HIP_TRY(ctx, hipMalloc(&st.d_gbuf, npx * sizeof(rvcp_gbuffer_texel_t)));
-        st.cap = npx;
-    }
-    *resume = have && st.valid && st.width == width && st.height == height;
-    if (!*resume) st.counter = 0;       // the state is dropped with the chain's history
-    st.valid = false;                   // until this frame is complete
-    float j[2];
-    (void)impl_taa_jitter(st.counter, j);
-    if (impl_taa_jitter_push(push, lw, lh, j, jpush) != RVCP_OK)
-        return fail(ctx, RVCP_E_INVALID, "the camera's forward is zero or parallel to up");
-    return RVCP_OK;
-}
-
-// ... and behind its last step: the output-size G-buffer through the unjittered camera when it
-// moved, and the upsampling of d_final (traced through jit_view) into the state's free slot and
-// d_rgba
-static int taau_chain_resolve(rvcp_ctx_t *ctx, rvcp_ctx::TaauState &st, bool resume,
-                              const rvcp_push_constant_t *push, const rvcp_temporal_view_t *base_view,
-                              const rvcp_temporal_view_t *jit_view, const float *d_final,
-                              uint32_t width, uint32_t height)
-{
-    const uint32_t prev = st.slot, cur = prev ^ 1u;
-    const bool moved = resume && std::memcmp(&st.camera, &push->camera, sizeof(rvcp_camera_t)) != 0;
-    if (moved) {
-        const int rc = impl_render_gbuffer_async(ctx, push, width, height, st.d_gbuf, ctx->stream);
-        if (rc != RVCP_OK) return rc;
-    }
-    return impl_taa_upsample_async(ctx, ctx->taau_scale, jit_view, base_view,
-                                   moved ? &st.view : nullptr, d_final, moved ? st.d_gbuf : nullptr,
-                                   resume ? st.d_res[prev] : nullptr,
-                                   resume ? st.d_wt[prev] : nullptr, width, height, nullptr,
-                                   st.d_res[cur], st.d_wt[cur], ctx->d_rgba, ctx->stream);
-}
-
-// ... and once the frame is complete
-static void taau_chain_commit(rvcp_ctx::TaauState &st, const rvcp_push_constant_t *push,
-                              const rvcp_temporal_view_t *base_view, uint32_t width, uint32_t height)
-{
-    st.slot ^= 1u;
-    st.width = width;
-    st.height = height;
-    st.camera = push->camera;
-    st.view = *base_view;
-    st.counter += 1;
-    st.valid = true;
-}
-
-static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
-                                uint32_t height, const rvcp_temporal_params_t *tparams,
-                                uint32_t flags, const rvcp_denoise_params_t *dparams,
-                                uint8_t *out_rgba8, float *out_linear_rgb,
-                                uint32_t *out_history_len, rvcp_stats_t *stats, float *temporal_ms,
-                                float *denoise_ms)
-{
-    if (!ctx) return RVCP_E_INVALID;
-    if (!push || !out_rgba8 || width == 0 || height == 0 ||
-        (uint64_t)width * height >= (1ull << 31) || (flags & ~RVCP_TEMPORAL_DENOISE))
-        return fail(ctx, RVCP_E_INVALID, "invalid render_temporal arguments");
-    if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
-        return fail(ctx, RVCP_E_UNSUPPORTED, "the G-buffer is implemented for the games101 integrator");
-    if (!ctx->subs.empty())
-        return fail(ctx, RVCP_E_UNSUPPORTED, "render_temporal drives one GPU (n_gpus = 1)");
-    if (ctx->pending)
-        return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
-    // With the upsampling scale above 1 (§4.14): width x height below is the TRACED frame, the
-    // whole chain runs at that size, and out_w x out_h is what the last step writes
-    const uint32_t up = ctx->taau_scale, out_w = width, out_h = height;
-    if (up > 1) {
-        if (width % up != 0 || height % up != 0)
-            return fail(ctx, RVCP_E_INVALID, "render_temporal: the TAA upsampling scale must divide width and height");
-        width /= up;
-        height /= up;
-    }
-    rvcp_temporal_view_t view_now;
-    if (impl_temporal_view_from_push(push, width, height, &view_now) != RVCP_OK)
-        return fail(ctx, RVCP_E_INVALID, "render_temporal: the camera's forward is zero or parallel to up");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool denoise = (flags & RVCP_TEMPORAL_DENOISE) != 0;
-    const size_t npx = (size_t)width * height, out_npx = (size_t)out_w * out_h;
-    int rc;
-    if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, out_npx, 4)) != RVCP_OK) return rc;
-    if (ctx->cap_tp < npx) {            // (a larger frame: the history is dropped with its buffers)
-        ctx->tp_valid = false;
-        ctx->cap_tp = 0;
-        for (int i = 0; i < 2; ++i) {
-            (void)hipFree(ctx->d_tp_lin[i]);
-            (void)hipFree(ctx->d_tp_len[i]);
-            (void)hipFree(ctx->d_tp_gbuf[i]);
-            ctx->d_tp_lin[i] = nullptr;
-            ctx->d_tp_len[i] = nullptr;
-            ctx->d_tp_gbuf[i] = nullptr;
-        }
-        (void)hipFree(ctx->d_tp_cur);
-        ctx->d_tp_cur = nullptr;
-        for (int i = 0; i < 2; ++i) {
-            HIP_TRY(ctx, hipMalloc((void **)&ctx->d_tp_lin[i], npx * 12));
-            HIP_TRY(ctx, hipMalloc((void **)&ctx->d_tp_len[i], npx * 4));
-            HIP_TRY(ctx, hipMalloc(&ctx->d_tp_gbuf[i], npx * sizeof(rvcp_gbuffer_texel_t)));
-        }
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_tp_cur, npx * 12));
-        ctx->cap_tp = npx;
-    }
-    if (denoise &&
-        (rc = grow(ctx, (void **)&ctx->d_tp_show, &ctx->cap_tp_show, npx, 12)) != RVCP_OK)
-        return rc;
-    const bool have = ctx->tp_valid && ctx->tp_width == width && ctx->tp_height == height;
-    // With the TAA switch set (§4.13): everything below runs through the jittered camera `jpush`,
-    // the chain's own history always reprojects (through the jittered cameras), no step stores
-    // RGBA8, and the resolve of the final linear colour under the unjittered cameras ends the frame.
-    // With the upsampling scale above 1 (§4.14) the upsampling step takes the resolve's place:
-    // base_view is then the unjittered camera at the output size
-    const bool taa = ctx->taa || up > 1;
-    const rvcp_push_constant_t *const base_push = push;
-    rvcp_temporal_view_t base_view = view_now;
-    if (up > 1 && impl_temporal_view_from_push(push, out_w, out_h, &base_view) != RVCP_OK)
-        return fail(ctx, RVCP_E_INVALID, "render_temporal: the camera's forward is zero or parallel to up");
-    rvcp_push_constant_t jpush;
-    bool taa_resume = false;
-    if (taa) {
-        rc = up > 1 ? taau_chain_begin(ctx, ctx->taau_tp, have, base_push, out_w, out_h, width,
-                                       height, &jpush, &taa_resume)
-                    : taa_chain_begin(ctx, ctx->taa_tp, have, base_push, width, height, &jpush,
-                                      &taa_resume);
-        if (rc != RVCP_OK)
-            return rc;
-        push = &jpush;
-        if (impl_temporal_view_from_push(push, width, height, &view_now) != RVCP_OK)
-            return fail(ctx, RVCP_E_INVALID, "render_temporal: the camera's forward is zero or parallel to up");
-    }
-    const bool same_camera = !taa && have &&
-                             std::memcmp(&ctx->tp_camera, &push->camera, sizeof(rvcp_camera_t)) == 0;
-    uint32_t *const store = taa ? nullptr : ctx->d_rgba;    // the chain's own RGBA8 store
-    const uint32_t prev = ctx->tp_slot, cur = prev ^ 1u;
-    ctx->tp_valid = false;              // until this frame is complete
-    // render (raw linear frame), G-buffer, accumulation [, filter], in this order on the context's
-    // stream; the last RGBA8 store overwrites the render's
-    if ((rc = rvcp_render_async(ctx, push, width, height, ctx->d_rgba, ctx->d_tp_cur, ctx->stream)) != RVCP_OK)
-        return rc;
-    // With the demodulation switch set (§4.12): the raw frame is demodulated in place right after
-    // the G-buffer, history and filter are in irradiance and store nothing, and the fused
-    // remodulate + store writes the colour into d_tp_cur (free by then) and the RGBA8 frame.
-    const bool demod = ctx->demodulation;
-    bool step_enqueued = false, filter_enqueued = false;
-    rc = impl_render_gbuffer_async(ctx, push, width, height, ctx->d_tp_gbuf[cur], ctx->stream);
-    if (rc == RVCP_OK && demod)
-        rc = impl_demodulate_async(ctx, ctx->d_tp_cur, ctx->d_tp_gbuf[cur], width, height,
-                                   ctx->d_tp_cur, ctx->stream);
-    if (rc == RVCP_OK) {
-        rc = impl_temporal_accumulate_async(
-            ctx, same_camera ? nullptr : &ctx->tp_view, ctx->d_tp_cur, ctx->d_tp_gbuf[cur],
-            have ? ctx->d_tp_lin[prev] : nullptr, have ? ctx->d_tp_gbuf[prev] : nullptr,
-            have ? ctx->d_tp_len[prev] : nullptr, width, height, tparams, ctx->d_tp_lin[cur],
-            ctx->d_tp_len[cur], denoise || demod ? nullptr : store, ctx->stream);
-        step_enqueued = rc == RVCP_OK;
-    }
-    if (rc == RVCP_OK && denoise) {
-        rc = impl_denoise_async(ctx, ctx->d_tp_lin[cur], ctx->d_tp_gbuf[cur], width, height, dparams,
-                                ctx->d_tp_show, demod ? nullptr : store, ctx->stream);
-        filter_enqueued = rc == RVCP_OK;
-    }
-    if (rc == RVCP_OK && demod)
-        rc = impl_remodulate_async(ctx, denoise ? ctx->d_tp_show : ctx->d_tp_lin[cur],
-                                   ctx->d_tp_gbuf[cur], width, height, ctx->d_tp_cur, store,
-                                   ctx->stream);
-    // the displayed linear frame
-    const float *d_final = demod ? ctx->d_tp_cur : denoise ? ctx->d_tp_show : ctx->d_tp_lin[cur];
-    bool resolve_enqueued = false;
-    if (rc == RVCP_OK && taa) {
-        rc = up > 1 ? taau_chain_resolve(ctx, ctx->taau_tp, taa_resume, base_push, &base_view,
-                                         &view_now, d_final, out_w, out_h)
-                    : taa_chain_resolve(ctx, ctx->taa_tp, taa_resume, base_push, &base_view, d_final,
-                                        ctx->d_tp_gbuf[cur], width, height);
-        resolve_enqueued = rc == RVCP_OK;
-    }
-    if (rc != RVCP_OK) {
-        const std::string why = ctx->err;
-        (void)rvcp_wait(ctx, nullptr);          // the render is enqueued: leave nothing pending
-        if (step_enqueued) (void)impl_temporal_wait(ctx, nullptr);
-        if (filter_enqueued) (void)impl_denoise_wait(ctx, nullptr);
-        albedo_drain(ctx);
-        ctx->err = why;
-        return rc;
-    }
-    if ((rc = rvcp_wait(ctx, stats)) != RVCP_OK) return rc;
-    if ((rc = impl_temporal_wait(ctx, temporal_ms)) != RVCP_OK) return rc;
-    if (denoise_ms) *denoise_ms = 0.0f;
-    if (denoise && (rc = impl_denoise_wait(ctx, denoise_ms)) != RVCP_OK) return rc;
-    if (demod && (rc = impl_albedo_wait(ctx, nullptr, nullptr)) != RVCP_OK) return rc;
-    if (resolve_enqueued) {
-        if ((rc = up > 1 ? impl_taau_wait(ctx, nullptr) : impl_taa_wait(ctx, nullptr)) != RVCP_OK)
-            return rc;
-        d_final = up > 1 ? ctx->taau_tp.d_res[ctx->taau_tp.slot ^ 1u]
-                         : ctx->taa_tp.d_res[ctx->taa_tp.slot ^ 1u];
-    }
-    HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, out_npx * 4, hipMemcpyDeviceToHost));
-    if (out_linear_rgb)
-        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, d_final, out_npx * 12, hipMemcpyDeviceToHost));
-    if (out_history_len)
-        HIP_TRY(ctx, hipMemcpy(out_history_len, ctx->d_tp_len[cur], npx * 4, hipMemcpyDeviceToHost));
-    ctx->tp_slot = cur;
-    ctx->tp_width = width;
-    ctx->tp_height = height;
-    ctx->tp_camera = push->camera;
-    ctx->tp_view = view_now;
-    ctx->tp_valid = true;
-    if (up > 1) taau_chain_commit(ctx->taau_tp, base_push, &base_view, out_w, out_h);
-    else if (taa) taa_chain_commit(ctx->taa_tp, base_push, &base_view, width, height);
     return RVCP_OK;
 }
 
@@ -2510,38 +2200,6 @@ static int svgf_params_checked(rvcp_ctx_t *ctx, const rvcp_svgf_params_t *params
     return RVCP_OK;
 }
 
-struct DevRange { const void *p; size_t n; };
-
-// no output may overlap an input or another output (NULL ranges overlap nothing)
-static bool outputs_overlap(const DevRange *in, int n_in, const DevRange *out, int n_out,
-                            const char **what)
-{
-    for (int o = 0; o < n_out; ++o) {
-        for (int i = 0; i < n_in; ++i)
-            if (ranges_overlap(out[o].p, out[o].n, in[i].p, in[i].n)) {
-                *what = "output overlaps an input";
-                return true;
-            }
-        for (int q = o + 1; q < n_out; ++q)
-            if (ranges_overlap(out[o].p, out[o].n, out[q].p, out[q].n)) {
-                *what = "outputs overlap each other";
-                return true;
-            }
-    }
-    return false;
-}
-
-// the SVGF steps share buffers from call to call: each is ordered behind a render pending on the
-// context (when it runs on another stream) and behind the context's previous accumulation and
-// filter
-static int svgf_order(rvcp_ctx_t *ctx, hipStream_t s)
-{
-    if (ctx->pending && ctx->render_stream != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev1, 0));
-    if (ctx->svgf_acc_recorded) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evsa1, 0));
-    if (ctx->svgf_flt_recorded) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evsf1, 0));
-    return RVCP_OK;
-}
-
 static int impl_svgf_accumulate_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_t *view,
                                       const void *d_cur, const void *d_cur_g, const void *d_prev,
                                       const void *d_prev_g, const void *d_prev_len,
@@ -2554,44 +2212,26 @@ static int impl_svgf_accumulate_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_
     if (!ctx) return RVCP_E_INVALID;
     if (!d_cur || !d_cur_g || !d_out || !d_out_len || !d_out_m || width == 0 || height == 0)
         return fail(ctx, RVCP_E_INVALID, "invalid svgf accumulation arguments");
-    if ((uint64_t)width * height >= (1ull << 31))
-        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    int rc;
+    if ((rc = frame_size_checked(ctx, width, height)) != RVCP_OK) return rc;
     const int n_prev = (d_prev ? 1 : 0) + (d_prev_g ? 1 : 0) + (d_prev_len ? 1 : 0) + (d_prev_m ? 1 : 0);
     if (n_prev != 0 && n_prev != 4)
         return fail(ctx, RVCP_E_INVALID, "svgf history needs d_prev_linear, d_prev_gbuffer, "
                     "d_prev_len and d_prev_moments together");
     rvcp_temporal_params_t P;
-    if (tparams) P = *tparams;
-    else (void)impl_temporal_params_default(&P);
-    if (!(P.alpha_min >= 0.0f && P.alpha_min <= 1.0f))
-        return fail(ctx, RVCP_E_INVALID, "temporal alpha_min must be in 0..1");
-    if (P.max_history < 1 || P.max_history > RVCP_TEMPORAL_MAX_HISTORY)
-        return fail(ctx, RVCP_E_INVALID, "temporal max_history must be in 1..65535");
-    if (!(P.sigma_plane > 0.0f))
-        return fail(ctx, RVCP_E_INVALID, "temporal sigma_plane must be > 0");
-    if (!(P.normal_min >= -1.0f && P.normal_min <= 1.0f))
-        return fail(ctx, RVCP_E_INVALID, "temporal normal_min must be in -1..1");
+    if ((rc = temporal_params_checked(ctx, tparams, &P)) != RVCP_OK) return rc;
     rvcp_svgf_params_t S;
-    int rc;
     if ((rc = svgf_params_checked(ctx, sparams, &S)) != RVCP_OK) return rc;
     const size_t npx = (size_t)width * height;
-    {
-        const DevRange in[6] = {{d_cur, npx * 12}, {d_cur_g, npx * 32}, {d_prev, npx * 12},
-                                {d_prev_g, npx * 32}, {d_prev_len, npx * 4}, {d_prev_m, npx * 8}};
-        const DevRange out[4] = {{d_out, npx * 12}, {d_out_len, npx * 4}, {d_out_m, npx * 8},
-                                 {d_rgba8_out, npx * 4}};
-        const char *what = nullptr;
-        if (outputs_overlap(in, 6, out, 4, &what))
-            return fail(ctx, RVCP_E_INVALID, std::string("svgf accumulation ") + what);
-    }
+    if ((rc = overlap_checked(ctx, "svgf accumulation",
+                              {{d_cur, npx * 12}, {d_cur_g, npx * 32}, {d_prev, npx * 12},
+                               {d_prev_g, npx * 32}, {d_prev_len, npx * 4}, {d_prev_m, npx * 8}},
+                              {{d_out, npx * 12}, {d_out_len, npx * 4}, {d_out_m, npx * 8},
+                               {d_rgba8_out, npx * 4}})) != RVCP_OK)
+        return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    if (!ctx->evsa0) {
-        HIP_TRY(ctx, hipEventCreate(&ctx->evsa0));
-        HIP_TRY(ctx, hipEventCreate(&ctx->evsa1));
-    }
-    if ((rc = svgf_order(ctx, s)) != RVCP_OK) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->evsa0, s));
+    if ((rc = stage_begin(ctx, ST_SVGF_ACC, s)) != RVCP_OK) return rc;
     const uint32_t mode = n_prev == 0 ? 0u : view ? 2u : 1u;
     if (rvcp_launch_svgf_temporal((const float *)d_cur, d_cur_g, (const float *)d_prev, d_prev_g,
                                   (const uint32_t *)d_prev_len, (const float *)d_prev_m,
@@ -2599,14 +2239,9 @@ static int impl_svgf_accumulate_async(rvcp_ctx_t *ctx, const rvcp_temporal_view_
                                   height, mode, view, &P, S.alpha_moments_min, s) != 0)
         return fail(ctx, RVCP_E_HIP, std::string("svgf accumulation launch failed: ") +
                                          hipGetErrorString(hipGetLastError()));
-    if (d_rgba8_out &&
-        rvcp_launch_tonemap((const float *)d_out, (uint32_t)npx, ctx->d_gamma,
-                            (uint32_t *)d_rgba8_out, s) != 0)
-        return fail(ctx, RVCP_E_HIP, "svgf accumulation tone-map launch failed");
-    HIP_TRY(ctx, hipEventRecord(ctx->evsa1, s));
-    ctx->svgf_acc_recorded = true;
-    ctx->svgf_acc_pending = true;
-    return RVCP_OK;
+    if ((rc = tonemap_tail(ctx, "svgf accumulation", d_out, npx, d_rgba8_out, s)) != RVCP_OK)
+        return rc;
+    return stage_end(ctx, ST_SVGF_ACC, s);
 }
 
 static int impl_svgf_filter_async(rvcp_ctx_t *ctx, const void *d_lin, const void *d_mom,
@@ -2617,27 +2252,19 @@ static int impl_svgf_filter_async(rvcp_ctx_t *ctx, const void *d_lin, const void
     if (!ctx) return RVCP_E_INVALID;
     if (!d_lin || !d_mom || !d_len || !d_gbuffer || !d_out || width == 0 || height == 0)
         return fail(ctx, RVCP_E_INVALID, "invalid svgf filter arguments");
-    if ((uint64_t)width * height >= (1ull << 31))
-        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
-    rvcp_svgf_params_t P;
     int rc;
+    if ((rc = frame_size_checked(ctx, width, height)) != RVCP_OK) return rc;
+    rvcp_svgf_params_t P;
     if ((rc = svgf_params_checked(ctx, params, &P)) != RVCP_OK) return rc;
     const size_t npx = (size_t)width * height;
-    {
-        const DevRange in[4] = {{d_lin, npx * 12}, {d_mom, npx * 8}, {d_len, npx * 4},
-                                {d_gbuffer, npx * 32}};
-        const DevRange out[4] = {{d_out, npx * 12}, {d_var_out, npx * 4}, {d_fb_out, npx * 12},
-                                 {d_rgba8_out, npx * 4}};
-        const char *what = nullptr;
-        if (outputs_overlap(in, 4, out, 4, &what))
-            return fail(ctx, RVCP_E_INVALID, std::string("svgf filter ") + what);
-    }
+    if ((rc = overlap_checked(ctx, "svgf filter",
+                              {{d_lin, npx * 12}, {d_mom, npx * 8}, {d_len, npx * 4},
+                               {d_gbuffer, npx * 32}},
+                              {{d_out, npx * 12}, {d_var_out, npx * 4}, {d_fb_out, npx * 12},
+                               {d_rgba8_out, npx * 4}})) != RVCP_OK)
+        return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    if (!ctx->evsf0) {
-        HIP_TRY(ctx, hipEventCreate(&ctx->evsf0));
-        HIP_TRY(ctx, hipEventCreate(&ctx->evsf1));
-    }
     // variance: the estimate in plane 0, pass i from plane i & 1 into the other one; colour
     // intermediates from two passes on (pass 0 may write the caller's feedback buffer instead)
     for (uint32_t b = 0; b < 2; ++b)
@@ -2646,8 +2273,7 @@ static int impl_svgf_filter_async(rvcp_ctx_t *ctx, const void *d_lin, const void
     for (uint32_t b = 0; b < 2 && b + 1 < P.iterations; ++b)
         if ((rc = grow(ctx, (void **)&ctx->d_sv_tmp[b], &ctx->cap_sv_tmp[b], npx, 12)) != RVCP_OK)
             return rc;
-    if ((rc = svgf_order(ctx, s)) != RVCP_OK) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->evsf0, s));
+    if ((rc = stage_begin(ctx, ST_SVGF_FLT, s)) != RVCP_OK) return rc;
     if (rvcp_launch_svgf_variance((const float *)d_mom, (const uint32_t *)d_len, d_gbuffer,
                                   ctx->d_sv_var[0], width, height, P.spatial_below,
                                   P.normal_power_log2, P.sigma_plane, s) != 0)
@@ -2670,61 +2296,21 @@ static int impl_svgf_filter_async(rvcp_ctx_t *ctx, const void *d_lin, const void
     }
     if (d_fb_out && P.iterations == 1)          // pass 0 is the last pass
         HIP_TRY(ctx, hipMemcpyAsync(d_fb_out, d_out, npx * 12, hipMemcpyDeviceToDevice, s));
-    if (d_rgba8_out &&
-        rvcp_launch_tonemap((const float *)d_out, (uint32_t)npx, ctx->d_gamma,
-                            (uint32_t *)d_rgba8_out, s) != 0)
-        return fail(ctx, RVCP_E_HIP, "svgf tone-map launch failed");
-    HIP_TRY(ctx, hipEventRecord(ctx->evsf1, s));
-    ctx->svgf_flt_recorded = true;
-    ctx->svgf_flt_pending = true;
-    return RVCP_OK;
+    if ((rc = tonemap_tail(ctx, "svgf", d_out, npx, d_rgba8_out, s)) != RVCP_OK) return rc;
+    return stage_end(ctx, ST_SVGF_FLT, s);
 }
 
 static int impl_svgf_wait(rvcp_ctx_t *ctx, float *accumulate_ms, float *filter_ms)
 {
-    if (!ctx) return RVCP_E_INVALID;
-    if (!ctx->svgf_acc_pending && !ctx->svgf_flt_pending)
-        return fail(ctx, RVCP_E_INVALID, "no svgf step in flight");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (accumulate_ms) *accumulate_ms = 0.0f;
-    if (filter_ms) *filter_ms = 0.0f;
-    if (ctx->svgf_acc_pending) {
-        HIP_TRY(ctx, hipEventSynchronize(ctx->evsa1));
-        if (accumulate_ms) HIP_TRY(ctx, hipEventElapsedTime(accumulate_ms, ctx->evsa0, ctx->evsa1));
-        ctx->svgf_acc_pending = false;
-    }
-    if (ctx->svgf_flt_pending) {
-        HIP_TRY(ctx, hipEventSynchronize(ctx->evsf1));
-        if (filter_ms) HIP_TRY(ctx, hipEventElapsedTime(filter_ms, ctx->evsf0, ctx->evsf1));
-        ctx->svgf_flt_pending = false;
-    }
-    return RVCP_OK;
+    return stage_wait2(ctx, ST_SVGF_ACC, ST_SVGF_FLT, "no svgf step in flight", accumulate_ms,
+                       filter_ms);
 }
 
 static int impl_svgf_reset(rvcp_ctx_t *ctx)
 {
     if (!ctx) return RVCP_E_INVALID;
-    ctx->sv_valid = false;
+    ctx->sv_hist.valid = false;
     return RVCP_OK;
-}
-
-static void svgf_free_state(rvcp_ctx_t *ctx)
-{
-    for (int i = 0; i < 2; ++i) {
-        (void)hipFree(ctx->d_sv_lin[i]);
-        (void)hipFree(ctx->d_sv_mom[i]);
-        (void)hipFree(ctx->d_sv_len[i]);
-        (void)hipFree(ctx->d_sv_gbuf[i]);
-        ctx->d_sv_lin[i] = ctx->d_sv_mom[i] = nullptr;
-        ctx->d_sv_len[i] = nullptr;
-        ctx->d_sv_gbuf[i] = nullptr;
-    }
-    (void)hipFree(ctx->d_sv_cur);
-    (void)hipFree(ctx->d_sv_show);
-    (void)hipFree(ctx->d_sv_showvar);
-    (void)hipFree(ctx->d_sv_fb);
-    ctx->d_sv_cur = ctx->d_sv_show = ctx->d_sv_showvar = ctx->d_sv_fb = nullptr;
-    ctx->cap_sv = 0;
 }
 
 // ---- albedo demodulation --------------------------------------------------
@@ -2732,8 +2318,8 @@ static void svgf_free_state(rvcp_ctx_t *ctx)
 // what both steps check before anything is enqueued (the restrictions of the G-buffer)
 static int albedo_checked(rvcp_ctx_t *ctx, uint32_t width, uint32_t height)
 {
-    if ((uint64_t)width * height >= (1ull << 31))
-        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    int rc;
+    if ((rc = frame_size_checked(ctx, width, height)) != RVCP_OK) return rc;
     if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
         return fail(ctx, RVCP_E_UNSUPPORTED, "the G-buffer is implemented for the games101 integrator");
     if (!ctx->subs.empty())
@@ -2759,20 +2345,12 @@ static int impl_demodulate_async(rvcp_ctx_t *ctx, const void *d_lin, const void 
         return fail(ctx, RVCP_E_INVALID, "demodulate output overlaps an input");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    if (!ctx->evad0) {
-        HIP_TRY(ctx, hipEventCreate(&ctx->evad0));
-        HIP_TRY(ctx, hipEventCreate(&ctx->evad1));
-    }
-    if ((rc = svgf_order(ctx, s)) != RVCP_OK) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->evad0, s));
+    if ((rc = stage_begin(ctx, ST_DEMOD, s)) != RVCP_OK) return rc;
     if (rvcp_launch_demodulate((const float *)d_lin, d_gbuffer, ctx->d_albedo, ctx->n_mats,
                                (float *)d_out, (uint32_t)npx, s) != 0)
         return fail(ctx, RVCP_E_HIP, std::string("demodulate launch failed: ") +
                                          hipGetErrorString(hipGetLastError()));
-    HIP_TRY(ctx, hipEventRecord(ctx->evad1, s));
-    ctx->demod_recorded = true;
-    ctx->demod_pending = true;
-    return RVCP_OK;
+    return stage_end(ctx, ST_DEMOD, s);
 }
 
 static int impl_remodulate_async(rvcp_ctx_t *ctx, const void *d_irr, const void *d_gbuffer,
@@ -2785,51 +2363,24 @@ static int impl_remodulate_async(rvcp_ctx_t *ctx, const void *d_irr, const void 
     int rc;
     if ((rc = albedo_checked(ctx, width, height)) != RVCP_OK) return rc;
     const size_t npx = (size_t)width * height;
-    {
-        const DevRange in[2] = {{d_irr, npx * 12}, {d_gbuffer, npx * 32}};
-        const DevRange out[2] = {{d_lin_out, npx * 12}, {d_rgba8_out, npx * 4}};
-        const char *what = nullptr;
-        if (outputs_overlap(in, 2, out, 2, &what))
-            return fail(ctx, RVCP_E_INVALID, std::string("remodulate ") + what);
-    }
+    if ((rc = overlap_checked(ctx, "remodulate", {{d_irr, npx * 12}, {d_gbuffer, npx * 32}},
+                              {{d_lin_out, npx * 12}, {d_rgba8_out, npx * 4}})) != RVCP_OK)
+        return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    if (!ctx->evar0) {
-        HIP_TRY(ctx, hipEventCreate(&ctx->evar0));
-        HIP_TRY(ctx, hipEventCreate(&ctx->evar1));
-    }
-    if ((rc = svgf_order(ctx, s)) != RVCP_OK) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->evar0, s));
+    if ((rc = stage_begin(ctx, ST_REMOD, s)) != RVCP_OK) return rc;
     if (rvcp_launch_remodulate((const float *)d_irr, d_gbuffer, ctx->d_albedo, ctx->n_mats,
                                ctx->d_gamma, (float *)d_lin_out, (uint32_t *)d_rgba8_out,
                                (uint32_t)npx, s) != 0)
         return fail(ctx, RVCP_E_HIP, std::string("remodulate launch failed: ") +
                                          hipGetErrorString(hipGetLastError()));
-    HIP_TRY(ctx, hipEventRecord(ctx->evar1, s));
-    ctx->remod_recorded = true;
-    ctx->remod_pending = true;
-    return RVCP_OK;
+    return stage_end(ctx, ST_REMOD, s);
 }
 
 static int impl_albedo_wait(rvcp_ctx_t *ctx, float *demodulate_ms, float *remodulate_ms)
 {
-    if (!ctx) return RVCP_E_INVALID;
-    if (!ctx->demod_pending && !ctx->remod_pending)
-        return fail(ctx, RVCP_E_INVALID, "no albedo step in flight");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (demodulate_ms) *demodulate_ms = 0.0f;
-    if (remodulate_ms) *remodulate_ms = 0.0f;
-    if (ctx->demod_pending) {
-        HIP_TRY(ctx, hipEventSynchronize(ctx->evad1));
-        if (demodulate_ms) HIP_TRY(ctx, hipEventElapsedTime(demodulate_ms, ctx->evad0, ctx->evad1));
-        ctx->demod_pending = false;
-    }
-    if (ctx->remod_pending) {
-        HIP_TRY(ctx, hipEventSynchronize(ctx->evar1));
-        if (remodulate_ms) HIP_TRY(ctx, hipEventElapsedTime(remodulate_ms, ctx->evar0, ctx->evar1));
-        ctx->remod_pending = false;
-    }
-    return RVCP_OK;
+    return stage_wait2(ctx, ST_DEMOD, ST_REMOD, "no albedo step in flight", demodulate_ms,
+                       remodulate_ms);
 }
 
 static int impl_set_demodulation(rvcp_ctx_t *ctx, int on)
@@ -2840,8 +2391,8 @@ static int impl_set_demodulation(rvcp_ctx_t *ctx, int on)
     const bool want = on != 0;
     if (want == ctx->demodulation) return RVCP_OK;
     ctx->demodulation = want;
-    ctx->tp_valid = false;      // colour histories and irradiance histories do not mix
-    ctx->sv_valid = false;
+    // colour histories and irradiance histories do not mix
+    ctx->tp_hist.valid = ctx->sv_hist.valid = false;
     return RVCP_OK;
 }
 
@@ -2853,159 +2404,396 @@ static int impl_get_demodulation(rvcp_ctx_t *ctx, int *on)
     return RVCP_OK;
 }
 
+// ---- the chains: rvcp_render_denoised, rvcp_render_temporal, rvcp_render_svgf ----------------
+
+// What a stateful chain does for its resolve state `st` before it renders (the TAA switch is set,
+// or the upsampling scale is above 1: with_gbuf).  width x height is the size of the state's
+// frames (the OUTPUT size when upsampling), lw x lh the traced frame's, whose jitter this is;
+// `have` says whether the chain's own history continues.  *jpush becomes the jittered push of
+// this frame, *resume whether the resolve has a history.
+static int resolve_begin(rvcp_ctx_t *ctx, ResolveState &st, bool with_gbuf, bool have,
+                         const rvcp_push_constant_t *push, uint32_t width, uint32_t height,
+                         uint32_t lw, uint32_t lh, rvcp_push_constant_t *jpush, bool *resume)
+{
+    int rc;
+    if ((rc = reserve_resolve_state(ctx, st, (size_t)width * height, with_gbuf)) != RVCP_OK)
+        return rc;
+    *resume = have && st.hist.continues_at(width, height);
+    if (!*resume) st.counter = 0;       // the state is dropped with the chain's history
+    st.hist.valid = false;              // until this frame is complete
+    float j[2];
+    (void)impl_taa_jitter(st.counter, j);
+    if (impl_taa_jitter_push(push, lw, lh, j, jpush) != RVCP_OK)
+        return fail(ctx, RVCP_E_INVALID, "the camera's forward is zero or parallel to up");
+    return RVCP_OK;
+}
+
+// ... and behind its last step, with the TAA switch: the resolve of d_final under the unjittered
+// cameras into the state's free slot and d_rgba
+static int taa_chain_resolve(rvcp_ctx_t *ctx, ResolveState &st, bool resume,
+                             const rvcp_push_constant_t *push, const rvcp_temporal_view_t *base_view,
+                             const float *d_final, const void *d_gbuffer, uint32_t width,
+                             uint32_t height)
+{
+    const uint32_t prev = st.hist.slot, cur = prev ^ 1u;
+    const bool at_rest = resume &&
+                         std::memcmp(&st.hist.camera, &push->camera, sizeof(rvcp_camera_t)) == 0;
+    return impl_taa_resolve_async(ctx, at_rest ? nullptr : base_view,
+                                  at_rest ? nullptr : &st.hist.view, d_final, d_gbuffer,
+                                  resume ? st.d_res[prev] : nullptr,
+                                  resume ? st.d_aux[prev] : nullptr, width, height, nullptr,
+                                  st.d_res[cur], st.d_aux[cur], ctx->d_rgba, ctx->stream);
+}
+
+// ... or, with the upsampling scale: the output-size G-buffer through the unjittered camera when
+// it moved, and the upsampling of d_final (traced through jit_view) into the state's free slot
+// and d_rgba
+static int taau_chain_resolve(rvcp_ctx_t *ctx, ResolveState &st, bool resume,
+                              const rvcp_push_constant_t *push, const rvcp_temporal_view_t *base_view,
+                              const rvcp_temporal_view_t *jit_view, const float *d_final,
+                              uint32_t width, uint32_t height)
+{
+    const uint32_t prev = st.hist.slot, cur = prev ^ 1u;
+    const bool moved = resume &&
+                       std::memcmp(&st.hist.camera, &push->camera, sizeof(rvcp_camera_t)) != 0;
+    if (moved) {
+        const int rc = impl_render_gbuffer_async(ctx, push, width, height, st.d_gbuf, ctx->stream);
+        if (rc != RVCP_OK) return rc;
+    }
+    return impl_taa_upsample_async(ctx, ctx->taau_scale, jit_view, base_view,
+                                   moved ? &st.hist.view : nullptr, d_final,
+                                   moved ? st.d_gbuf : nullptr, resume ? st.d_res[prev] : nullptr,
+                                   resume ? st.d_aux[prev] : nullptr, width, height, nullptr,
+                                   st.d_res[cur], st.d_aux[cur], ctx->d_rgba, ctx->stream);
+}
+
+// The per-frame locals of a chain.  A chain is: render (the raw linear frame), G-buffer
+// [, demodulate in place], its own one or two steps [, remodulate] [, resolve or upsampling], in
+// this order on the context's stream; the last RGBA8 store overwrites the render's.
+struct ChainFrame {
+    const char *name = "";                          // for the error texts
+    const rvcp_push_constant_t *base_push = nullptr;    // the caller's camera
+    const rvcp_push_constant_t *push = nullptr;     // what the chain renders through (or &jpush)
+    rvcp_push_constant_t jpush;
+    // With the upsampling scale `up` above 1 (§4.14): width x height is the TRACED frame, the
+    // whole chain runs at that size, and out_w x out_h is what the last step writes
+    uint32_t up = 1, width = 0, height = 0, out_w = 0, out_h = 0;
+    size_t npx = 0, out_npx = 0;
+    rvcp_temporal_view_t view_now = {};             // of push, at the traced size
+    rvcp_temporal_view_t base_view = {};            // of base_push, at the output size
+    bool have = false;              // the chain's own history continues
+    bool same_camera = false;       // ... and needs no reprojection
+    // With the demodulation switch set (§4.12): the raw frame is demodulated in place right after
+    // the G-buffer, histories and filters are in irradiance and store nothing, and the fused
+    // remodulate + store writes the colour into the raw frame's buffer (free by then) and the
+    // RGBA8 frame.
+    bool demod = false;
+    // With the TAA switch set (§4.13), rs = the chain's state of it: everything runs through the
+    // jittered camera jpush, the chain's own history always reprojects (through the jittered
+    // cameras), no step stores RGBA8, and the resolve of the final linear colour under the
+    // unjittered cameras ends the frame.  With the upsampling scale above 1 the upsampling step
+    // takes the resolve's place.
+    ResolveState *rs = nullptr;
+    bool resume = false;            // the resolve has a history
+    uint32_t *store = nullptr;      // the chain's own RGBA8 store
+    uint32_t enqueued = 0;          // stage_bit()s of the own steps the chain has enqueued
+};
+
+// what every chain checks first
+static int chain_args_checked(rvcp_ctx_t *ctx, const char *name, const rvcp_push_constant_t *push,
+                              const uint8_t *out_rgba8, uint32_t width, uint32_t height,
+                              bool bad_flags)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!push || !out_rgba8 || width == 0 || height == 0 ||
+        (uint64_t)width * height >= (1ull << 31) || bad_flags)
+        return fail(ctx, RVCP_E_INVALID, std::string("invalid ") + name + " arguments");
+    if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
+        return fail(ctx, RVCP_E_UNSUPPORTED, "the G-buffer is implemented for the games101 integrator");
+    if (!ctx->subs.empty())
+        return fail(ctx, RVCP_E_UNSUPPORTED, std::string(name) + " drives one GPU (n_gpus = 1)");
+    if (ctx->pending)
+        return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    return RVCP_OK;
+}
+
+static int chain_bad_camera(rvcp_ctx_t *ctx, const ChainFrame &F)
+{
+    return fail(ctx, RVCP_E_INVALID,
+                std::string(F.name) + ": the camera's forward is zero or parallel to up");
+}
+
+// A stateful chain's frame: the sizes, the camera's view, the device and the RGBA8 staging
+static int chain_begin(rvcp_ctx_t *ctx, ChainFrame &F, const char *name,
+                       const rvcp_push_constant_t *push, uint32_t width, uint32_t height)
+{
+    F.name = name;
+    F.base_push = F.push = push;
+    F.up = ctx->taau_scale;
+    F.out_w = width;
+    F.out_h = height;
+    if (F.up > 1) {
+        if (width % F.up != 0 || height % F.up != 0)
+            return fail(ctx, RVCP_E_INVALID, std::string(name) +
+                        ": the TAA upsampling scale must divide width and height");
+        width /= F.up;
+        height /= F.up;
+    }
+    F.width = width;
+    F.height = height;
+    if (impl_temporal_view_from_push(push, width, height, &F.view_now) != RVCP_OK)
+        return chain_bad_camera(ctx, F);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    F.npx = (size_t)width * height;
+    F.out_npx = (size_t)F.out_w * F.out_h;
+    return grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, F.out_npx, 4);
+}
+
+// ... and, once the chain's buffers hold F.npx pixels, what continues: the chain's history `hist`
+// and, with the TAA switch or the upsampling scale, its state of that (taa_st / taau_st), whose
+// jittered camera the frame is then rendered through.  Both are invalid until chain_commit.
+static int chain_history(rvcp_ctx_t *ctx, ChainFrame &F, History &hist, ResolveState &taa_st,
+                         ResolveState &taau_st)
+{
+    F.have = hist.continues_at(F.width, F.height);
+    F.demod = ctx->demodulation;
+    F.base_view = F.view_now;
+    if (F.up > 1 &&
+        impl_temporal_view_from_push(F.base_push, F.out_w, F.out_h, &F.base_view) != RVCP_OK)
+        return chain_bad_camera(ctx, F);
+    if (ctx->taa || F.up > 1) {
+        F.rs = F.up > 1 ? &taau_st : &taa_st;
+        const int rc = resolve_begin(ctx, *F.rs, F.up > 1, F.have, F.base_push, F.out_w, F.out_h,
+                                     F.width, F.height, &F.jpush, &F.resume);
+        if (rc != RVCP_OK) return rc;
+        F.push = &F.jpush;
+        if (impl_temporal_view_from_push(F.push, F.width, F.height, &F.view_now) != RVCP_OK)
+            return chain_bad_camera(ctx, F);
+    }
+    F.same_camera = !F.rs && F.have &&
+                    std::memcmp(&hist.camera, &F.push->camera, sizeof(rvcp_camera_t)) == 0;
+    F.store = F.rs ? nullptr : ctx->d_rgba;
+    hist.valid = false;
+    return RVCP_OK;
+}
+
+// Behind the render of the raw frame into d_cur: the G-buffer [and the demodulation in place]
+static int chain_gbuffer(rvcp_ctx_t *ctx, const ChainFrame &F, float *d_cur, void *d_gbuf)
+{
+    int rc = impl_render_gbuffer_async(ctx, F.push, F.width, F.height, d_gbuf, ctx->stream);
+    if (rc == RVCP_OK && F.demod)
+        rc = impl_demodulate_async(ctx, d_cur, d_gbuf, F.width, F.height, d_cur, ctx->stream);
+    return rc;
+}
+
+// Behind the chain's own steps, which went `rc` and left d_out: [the remodulation into d_cur]
+// [and the resolve or the upsampling] of *d_final, the displayed linear frame.  After a failure
+// anywhere behind the render the chain waits for what it enqueued -- the render always, its own
+// steps if they were, the albedo steps if pending -- so that nothing stays pending, and the first
+// error's text is kept.
+static int chain_tail(rvcp_ctx_t *ctx, ChainFrame &F, int rc, const float *d_out, const void *d_gbuf,
+                      float *d_cur, const float **d_final)
+{
+    if (rc == RVCP_OK && F.demod)
+        rc = impl_remodulate_async(ctx, d_out, d_gbuf, F.width, F.height, d_cur, F.store,
+                                   ctx->stream);
+    *d_final = F.demod ? d_cur : d_out;
+    if (rc == RVCP_OK && F.rs)
+        rc = F.up > 1 ? taau_chain_resolve(ctx, *F.rs, F.resume, F.base_push, &F.base_view,
+                                           &F.view_now, *d_final, F.out_w, F.out_h)
+                      : taa_chain_resolve(ctx, *F.rs, F.resume, F.base_push, &F.base_view, *d_final,
+                                          d_gbuf, F.width, F.height);
+    if (rc == RVCP_OK) return RVCP_OK;
+    const std::string why = ctx->err;
+    (void)rvcp_wait(ctx, nullptr);
+    if (F.enqueued & stage_bit(ST_TEMPORAL)) (void)impl_temporal_wait(ctx, nullptr);
+    if (F.enqueued & stage_bit(ST_DENOISE)) (void)impl_denoise_wait(ctx, nullptr);
+    if (F.enqueued & stage_bit(ST_SVGF_ACC)) (void)impl_svgf_wait(ctx, nullptr, nullptr);
+    if (ctx->stage[ST_DEMOD].pending || ctx->stage[ST_REMOD].pending)
+        (void)impl_albedo_wait(ctx, nullptr, nullptr);
+    ctx->err = why;
+    return rc;
+}
+
+// Behind the waits for the render and the chain's own steps: those for the albedo steps and the
+// resolve, and the frame's copies to the host
+static int chain_end(rvcp_ctx_t *ctx, const ChainFrame &F, const float *d_final, uint8_t *out_rgba8,
+                     float *out_linear_rgb)
+{
+    int rc;
+    if (F.demod && (rc = impl_albedo_wait(ctx, nullptr, nullptr)) != RVCP_OK) return rc;
+    if (F.rs) {
+        if ((rc = F.up > 1 ? impl_taau_wait(ctx, nullptr) : impl_taa_wait(ctx, nullptr)) != RVCP_OK)
+            return rc;
+        d_final = F.rs->d_res[F.rs->hist.slot ^ 1u];
+    }
+    HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, F.out_npx * 4, hipMemcpyDeviceToHost));
+    if (out_linear_rgb)
+        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, d_final, F.out_npx * 12, hipMemcpyDeviceToHost));
+    return RVCP_OK;
+}
+
+// the frame is complete
+static void chain_commit(const ChainFrame &F, History &hist)
+{
+    hist.commit(F.width, F.height, F.push->camera, F.view_now);
+    if (F.rs) {
+        F.rs->hist.commit(F.out_w, F.out_h, F.base_push->camera, F.base_view);
+        F.rs->counter += 1;
+    }
+}
+
+static int impl_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                                uint32_t height, const rvcp_denoise_params_t *params,
+                                uint8_t *out_rgba8, float *out_linear_rgb, rvcp_stats_t *stats,
+                                float *denoise_ms)
+{
+    int rc;
+    if ((rc = chain_args_checked(ctx, "render_denoised", push, out_rgba8, width, height,
+                                 false)) != RVCP_OK)
+        return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t npx = (size_t)width * height;
+    if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, npx, 4)) != RVCP_OK) return rc;
+    if ((rc = grow(ctx, &ctx->d_gbuf, &ctx->cap_gbuf, npx, sizeof(rvcp_gbuffer_texel_t))) != RVCP_OK)
+        return rc;
+    if (ctx->cap_dn_io < npx) {
+        dev_free(ctx->d_dn_in);
+        dev_free(ctx->d_dn_out);
+        ctx->cap_dn_io = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_dn_in, npx * 12));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_dn_out, npx * 12));
+        ctx->cap_dn_io = npx;
+    }
+    ChainFrame F;               // (stateless: no history, no resolve)
+    F.push = push;
+    F.width = width;
+    F.height = height;
+    F.out_npx = npx;
+    F.demod = ctx->demodulation;
+    F.store = ctx->d_rgba;
+    if ((rc = rvcp_render_async(ctx, push, width, height, ctx->d_rgba, ctx->d_dn_in, ctx->stream)) != RVCP_OK)
+        return rc;
+    rc = chain_gbuffer(ctx, F, ctx->d_dn_in, ctx->d_gbuf);
+    if (rc == RVCP_OK) {
+        rc = impl_denoise_async(ctx, ctx->d_dn_in, ctx->d_gbuf, width, height, params,
+                                ctx->d_dn_out, F.demod ? nullptr : F.store, ctx->stream);
+        if (rc == RVCP_OK) F.enqueued |= stage_bit(ST_DENOISE);
+    }
+    const float *d_final;
+    if ((rc = chain_tail(ctx, F, rc, ctx->d_dn_out, ctx->d_gbuf, ctx->d_dn_in, &d_final)) != RVCP_OK)
+        return rc;
+    if ((rc = rvcp_wait(ctx, stats)) != RVCP_OK) return rc;
+    if ((rc = impl_denoise_wait(ctx, denoise_ms)) != RVCP_OK) return rc;
+    return chain_end(ctx, F, d_final, out_rgba8, out_linear_rgb);
+}
+
+static int impl_render_temporal(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                                uint32_t height, const rvcp_temporal_params_t *tparams,
+                                uint32_t flags, const rvcp_denoise_params_t *dparams,
+                                uint8_t *out_rgba8, float *out_linear_rgb,
+                                uint32_t *out_history_len, rvcp_stats_t *stats, float *temporal_ms,
+                                float *denoise_ms)
+{
+    int rc;
+    if ((rc = chain_args_checked(ctx, "render_temporal", push, out_rgba8, width, height,
+                                 (flags & ~RVCP_TEMPORAL_DENOISE) != 0)) != RVCP_OK)
+        return rc;
+    ChainFrame F;
+    if ((rc = chain_begin(ctx, F, "render_temporal", push, width, height)) != RVCP_OK) return rc;
+    const bool denoise = (flags & RVCP_TEMPORAL_DENOISE) != 0;
+    if ((rc = reserve_temporal_state(ctx, F.npx)) != RVCP_OK) return rc;
+    if (denoise &&
+        (rc = grow(ctx, (void **)&ctx->d_tp_show, &ctx->cap_tp_show, F.npx, 12)) != RVCP_OK)
+        return rc;
+    History &hist = ctx->tp_hist;
+    if ((rc = chain_history(ctx, F, hist, ctx->taa_tp, ctx->taau_tp)) != RVCP_OK) return rc;
+    const uint32_t prev = hist.slot, cur = prev ^ 1u;
+    float *const d_cur = ctx->d_tp_cur, *const d_acc = ctx->d_tp_lin[cur];
+    void *const d_gbuf = ctx->d_tp_gbuf[cur];
+    if ((rc = rvcp_render_async(ctx, F.push, F.width, F.height, ctx->d_rgba, d_cur, ctx->stream)) != RVCP_OK)
+        return rc;
+    // accumulation [, filter of the accumulated frame: the history stays unfiltered]
+    rc = chain_gbuffer(ctx, F, d_cur, d_gbuf);
+    if (rc == RVCP_OK) {
+        rc = impl_temporal_accumulate_async(
+            ctx, F.same_camera ? nullptr : &hist.view, d_cur, d_gbuf,
+            F.have ? ctx->d_tp_lin[prev] : nullptr, F.have ? ctx->d_tp_gbuf[prev] : nullptr,
+            F.have ? ctx->d_tp_len[prev] : nullptr, F.width, F.height, tparams, d_acc,
+            ctx->d_tp_len[cur], denoise || F.demod ? nullptr : F.store, ctx->stream);
+        if (rc == RVCP_OK) F.enqueued |= stage_bit(ST_TEMPORAL);
+    }
+    if (rc == RVCP_OK && denoise) {
+        rc = impl_denoise_async(ctx, d_acc, d_gbuf, F.width, F.height, dparams, ctx->d_tp_show,
+                                F.demod ? nullptr : F.store, ctx->stream);
+        if (rc == RVCP_OK) F.enqueued |= stage_bit(ST_DENOISE);
+    }
+    const float *d_final;
+    if ((rc = chain_tail(ctx, F, rc, denoise ? ctx->d_tp_show : d_acc, d_gbuf, d_cur,
+                         &d_final)) != RVCP_OK)
+        return rc;
+    if ((rc = rvcp_wait(ctx, stats)) != RVCP_OK) return rc;
+    if ((rc = impl_temporal_wait(ctx, temporal_ms)) != RVCP_OK) return rc;
+    if (denoise_ms) *denoise_ms = 0.0f;
+    if (denoise && (rc = impl_denoise_wait(ctx, denoise_ms)) != RVCP_OK) return rc;
+    if ((rc = chain_end(ctx, F, d_final, out_rgba8, out_linear_rgb)) != RVCP_OK) return rc;
+    if (out_history_len)
+        HIP_TRY(ctx, hipMemcpy(out_history_len, ctx->d_tp_len[cur], F.npx * 4, hipMemcpyDeviceToHost));
+    chain_commit(F, hist);
+    return RVCP_OK;
+}
+
 static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
                             uint32_t height, const rvcp_temporal_params_t *tparams,
                             const rvcp_svgf_params_t *sparams, uint32_t flags, uint8_t *out_rgba8,
                             float *out_linear_rgb, float *out_variance, uint32_t *out_history_len,
                             rvcp_stats_t *stats, float *accumulate_ms, float *filter_ms)
 {
-    if (!ctx) return RVCP_E_INVALID;
-    if (!push || !out_rgba8 || width == 0 || height == 0 ||
-        (uint64_t)width * height >= (1ull << 31) || (flags & ~RVCP_SVGF_FEEDBACK))
-        return fail(ctx, RVCP_E_INVALID, "invalid render_svgf arguments");
-    if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
-        return fail(ctx, RVCP_E_UNSUPPORTED, "the G-buffer is implemented for the games101 integrator");
-    if (!ctx->subs.empty())
-        return fail(ctx, RVCP_E_UNSUPPORTED, "render_svgf drives one GPU (n_gpus = 1)");
-    if (ctx->pending)
-        return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
-    // With the upsampling scale above 1 (§4.14): width x height below is the TRACED frame, the
-    // whole chain runs at that size, and out_w x out_h is what the last step writes
-    const uint32_t up = ctx->taau_scale, out_w = width, out_h = height;
-    if (up > 1) {
-        if (width % up != 0 || height % up != 0)
-            return fail(ctx, RVCP_E_INVALID, "render_svgf: the TAA upsampling scale must divide width and height");
-        width /= up;
-        height /= up;
-    }
-    rvcp_temporal_view_t view_now;
-    if (impl_temporal_view_from_push(push, width, height, &view_now) != RVCP_OK)
-        return fail(ctx, RVCP_E_INVALID, "render_svgf: the camera's forward is zero or parallel to up");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool feedback = (flags & RVCP_SVGF_FEEDBACK) != 0;
-    const size_t npx = (size_t)width * height, out_npx = (size_t)out_w * out_h;
     int rc;
-    if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, out_npx, 4)) != RVCP_OK) return rc;
-    if (ctx->cap_sv < npx) {            // (a larger frame: the history is dropped with its buffers)
-        ctx->sv_valid = false;
-        svgf_free_state(ctx);
-        for (int i = 0; i < 2; ++i) {
-            HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_lin[i], npx * 12));
-            HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_mom[i], npx * 8));
-            HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_len[i], npx * 4));
-            HIP_TRY(ctx, hipMalloc(&ctx->d_sv_gbuf[i], npx * sizeof(rvcp_gbuffer_texel_t)));
-        }
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_cur, npx * 12));
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_show, npx * 12));
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_showvar, npx * 4));
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_sv_fb, npx * 12));
-        ctx->cap_sv = npx;
-    }
-    const bool have = ctx->sv_valid && ctx->sv_width == width && ctx->sv_height == height;
-    // With the TAA switch set (§4.13): as rvcp_render_temporal
-    // With the upsampling scale above 1 (§4.14) the upsampling step takes the resolve's place:
-    // base_view is then the unjittered camera at the output size
-    const bool taa = ctx->taa || up > 1;
-    const rvcp_push_constant_t *const base_push = push;
-    rvcp_temporal_view_t base_view = view_now;
-    if (up > 1 && impl_temporal_view_from_push(push, out_w, out_h, &base_view) != RVCP_OK)
-        return fail(ctx, RVCP_E_INVALID, "render_svgf: the camera's forward is zero or parallel to up");
-    rvcp_push_constant_t jpush;
-    bool taa_resume = false;
-    if (taa) {
-        rc = up > 1 ? taau_chain_begin(ctx, ctx->taau_sv, have, base_push, out_w, out_h, width,
-                                       height, &jpush, &taa_resume)
-                    : taa_chain_begin(ctx, ctx->taa_sv, have, base_push, width, height, &jpush,
-                                      &taa_resume);
-        if (rc != RVCP_OK)
-            return rc;
-        push = &jpush;
-        if (impl_temporal_view_from_push(push, width, height, &view_now) != RVCP_OK)
-            return fail(ctx, RVCP_E_INVALID, "render_svgf: the camera's forward is zero or parallel to up");
-    }
-    const bool same_camera = !taa && have &&
-                             std::memcmp(&ctx->sv_camera, &push->camera, sizeof(rvcp_camera_t)) == 0;
-    uint32_t *const store = taa ? nullptr : ctx->d_rgba;    // the chain's own RGBA8 store
-    const uint32_t prev = ctx->sv_slot, cur = prev ^ 1u;
-    ctx->sv_valid = false;              // until this frame is complete
-    // render (raw linear frame), G-buffer, accumulation, filter, in this order on the context's
-    // stream; the filter's RGBA8 store overwrites the render's
-    if ((rc = rvcp_render_async(ctx, push, width, height, ctx->d_rgba, ctx->d_sv_cur, ctx->stream)) != RVCP_OK)
+    if ((rc = chain_args_checked(ctx, "render_svgf", push, out_rgba8, width, height,
+                                 (flags & ~RVCP_SVGF_FEEDBACK) != 0)) != RVCP_OK)
         return rc;
-    // With the demodulation switch set (§4.12): the raw frame is demodulated in place right after
-    // the G-buffer, colour history, moments and filter are in irradiance and store nothing, and
-    // the fused remodulate + store writes the colour into d_sv_cur (free by then) and the RGBA8
-    // frame.
-    const bool demod = ctx->demodulation;
-    bool enqueued = false;
-    rc = impl_render_gbuffer_async(ctx, push, width, height, ctx->d_sv_gbuf[cur], ctx->stream);
-    if (rc == RVCP_OK && demod)
-        rc = impl_demodulate_async(ctx, ctx->d_sv_cur, ctx->d_sv_gbuf[cur], width, height,
-                                   ctx->d_sv_cur, ctx->stream);
+    ChainFrame F;
+    if ((rc = chain_begin(ctx, F, "render_svgf", push, width, height)) != RVCP_OK) return rc;
+    const bool feedback = (flags & RVCP_SVGF_FEEDBACK) != 0;
+    if ((rc = reserve_svgf_state(ctx, F.npx)) != RVCP_OK) return rc;
+    History &hist = ctx->sv_hist;
+    if ((rc = chain_history(ctx, F, hist, ctx->taa_sv, ctx->taau_sv)) != RVCP_OK) return rc;
+    const uint32_t prev = hist.slot, cur = prev ^ 1u;
+    float *const d_cur = ctx->d_sv_cur;
+    void *const d_gbuf = ctx->d_sv_gbuf[cur];
+    if ((rc = rvcp_render_async(ctx, F.push, F.width, F.height, ctx->d_rgba, d_cur, ctx->stream)) != RVCP_OK)
+        return rc;
+    // accumulation of colour and moments, then the filter
+    rc = chain_gbuffer(ctx, F, d_cur, d_gbuf);
     if (rc == RVCP_OK) {
         rc = impl_svgf_accumulate_async(
-            ctx, same_camera ? nullptr : &ctx->sv_view, ctx->d_sv_cur, ctx->d_sv_gbuf[cur],
-            have ? ctx->d_sv_lin[prev] : nullptr, have ? ctx->d_sv_gbuf[prev] : nullptr,
-            have ? ctx->d_sv_len[prev] : nullptr, have ? ctx->d_sv_mom[prev] : nullptr, width,
-            height, tparams, sparams, ctx->d_sv_lin[cur], ctx->d_sv_len[cur], ctx->d_sv_mom[cur],
+            ctx, F.same_camera ? nullptr : &hist.view, d_cur, d_gbuf,
+            F.have ? ctx->d_sv_lin[prev] : nullptr, F.have ? ctx->d_sv_gbuf[prev] : nullptr,
+            F.have ? ctx->d_sv_len[prev] : nullptr, F.have ? ctx->d_sv_mom[prev] : nullptr, F.width,
+            F.height, tparams, sparams, ctx->d_sv_lin[cur], ctx->d_sv_len[cur], ctx->d_sv_mom[cur],
             nullptr, ctx->stream);
-        enqueued = enqueued || rc == RVCP_OK;
+        if (rc == RVCP_OK) F.enqueued |= stage_bit(ST_SVGF_ACC);   // (its wait is the filter's too)
     }
-    if (rc == RVCP_OK) {
+    if (rc == RVCP_OK)
         rc = impl_svgf_filter_async(ctx, ctx->d_sv_lin[cur], ctx->d_sv_mom[cur], ctx->d_sv_len[cur],
-                                    ctx->d_sv_gbuf[cur], width, height, sparams, ctx->d_sv_show,
+                                    d_gbuf, F.width, F.height, sparams, ctx->d_sv_show,
                                     ctx->d_sv_showvar, feedback ? ctx->d_sv_fb : nullptr,
-                                    demod ? nullptr : store, ctx->stream);
-    }
-    if (rc == RVCP_OK && demod)
-        rc = impl_remodulate_async(ctx, ctx->d_sv_show, ctx->d_sv_gbuf[cur], width, height,
-                                   ctx->d_sv_cur, store, ctx->stream);
-    const float *d_final = demod ? ctx->d_sv_cur : ctx->d_sv_show;     // the displayed linear frame
-    bool resolve_enqueued = false;
-    if (rc == RVCP_OK && taa) {
-        rc = up > 1 ? taau_chain_resolve(ctx, ctx->taau_sv, taa_resume, base_push, &base_view,
-                                         &view_now, d_final, out_w, out_h)
-                    : taa_chain_resolve(ctx, ctx->taa_sv, taa_resume, base_push, &base_view, d_final,
-                                        ctx->d_sv_gbuf[cur], width, height);
-        resolve_enqueued = rc == RVCP_OK;
-    }
-    if (rc != RVCP_OK) {
-        const std::string why = ctx->err;
-        (void)rvcp_wait(ctx, nullptr);          // the render is enqueued: leave nothing pending
-        if (enqueued) (void)impl_svgf_wait(ctx, nullptr, nullptr);
-        albedo_drain(ctx);
-        ctx->err = why;
-        return rc;
-    }
+                                    F.demod ? nullptr : F.store, ctx->stream);
+    const float *d_final;
+    if ((rc = chain_tail(ctx, F, rc, ctx->d_sv_show, d_gbuf, d_cur, &d_final)) != RVCP_OK) return rc;
     if ((rc = rvcp_wait(ctx, stats)) != RVCP_OK) return rc;
     if ((rc = impl_svgf_wait(ctx, accumulate_ms, filter_ms)) != RVCP_OK) return rc;
-    if (demod && (rc = impl_albedo_wait(ctx, nullptr, nullptr)) != RVCP_OK) return rc;
-    if (resolve_enqueued) {
-        if ((rc = up > 1 ? impl_taau_wait(ctx, nullptr) : impl_taa_wait(ctx, nullptr)) != RVCP_OK)
-            return rc;
-        d_final = up > 1 ? ctx->taau_sv.d_res[ctx->taau_sv.slot ^ 1u]
-                         : ctx->taa_sv.d_res[ctx->taa_sv.slot ^ 1u];
-    }
-    HIP_TRY(ctx, hipMemcpy(out_rgba8, ctx->d_rgba, out_npx * 4, hipMemcpyDeviceToHost));
-    if (out_linear_rgb)
-        HIP_TRY(ctx, hipMemcpy(out_linear_rgb, d_final, out_npx * 12, hipMemcpyDeviceToHost));
+    if ((rc = chain_end(ctx, F, d_final, out_rgba8, out_linear_rgb)) != RVCP_OK) return rc;
     if (out_variance)
-        HIP_TRY(ctx, hipMemcpy(out_variance, ctx->d_sv_showvar, npx * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_variance, ctx->d_sv_showvar, F.npx * 4, hipMemcpyDeviceToHost));
     if (out_history_len)
-        HIP_TRY(ctx, hipMemcpy(out_history_len, ctx->d_sv_len[cur], npx * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_history_len, ctx->d_sv_len[cur], F.npx * 4, hipMemcpyDeviceToHost));
     // feedback: the next frame's colour history is pass 0's output (moments and lengths stay)
     if (feedback) std::swap(ctx->d_sv_lin[cur], ctx->d_sv_fb);
-    ctx->sv_slot = cur;
-    ctx->sv_width = width;
-    ctx->sv_height = height;
-    ctx->sv_camera = push->camera;
-    ctx->sv_view = view_now;
-    ctx->sv_valid = true;
-    if (up > 1) taau_chain_commit(ctx->taau_sv, base_push, &base_view, out_w, out_h);
-    else if (taa) taa_chain_commit(ctx->taa_sv, base_push, &base_view, width, height);
+    chain_commit(F, hist);
     return RVCP_OK;
 }
-
 static int impl_assemble_frame_async(rvcp_ctx_t *ctx, const void *d_gathered, uint32_t slot_rows,
                               uint32_t width, uint32_t height, uint32_t shard_count,
                               void *d_frame, void *stream)

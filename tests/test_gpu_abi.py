@@ -61,6 +61,43 @@ def test_destroy_with_frame_pending(cornell):
     assert np.array_equal(a.cpu().numpy().view(np.uint8).reshape(H, W, 4), ref)
 
 
+def test_destroy_with_post_process_steps_never_waited_for(cornell):
+    """rvcp_destroy synchronises the end event of every post-process step that was enqueued and
+    never waited for (here on the caller's side stream): it returns RVCP_OK, and the caller's
+    buffers hold what the same calls leave when they are waited for."""
+    torch = pytest.importorskip("torch")
+    W = H = 16
+    push = cornell.push_constant(TIME)
+
+    def run(waited):
+        buf = {k: torch.zeros(W * H * n, dtype=torch.uint8, device="cuda")
+               for k, n in (("rgba", 4), ("lin", 12), ("g", 32), ("dn", 12), ("acc", 12), ("len", 4))}
+        p = {k: t.data_ptr() for k, t in buf.items()}
+        side = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        rt = rvcp_amd.RayTracer(spp=2)
+        rt.upload_scene(cornell)
+        rt.render_async(push, W, H, p["rgba"], p["lin"])
+        rt.render_gbuffer_async(push, W, H, p["g"])
+        rt.wait()
+        torch.cuda.synchronize()                           # (the G-buffer has no wait of its own)
+        rt.denoise_async(p["lin"], p["g"], W, H, p["dn"], stream=side.cuda_stream)
+        rt.temporal_accumulate_async(None, p["lin"], p["g"], 0, 0, 0, W, H, p["acc"], p["len"],
+                                     stream=side.cuda_stream)
+        if waited:
+            rt.denoise_wait()
+            rt.temporal_wait()
+        assert rt.close() == rvcp_amd.abi.RVCP_OK
+        out = {k: buf[k].cpu().numpy().copy() for k in ("dn", "acc", "len")}
+        torch.cuda.synchronize()
+        return out
+
+    got, want = run(waited=False), run(waited=True)
+    assert want["dn"].any() and want["len"].any()
+    for k in want:
+        assert np.array_equal(got[k], want[k]), k
+
+
 @pytest.mark.parametrize("W,H", [(128, 96), (77, 45)])
 def test_rccl_gather_world1(cornell, W, H):
     """rvcp_rccl_init + rvcp_render_shard_async + rvcp_gather_frame_async (ncclGather to

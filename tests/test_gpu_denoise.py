@@ -243,6 +243,25 @@ def test_gbuffer_unsupported_contexts(cornell, kw):
         assert e.value.code == abi.RVCP_E_UNSUPPORTED
 
 
+def test_bad_filter_parameters_midway_leave_nothing_pending(cornell):
+    """render_denoised whose filter is rejected after the render was enqueued leaves neither a
+    frame nor a filter pending, and the context goes on as before."""
+    L = abi.load()
+    W = H = 16
+    with rvcp_amd.RayTracer(spp=2) as rt:
+        rt.upload_scene(cornell)
+        raw = rt.render(W, H, 1.0)
+        good = rt.render_denoised(W, H, 2.0, want_linear=True)
+        with pytest.raises(abi.RvcpError) as e:
+            rt.render_denoised(W, H, 3.0, abi.make_denoise_params(iterations=9))
+        assert e.value.code == abi.RVCP_E_INVALID and "denoise iterations" in str(e.value)
+        assert L.rvcp_denoise_wait(rt.handle, None) == abi.RVCP_E_INVALID
+        assert b"in flight" in L.rvcp_last_error(rt.handle)
+        assert np.array_equal(rt.render(W, H, 1.0), raw)
+        again = rt.render_denoised(W, H, 2.0, want_linear=True)
+    assert np.array_equal(again[0], good[0]) and np.array_equal(bits(again[1]), bits(good[1]))
+
+
 def test_denoise_is_ordered_behind_a_pending_render(cornell, cornell_arrays):
     """A render pending on the context is no error for the denoiser: on the same stream the
     filter reads the frame that render leaves."""

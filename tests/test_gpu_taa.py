@@ -352,6 +352,49 @@ def test_switch_off_equals_a_context_that_never_heard_of_taa(pair, cornell):
         assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), k
 
 
+FAILED_CHAINS = [(False, False), (True, False), (False, True)]       # svgf, demod
+FAILED_IDS = ["temporal", "svgf", "temporal-demodulated"]
+
+
+def failed_chain_restarts(cornell, svgf, demod, switch, W, H):
+    """Context A renders two frames and fails midway in the third, on bad filter parameters behind
+    the render; its frames at t4 and t5 must then be, byte for byte, those of a fresh context B
+    that renders nothing else: the failure drops the chain's history and the resolve state, and
+    the jitter sequence starts over.  switch(rt) sets the switch under test."""
+    bad_d, bad_s = abi.make_denoise_params(iterations=9), abi.make_svgf_params(iterations=9)
+
+    def frame(rt, t, bad=False):
+        if svgf:
+            return rt.render_svgf(W, H, t, svgf=bad_s if bad else None, want_linear=True)
+        return rt.render_temporal(W, H, t, denoise=bad_d if bad else abi.make_denoise_params(),
+                                  want_linear=True)
+
+    def context():
+        rt = rvcp_amd.RayTracer(spp=2)
+        rt.upload_scene(cornell)
+        rt.demodulation = demod
+        switch(rt)
+        return rt
+
+    with context() as a, context() as b:
+        frame(a, 1.0)
+        frame(a, 2.0)
+        with pytest.raises(abi.RvcpError) as e:
+            frame(a, 3.0, bad=True)
+        assert e.value.code == abi.RVCP_E_INVALID and "iterations" in str(e.value)
+        for t in (4.0, 5.0):
+            (rgba, lin), (want_rgba, want_lin) = frame(a, t), frame(b, t)
+            assert rgba.shape == (H, W, 4) and lin.shape == (H, W, 3)
+            assert rgba.tobytes() == want_rgba.tobytes() and lin.tobytes() == want_lin.tobytes(), t
+
+
+@pytest.mark.parametrize("svgf,demod", FAILED_CHAINS, ids=FAILED_IDS)
+def test_a_failed_chain_drops_the_taa_state_and_restarts_the_jitter(cornell, svgf, demod):
+    def switch(rt):
+        rt.taa = True
+    failed_chain_restarts(cornell, svgf, demod, switch, 16, 16)
+
+
 # ---------------------------------------------------------------------------- 4. quality
 def test_anti_aliasing_gate_64sq_on_gpu_gbuffers(pair, cornell):
     """The CPU gate (test_taa_cpu) at 64 x 64 on the library's own G-buffers, with the resolved

@@ -17,7 +17,8 @@ import rvcp_amd
 from rvcp_amd import abi
 from test_gpu_albedo import (assert_same, bits, blank, dev, floats, gpu_demodulate, gpu_remodulate,
                              gpu_svgf, gpu_temporal)
-from test_gpu_taa import Composition, chain_frame, chain_pushes, gpu_gbuffer
+from test_gpu_taa import (FAILED_CHAINS, FAILED_IDS, Composition, chain_frame, chain_pushes,
+                          failed_chain_restarts, gpu_gbuffer)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -406,6 +407,13 @@ def test_scale_1_equals_a_context_that_never_heard_of_upsampling(pair, cornell):
     assert len(got) == len(want)
     for k, (a, b) in enumerate(zip(got, want)):
         assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), k
+
+
+@pytest.mark.parametrize("svgf,demod", FAILED_CHAINS, ids=FAILED_IDS)
+def test_a_failed_chain_drops_the_upsampling_state_and_restarts_the_jitter(cornell, svgf, demod):
+    def switch(rt):
+        rt.taa_upsample = 2
+    failed_chain_restarts(cornell, svgf, demod, switch, 32, 32)      # traced at 16 x 16
 
 
 # ---------------------------------------------------------------------------- 4. quality

@@ -309,6 +309,25 @@ def test_render_temporal_unsupported_contexts(cornell, kw):
         assert e.value.code == abi.RVCP_E_UNSUPPORTED
 
 
+def test_bad_filter_parameters_midway_drain_the_chain(cornell):
+    """A call whose filter is rejected after the render and the temporal step were enqueued waits
+    for what it enqueued, leaves nothing pending and drops the history."""
+    L = abi.load()
+    W = H = 16
+    with rvcp_amd.RayTracer(spp=2) as rt:
+        rt.upload_scene(cornell)
+        assert rt.render_temporal(W, H, 1.0, want_history=True)[1].max() == 1
+        assert rt.render_temporal(W, H, 2.0, want_history=True)[1].max() == 2
+        with pytest.raises(abi.RvcpError) as e:
+            rt.render_temporal(W, H, 3.0, denoise=abi.make_denoise_params(iterations=9))
+        assert e.value.code == abi.RVCP_E_INVALID and "denoise iterations" in str(e.value)
+        for wait in (L.rvcp_temporal_wait, L.rvcp_denoise_wait):      # the chain drained its step
+            assert wait(rt.handle, None) == abi.RVCP_E_INVALID
+            assert b"in flight" in L.rvcp_last_error(rt.handle)
+        rt.render(W, H, 4.0)                               # nothing is left pending
+        assert rt.render_temporal(W, H, 5.0, want_history=True)[1].max() == 1
+
+
 def test_accumulate_is_ordered_behind_a_pending_render(cornell, cornell_arrays):
     """A render pending on the context is no error: on the same stream the step reads the frame
     and the texels that render and the G-buffer pass leave."""
