@@ -13,7 +13,8 @@ Meshes ([F, 3, 3] float32 positions, face materials, a camera; `scene()` makes t
               that early split clipping repeats duplicated faces across leaves;
   degenerate  point and line triangles, a sheet of coplanar triangles, 200 identical triangles
               (the median split's depth bound) and one triangle 1e6 cluster diagonals away (the
-              root's byte quantisation is then coarser than the whole cluster);
+              root's byte quantisation is then coarser than the whole cluster); with
+              alternating = True the 200 take materials 0 / 1 in turn (tests/tile_ties.py);
   offset      the ties mesh translated with its camera by 2^20, 2^30, 2^38 per axis.  The mesh
               is first scaled by 2^min(e - 20, 14), a power of two and so exact, to stay a few
               hundred ulps of the offset across (as fuzz_scenes does): at 2^38 an ulp is 32768.
@@ -148,7 +149,9 @@ def offset_mesh(e):
     return ties_mesh(scale=s, offset=(2.0 ** e, 2.0 ** e, 2.0 ** e), name=f"offset2^{e}")
 
 
-def degenerate_mesh():
+def degenerate_mesh(alternating=False):
+    """`alternating`: the 200 identical faces take materials 0 / 1 in turn ("degenerate_alt"), so
+    that a frame shows which face of the run won a tie; with one material no frame can."""
     rng = np.random.default_rng(0xDE6E)
     tris = _quad((0, 12, 0), (3, 0, 0), (0, 0, 3))
     mats = [2, 2]
@@ -165,11 +168,13 @@ def degenerate_mesh():
         tris.append(np.array([[q[0, 0], -3, q[0, 1]], [q[1, 0], -3, q[1, 1]], [q[2, 0], -3, q[2, 1]]], f32))
         mats.append(0)
     one = np.array([[-4, 2, 5], [5, 1, 6], [0, 8, 4]], f32)
-    tris += [one] * 200; mats += [1] * 200                  # identical: centroid extent zero
+    tris += [one] * 200                                     # identical: centroid extent zero
+    mats += [j & 1 for j in range(200)] if alternating else [1] * 200
     diag = np.linalg.norm(np.ptp(np.array(tris, np.float64).reshape(-1, 3), axis=0))
     far = f32(1e6 * diag)
     tris.append(np.array([[far, far, far], [far + 2, far, far], [far, far + 2, far]], f32)); mats.append(0)
-    m = Mesh("degenerate", np.array(tris, f32), mats, [3, 6, -30], [0, 0, 0], 1e-3, t_near=1.0)
+    m = Mesh("degenerate_alt" if alternating else "degenerate", np.array(tris, f32), mats, [3, 6, -30],
+             [0, 0, 0], 1e-3, t_near=1.0)
     # rays and cameras are laid out around the cluster, not around the far triangle
     p = m.pos[:-1].reshape(-1, 3).astype(np.float64)
     m.lo, m.hi = p.min(0), p.max(0)

@@ -161,6 +161,30 @@ def fuzz_scene(seed):
     return sc, kw, desc
 
 
+def _with_specks(sc, n, seed):
+    """The fuzz scene with n small triangles appended, scattered over its bounding box
+    (material 0): enough faces behind the room for the BVH hybrid to leave
+    the leading room faces to the specialised scan and build the BVH over the rest, and -- with
+    230 of them -- for the tiled scans to cross a tile boundary."""
+    v = sc.mesh.aligned_vertices()
+    f = sc.mesh.aligned_faces()
+    pos = v["position"][:, :3].astype(np.float64)
+    lo, hi = pos.min(0), pos.max(0)
+    ext = np.maximum(hi - lo, 1e-30)
+    rng = np.random.default_rng(0xB1D + seed)
+    c = lo + rng.random((n, 3)) * ext
+    p = (c[:, None, :] + (rng.random((n, 3, 3)) - 0.5) * ext / 64).astype(np.float32)
+    V = rvcp_amd.scene.VERTEX_DTYPE
+    F = rvcp_amd.scene.FACE_DTYPE
+    nv = np.zeros(3 * n, V)
+    nv["position"][:, :3] = p.reshape(3 * n, 3)
+    nv["normal"][:, 1] = 1.0
+    nf = np.zeros(n, F)
+    nf["vertices"] = len(v) + np.arange(3 * n, dtype=np.uint32).reshape(n, 3)
+    mesh = rvcp_amd.scene.ArrayMesh(np.concatenate([v, nv]), np.concatenate([f, nf]))
+    return rvcp_amd.Scene(sc.camera, list(sc.materials), [], mesh)
+
+
 def positions(sc):
     """[F, 3, 3] vertex positions of a scene's faces (float32)."""
     v = sc.mesh.aligned_vertices()["position"][:, :3]
