@@ -6,12 +6,13 @@
 // One launch per pass, one lane per pixel.  Pass i visits the 25 taps q = p + 2^i (dx, dy),
 // dx, dy in -2..2, row-major.  Two kernels, chosen by the step (DESIGN.md §4.9 has the times):
 //   steps 1 and 2: atrous_lds_kernel -- the workgroup's 32 x 8 pixels and their halo of 2 x step
-//     are staged once in LDS (colour, position, normal and the filterable flag as separate
+//     are staged once in LDS (colour, position, normal and the live flag as separate
 //     arrays, so a wave's reads of one array hit consecutive banks), each texel read from memory
-//     as two 16-byte loads; the taps then come from LDS.  1024^2: 0.041 / 0.039 ms per pass
-//     against 0.089 / 0.086 ms for the direct kernel, which issues 75 loads per pixel.
+//     as two 16-byte loads; the taps then come from LDS.  1024^2: 0.040 / 0.039 ms per pass.
 //   steps >= 4: atrous_kernel -- every tap read straight from memory (L2-served); the halo would
-//     be 2.6 x the tile (step 4) and more.  0.085 - 0.090 ms per pass at every step.
+//     be 2.6 x the tile (step 4) and more.  0.057 - 0.062 ms per pass at every step (0.085 -
+//     0.090 while a tap's colour was loaded only after its texel had passed the test; the live
+//     test of §4.15 needs the colour first, so a tap's five loads now issue together).
 // Both run the same arithmetic on the same values in the same order.
 //
 // Numeric contract: every weight is built from single, correctly rounded f32
@@ -33,6 +34,22 @@ __device__ __forceinline__ bool filterable(float4 g0, float4 g1) {
 }
 
 struct v3 { float x, y, z; };
+
+// neither an infinity nor a NaN: the exponent field is not all ones
+__device__ __forceinline__ bool finite1(float a) {
+    return (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
+}
+__device__ __forceinline__ bool finite3(float a, float b, float c) {
+    return finite1(a) && finite1(b) && finite1(c);
+}
+
+// A texel is live for a pass when it is filterable and its position, its normal and its colour
+// in the pass's input are finite.  Any other texel is treated as a MISS texel:
+// as a tap it adds nothing, as the centre it passes its colour through.
+__device__ __forceinline__ bool live(float4 g0, float4 g1, v3 c) {
+    return filterable(g0, g1) && finite3(g0.x, g0.y, g0.z) && finite3(g1.x, g1.y, g1.z) &&
+           finite3(c.x, c.y, c.z);
+}
 
 // (a.x b.x + a.y b.y) + a.z b.z, each operation rounded
 __device__ __forceinline__ float dot3(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
@@ -88,8 +105,8 @@ __global__ __launch_bounds__(kTileX * kTileY) void atrous_kernel(
     const size_t p = (size_t)y * width + x;
     const v3 pc = v3{in[3 * p], in[3 * p + 1], in[3 * p + 2]};
     const float4 p0 = guide[2 * p], p1 = guide[2 * p + 1];
-    v3 o = pc;                                   // a non-filterable pixel passes through
-    if (filterable(p0, p1)) {
+    v3 o = pc;                                   // a pixel that is not live passes through
+    if (live(p0, p1, pc)) {
         const v3 pp = v3{p0.x, p0.y, p0.z}, pn = v3{p1.x, p1.y, p1.z};
         Sums s = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -101,13 +118,17 @@ __global__ __launch_bounds__(kTileX * kTileY) void atrous_kernel(
                 if (qx >= width || qy >= height) continue;
                 const size_t q = (size_t)qy * width + qx;
                 const float4 q0 = guide[2 * q], q1 = guide[2 * q + 1];
-                if (!filterable(q0, q1)) continue;
+                const v3 qc = v3{in[3 * q], in[3 * q + 1], in[3 * q + 2]};
+                if (!live(q0, q1, qc)) continue;
                 tap(s, b3(dy) * b3(dx), A, pn, pp, pc, v3{q1.x, q1.y, q1.z}, v3{q0.x, q0.y, q0.z},
-                    v3{in[3 * q], in[3 * q + 1], in[3 * q + 2]});
+                    qc);
             }
         }
-        // the centre tap has w = 9/64 (w_n = w_z = w_c = 1 for a unit normal), so s.w > 0
-        o = v3{s.r / s.w, s.g / s.w, s.b / s.w};
+        // The centre tap has w = (9/64) w_n with w_n = |n_p|^2 squared normal_power_log2 times
+        // (w_z = w_c = 1): 9/64 for a unit normal, but 0 for a zero normal or one so short that
+        // the squaring underflows.  Weights that do not sum to more than 0 (a NaN sum, from
+        // finite values whose products overflow, included) leave the colour as it came.
+        if (s.w > 0.0f) o = v3{s.r / s.w, s.g / s.w, s.b / s.w};
     }
     out[3 * p] = o.x;
     out[3 * p + 1] = o.y;
@@ -141,8 +162,9 @@ __global__ __launch_bounds__(kLX * kLY) void atrous_lds_kernel(
             const float4 q0 = guide[2 * q], q1 = guide[2 * q + 1];
             s_px[i] = q0.x; s_py[i] = q0.y; s_pz[i] = q0.z;
             s_nx[i] = q1.x; s_ny[i] = q1.y; s_nz[i] = q1.z;
-            s_r[i] = in[3 * q]; s_g[i] = in[3 * q + 1]; s_b[i] = in[3 * q + 2];
-            ok = filterable(q0, q1) ? 1u : 0u;
+            const v3 qc = v3{in[3 * q], in[3 * q + 1], in[3 * q + 2]};
+            s_r[i] = qc.x; s_g[i] = qc.y; s_b[i] = qc.z;
+            ok = live(q0, q1, qc) ? 1u : 0u;     // the live flag, once per staged texel
         }
         s_ok[i] = ok;
     }
@@ -167,7 +189,7 @@ __global__ __launch_bounds__(kLX * kLY) void atrous_lds_kernel(
                     v3{s_px[q], s_py[q], s_pz[q]}, v3{s_r[q], s_g[q], s_b[q]});
             }
         }
-        o = v3{s.r / s.w, s.g / s.w, s.b / s.w};
+        if (s.w > 0.0f) o = v3{s.r / s.w, s.g / s.w, s.b / s.w};      // as atrous_kernel
     }
     const size_t p = (size_t)y * width + x;
     out[3 * p] = o.x;

@@ -42,6 +42,21 @@ __device__ __forceinline__ bool filterable(float4 g0, float4 g1) {
 
 struct v3 { float x, y, z; };
 
+// neither an infinity nor a NaN: the exponent field is not all ones
+__device__ __forceinline__ bool finite1(float a) {
+    return (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
+}
+__device__ __forceinline__ bool finite3(float a, float b, float c) {
+    return finite1(a) && finite1(b) && finite1(c);
+}
+
+// A texel is live for a launch when it is filterable and every float the launch reads from it is
+// finite: position and normal here, plus the colour, the moments or the variance
+// where a kernel reads them.  Any other texel is treated as a MISS texel.
+__device__ __forceinline__ bool live_g(float4 g0, float4 g1) {
+    return filterable(g0, g1) && finite3(g0.x, g0.y, g0.z) && finite3(g1.x, g1.y, g1.z);
+}
+
 // (a.x b.x + a.y b.y) + a.z b.z, each operation rounded
 __device__ __forceinline__ float dot3(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
@@ -69,8 +84,9 @@ __device__ __forceinline__ float weight_z(v3 pn, v3 pp, v3 qp, float sigma_plane
 // running sums over the accepted taps: sum w, sum w c, sum w m, the shortest history
 struct HistSums { float w, r, g, b, m1, m2; uint32_t nmin; };
 
-// One history tap q = (qx, qy) of weight w (rvcp_temporal.hip's tap, plus the moments).  The
-// colour, the moments and the length of a rejected tap are not read.
+// One history tap q = (qx, qy) of weight w (rvcp_temporal.hip's tap, plus the moments).  A tap
+// that is not live (position, normal, colour, moments) is rejected; the length of a rejected tap
+// is not read.
 __device__ __forceinline__ void hist_tap(HistSums &s, float w, int qx, int qy, uint32_t width,
                                          uint32_t height, v3 pn, v3 pp, uint32_t pm,
                                          float normal_min, float sigma_plane,
@@ -83,17 +99,19 @@ __device__ __forceinline__ void hist_tap(HistSums &s, float w, int qx, int qy, u
     if ((uint32_t)qx >= width || (uint32_t)qy >= height) return;
     const size_t q = (size_t)(uint32_t)qy * width + (uint32_t)qx;
     const float4 q0 = prev_g[2 * q], q1 = prev_g[2 * q + 1];
-    if (!filterable(q0, q1) || __float_as_uint(q1.w) != pm) return;
+    if (!live_g(q0, q1) || __float_as_uint(q1.w) != pm) return;
     if (!(dot3(pn, v3{q1.x, q1.y, q1.z}) >= normal_min)) return;
     const float d = dot3(pn, v3{q0.x - pp.x, q0.y - pp.y, q0.z - pp.z});
     if (!(fabsf(d) <= sigma_plane)) return;
+    const v3 qc = v3{prev_c[3 * q], prev_c[3 * q + 1], prev_c[3 * q + 2]};
+    const float2 m = prev_m[q];
+    if (!finite3(qc.x, qc.y, qc.z) || !finite1(m.x) || !finite1(m.y)) return;
     const uint32_t n = prev_len[q];
     if (n < 1u) return;
-    const float2 m = prev_m[q];
     s.w = s.w + w;
-    s.r = s.r + w * prev_c[3 * q];
-    s.g = s.g + w * prev_c[3 * q + 1];
-    s.b = s.b + w * prev_c[3 * q + 2];
+    s.r = s.r + w * qc.x;
+    s.g = s.g + w * qc.y;
+    s.b = s.b + w * qc.z;
     s.m1 = s.m1 + w * m.x;
     s.m2 = s.m2 + w * m.y;
     s.nmin = n < s.nmin ? n : s.nmin;
@@ -118,9 +136,9 @@ __global__ __launch_bounds__(kTileX * kTileY) void svgf_temporal_kernel(
     const v3 c = v3{cur_c[3 * p], cur_c[3 * p + 1], cur_c[3 * p + 2]};
     const float4 p0 = cur_g[2 * p], p1 = cur_g[2 * p + 1];
     v3 o = c;                                    // no usable history: the current colour
-    float2 om = make_float2(0.0f, 0.0f);         // a non-filterable pixel keeps no moments
+    float2 om = make_float2(0.0f, 0.0f);         // a pixel that is not live keeps no moments
     uint32_t len = 0;                            // ... and no history
-    if (filterable(p0, p1)) {
+    if (live_g(p0, p1) && finite3(c.x, c.y, c.z)) {
         len = 1;
         const float l1 = lum(c);
         const float2 mu = make_float2(l1, l1 * l1);
@@ -201,12 +219,16 @@ __global__ __launch_bounds__(kLX * kLY) void svgf_variance_kernel(
     v3 pp = v3{0.0f, 0.0f, 0.0f}, pn = pp;
     if (inside) {
         const float4 p0 = guide[2 * p], p1 = guide[2 * p + 1];
-        filt = filterable(p0, p1);
+        // live for this launch: finite moments too, and a history of at least one frame (the
+        // accumulation leaves length 0 and zero moments on a pixel that was not live for it)
+        if (live_g(p0, p1)) {
+            m = mom[p];
+            n = len[p];
+            filt = finite1(m.x) && finite1(m.y) && n >= 1u;
+        }
         if (filt) {
             pp = v3{p0.x, p0.y, p0.z};
             pn = v3{p1.x, p1.y, p1.z};
-            n = len[p];
-            m = mom[p];
         }
     }
     const bool young = filt && n < spatial_below;
@@ -220,8 +242,8 @@ __global__ __launch_bounds__(kLX * kLY) void svgf_variance_kernel(
             if (gx < width && gy < height) {
                 const size_t q = (size_t)gy * width + gx;
                 const float4 q0 = guide[2 * q], q1 = guide[2 * q + 1];
-                if (filterable(q0, q1)) {
-                    const float2 qm = mom[q];
+                const float2 qm = mom[q];
+                if (live_g(q0, q1) && finite1(qm.x) && finite1(qm.y) && len[q] >= 1u) {   // live
                     s_px[i] = q0.x; s_py[i] = q0.y; s_pz[i] = q0.z;
                     s_nx[i] = q1.x; s_ny[i] = q1.y; s_nz[i] = q1.z;
                     s_m1[i] = qm.x; s_m2[i] = qm.y;
@@ -233,7 +255,7 @@ __global__ __launch_bounds__(kLX * kLY) void svgf_variance_kernel(
         __syncthreads();
     }
     if (!inside) return;
-    float v = 0.0f;                              // a non-filterable pixel has no variance
+    float v = 0.0f;                              // a pixel that is not live has no variance
     if (filt) {
         if (!young) {
             v = m.y - m.x * m.x;
@@ -255,11 +277,14 @@ __global__ __launch_bounds__(kLX * kLY) void svgf_variance_kernel(
                     a2 = a2 + w * s_m2[q];
                 }
             }
-            // the centre tap has w ~ 1 (w_n = |n|^2 squared, w_z = 1), so ws > 0
-            const float e1 = a1 / ws, e2 = a2 / ws;
-            v = e2 - e1 * e1;
-            if (!(v > 0.0f)) v = 0.0f;
-            v = v * ((float)spatial_below / (float)n);
+            // the centre tap has w ~ 1 for a unit normal (w_n = |n|^2 squared, w_z = 1); weights
+            // that do not sum to more than 0 (a zero normal) give no estimate
+            if (ws > 0.0f) {
+                const float e1 = a1 / ws, e2 = a2 / ws;
+                v = e2 - e1 * e1;
+                if (!(v > 0.0f)) v = 0.0f;
+                v = v * ((float)spatial_below / (float)n);
+            }
         }
     }
     out_v[p] = v;
@@ -296,6 +321,22 @@ __device__ __forceinline__ void tap(Sums &s, float h, const GuideArgs &A, float 
     s.v = s.v + (w * w) * qv;
 }
 
+// The end of a pass.  The centre tap has w = (9/64) w_n with w_n = |n_p|^2 squared
+// normal_power_log2 times (w_z = w_l = 1): 9/64 for a unit normal, 0 for a zero normal.  Weights
+// that do not sum to more than 0 leave colour and variance as a MISS pixel's (o, ov preset); a sum
+// whose square underflows leaves the variance 0.
+__device__ __forceinline__ void finish(const Sums &s, v3 &o, float &ov) {
+    if (!(s.w > 0.0f)) return;
+    o = v3{s.r / s.w, s.g / s.w, s.b / s.w};
+    const float w2 = s.w * s.w;
+    if (w2 > 0.0f) ov = s.v / w2;
+}
+
+// live for a pass: position, normal, colour and variance
+__device__ __forceinline__ bool live(float4 g0, float4 g1, v3 c, float v) {
+    return live_g(g0, g1) && finite3(c.x, c.y, c.z) && finite1(v);
+}
+
 // the B3 spline (1/16, 1/4, 3/8, 1/4, 1/16): every product of two entries is exact in f32
 __device__ __forceinline__ constexpr float b3(int i) {
     return i == 0 ? 0.375f : (i == 1 || i == -1) ? 0.25f : 0.0625f;
@@ -318,13 +359,12 @@ __global__ __launch_bounds__(kTileX * kTileY) void svgf_atrous_kernel(
     const size_t p = (size_t)y * width + x;
     const v3 pc = v3{in_c[3 * p], in_c[3 * p + 1], in_c[3 * p + 2]};
     const float4 p0 = guide[2 * p], p1 = guide[2 * p + 1];
-    v3 o = pc;                                   // a non-filterable pixel passes through
+    v3 o = pc;                                   // a pixel that is not live passes through
     float ov = 0.0f;
-    if (filterable(p0, p1)) {
+    if (live(p0, p1, pc, in_v[p])) {
         const v3 pp = v3{p0.x, p0.y, p0.z}, pn = v3{p1.x, p1.y, p1.z};
         float den = 1.0f, lp = 0.0f;
         if (A.use_lum) {
-            const uint32_t *gw = (const uint32_t *)guide;        // the texels' face / material words
             float gs = 0.0f, vs = 0.0f;
 #pragma unroll
             for (int dy = -1; dy <= 1; ++dy) {
@@ -334,12 +374,14 @@ __global__ __launch_bounds__(kTileX * kTileY) void svgf_atrous_kernel(
                     const uint32_t qx = x + (uint32_t)dx, qy = y + (uint32_t)dy;
                     if (qx >= width || qy >= height) continue;
                     const size_t q = (size_t)qy * width + qx;
-                    if (!filterable_w(gw[8 * q + 3], gw[8 * q + 7])) continue;
+                    const float qv = in_v[q];
+                    if (!live(guide[2 * q], guide[2 * q + 1],
+                              v3{in_c[3 * q], in_c[3 * q + 1], in_c[3 * q + 2]}, qv)) continue;
                     gs = gs + g3(dy, dx);
-                    vs = vs + g3(dy, dx) * in_v[q];
+                    vs = vs + g3(dy, dx) * qv;
                 }
             }
-            den = A.sigma_l2 * (vs / gs) + A.epsilon;
+            den = A.sigma_l2 * (vs / gs) + A.epsilon;            // gs >= 1/4: the centre is live
             lp = lum(pc);
         }
         Sums s = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
@@ -352,15 +394,14 @@ __global__ __launch_bounds__(kTileX * kTileY) void svgf_atrous_kernel(
                 if (qx >= width || qy >= height) continue;
                 const size_t q = (size_t)qy * width + qx;
                 const float4 q0 = guide[2 * q], q1 = guide[2 * q + 1];
-                if (!filterable(q0, q1)) continue;
+                const v3 qc = v3{in_c[3 * q], in_c[3 * q + 1], in_c[3 * q + 2]};
+                const float qv = in_v[q];
+                if (!live(q0, q1, qc, qv)) continue;
                 tap(s, b3(dy) * b3(dx), A, den, lp, pn, pp, v3{q1.x, q1.y, q1.z},
-                    v3{q0.x, q0.y, q0.z}, v3{in_c[3 * q], in_c[3 * q + 1], in_c[3 * q + 2]},
-                    in_v[q]);
+                    v3{q0.x, q0.y, q0.z}, qc, qv);
             }
         }
-        // the centre tap has w = 9/64 (w_n = w_z = w_l = 1 for a unit normal), so s.w > 0
-        o = v3{s.r / s.w, s.g / s.w, s.b / s.w};
-        ov = s.v / (s.w * s.w);
+        finish(s, o, ov);
     }
     out_c[3 * p] = o.x;
     out_c[3 * p + 1] = o.y;
@@ -395,9 +436,11 @@ __global__ __launch_bounds__(kLX * kLY) void svgf_atrous_lds_kernel(
             const float4 q0 = guide[2 * q], q1 = guide[2 * q + 1];
             s_px[i] = q0.x; s_py[i] = q0.y; s_pz[i] = q0.z;
             s_nx[i] = q1.x; s_ny[i] = q1.y; s_nz[i] = q1.z;
-            s_r[i] = in_c[3 * q]; s_g[i] = in_c[3 * q + 1]; s_b[i] = in_c[3 * q + 2];
-            s_v[i] = in_v[q];
-            ok = filterable(q0, q1) ? 1u : 0u;
+            const v3 qc = v3{in_c[3 * q], in_c[3 * q + 1], in_c[3 * q + 2]};
+            const float qv = in_v[q];
+            s_r[i] = qc.x; s_g[i] = qc.y; s_b[i] = qc.z;
+            s_v[i] = qv;
+            ok = live(q0, q1, qc, qv) ? 1u : 0u;     // the live flag, once per staged texel
         }
         s_ok[i] = ok;
     }
@@ -425,7 +468,7 @@ __global__ __launch_bounds__(kLX * kLY) void svgf_atrous_lds_kernel(
                     vs = vs + g3(dy, dx) * s_v[q];
                 }
             }
-            den = A.sigma_l2 * (vs / gs) + A.epsilon;
+            den = A.sigma_l2 * (vs / gs) + A.epsilon;            // gs >= 1/4: the centre is live
             lp = lum(pc);
         }
         Sums s = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
@@ -440,8 +483,7 @@ __global__ __launch_bounds__(kLX * kLY) void svgf_atrous_lds_kernel(
                     v3{s_px[q], s_py[q], s_pz[q]}, v3{s_r[q], s_g[q], s_b[q]}, s_v[q]);
             }
         }
-        o = v3{s.r / s.w, s.g / s.w, s.b / s.w};
-        ov = s.v / (s.w * s.w);
+        finish(s, o, ov);
     }
     const size_t p = (size_t)y * width + x;
     out_c[3 * p] = o.x;

@@ -37,6 +37,14 @@ __device__ __forceinline__ bool filterable(float4 g0, float4 g1) {
 
 struct v3 { float x, y, z; };
 
+// neither an infinity nor a NaN: the exponent field is not all ones
+__device__ __forceinline__ bool finite1(float a) {
+    return (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
+}
+__device__ __forceinline__ bool finite3(float a, float b, float c) {
+    return finite1(a) && finite1(b) && finite1(c);
+}
+
 // (a.x b.x + a.y b.y) + a.z b.z, each operation rounded
 __device__ __forceinline__ float dot3(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
@@ -44,7 +52,8 @@ __device__ __forceinline__ float dot3(v3 a, v3 b) { return (a.x * b.x + a.y * b.
 struct Sums { float w, r, g, b; uint32_t nmin; };
 
 // One history tap q = (qx, qy) of weight w for the pixel with normal pn, position pp and
-// material word pm.  The colour and the length of a rejected tap are not read.
+// material word pm.  A tap whose position, normal or colour is not finite is rejected as a MISS
+// texel is; the length of a rejected tap is not read.
 __device__ __forceinline__ void tap(Sums &s, float w, int qx, int qy, uint32_t width,
                                     uint32_t height, v3 pn, v3 pp, uint32_t pm, float normal_min,
                                     float sigma_plane, const float *__restrict__ prev_c,
@@ -56,15 +65,18 @@ __device__ __forceinline__ void tap(Sums &s, float w, int qx, int qy, uint32_t w
     const size_t q = (size_t)(uint32_t)qy * width + (uint32_t)qx;
     const float4 q0 = prev_g[2 * q], q1 = prev_g[2 * q + 1];
     if (!filterable(q0, q1) || __float_as_uint(q1.w) != pm) return;
+    if (!finite3(q0.x, q0.y, q0.z) || !finite3(q1.x, q1.y, q1.z)) return;
     if (!(dot3(pn, v3{q1.x, q1.y, q1.z}) >= normal_min)) return;
     const float d = dot3(pn, v3{q0.x - pp.x, q0.y - pp.y, q0.z - pp.z});
     if (!(fabsf(d) <= sigma_plane)) return;
+    const v3 qc = v3{prev_c[3 * q], prev_c[3 * q + 1], prev_c[3 * q + 2]};
+    if (!finite3(qc.x, qc.y, qc.z)) return;
     const uint32_t n = prev_len[q];
     if (n < 1u) return;
     s.w = s.w + w;
-    s.r = s.r + w * prev_c[3 * q];
-    s.g = s.g + w * prev_c[3 * q + 1];
-    s.b = s.b + w * prev_c[3 * q + 2];
+    s.r = s.r + w * qc.x;
+    s.g = s.g + w * qc.y;
+    s.b = s.b + w * qc.z;
     s.nmin = n < s.nmin ? n : s.nmin;
 }
 
@@ -88,8 +100,10 @@ __global__ __launch_bounds__(kTileX * kTileY) void temporal_kernel(
     const v3 c = v3{cur_c[3 * p], cur_c[3 * p + 1], cur_c[3 * p + 2]};
     const float4 p0 = cur_g[2 * p], p1 = cur_g[2 * p + 1];
     v3 o = c;                                    // no usable history: the current colour
-    uint32_t len = 0;                            // a non-filterable pixel keeps no history
-    if (filterable(p0, p1)) {
+    uint32_t len = 0;                            // a pixel that is not live keeps no history
+    // live: filterable, with a finite position, normal and colour
+    if (filterable(p0, p1) && finite3(p0.x, p0.y, p0.z) && finite3(p1.x, p1.y, p1.z) &&
+        finite3(c.x, c.y, c.z)) {
         len = 1;
         const v3 pp = v3{p0.x, p0.y, p0.z}, pn = v3{p1.x, p1.y, p1.z};
         const uint32_t pm = __float_as_uint(p1.w);

@@ -4,7 +4,8 @@ pyref's triangle test (TEST INFRASTRUCTURE ONLY: never imported by the package).
 
 It shares no code with csrc/rvcp_denoise.hip, only the contract: every weight is a chain of
 single, correctly rounded float32 +, -, x, / in a fixed order, the 25 taps of a pass are
-accumulated in row-major order, and skipped taps add nothing.  numpy evaluates each array
+accumulated in row-major order, skipped taps add nothing, and a texel that is not live
+(§4.15: not filterable, or a non-finite position, normal or colour) is a MISS texel.  numpy evaluates each array
 operation in float32 with one rounding and never fuses, so the kernel's output is reproduced
 bit for bit.
 """
@@ -27,6 +28,24 @@ def filterable(g) -> np.ndarray:
     return (g["face"] != MISS) & ((g["material"] & np.uint32(EMISSIVE)) == 0)
 
 
+def finite(a) -> np.ndarray:
+    """Per texel: every float32 of the last axis (or the value itself, `a` [H, W]) has an
+    exponent field below all ones -- neither an infinity nor a NaN."""
+    a = np.ascontiguousarray(a, dtype=F)
+    ok = (a.view(np.uint32) & np.uint32(0x7F800000)) != np.uint32(0x7F800000)
+    return ok if a.ndim == 2 else ok.all(axis=-1)
+
+
+def live(g, *floats) -> np.ndarray:
+    """The live texels of a launch: filterable, with a finite position and
+    normal, and finite in every further per-texel array the launch reads (`floats`: [H, W] or
+    [H, W, k]).  Every other texel is treated as a MISS texel."""
+    ok = filterable(g) & finite(g["position"]) & finite(g["normal"])
+    for a in floats:
+        ok &= finite(a)
+    return ok
+
+
 def _dot3(a, b):
     """(a0 b0 + a1 b1) + a2 b2, every operation rounded to float32."""
     return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
@@ -43,7 +62,7 @@ def atrous_pass(c, g, i, normal_power_log2, sigma_color, sigma_plane):
     c = np.ascontiguousarray(c, dtype=F)
     H, W = c.shape[:2]
     step = 1 << i
-    pos, nrm, filt = g["position"], g["normal"], filterable(g)
+    pos, nrm, filt = g["position"], g["normal"], live(g, c)
     use_color = not np.isinf(F(sigma_color))
     s2 = color_s2(sigma_color, i) if use_color else None
     sp = F(sigma_plane)
@@ -75,7 +94,8 @@ def atrous_pass(c, g, i, normal_power_log2, sigma_color, sigma_plane):
                 assert w.dtype == F
                 sw[P] = np.where(valid, sw[P] + w, sw[P])
                 acc[P] = np.where(valid[..., None], acc[P] + w[..., None] * c[Q], acc[P])
-        out = np.where(filt[..., None], acc / sw[..., None], c)
+        # a texel that is not live, or whose weights sum to nothing (a zero normal), passes through
+        out = np.where((filt & (sw > 0))[..., None], acc / sw[..., None], c)
     return np.ascontiguousarray(out, dtype=F)
 
 

@@ -5,14 +5,14 @@ INFRASTRUCTURE ONLY: never imported by the package).
 
 It shares no code with csrc/rvcp_svgf.hip, only the contract: float32 throughout, every
 operation rounded once in the order §4.11 writes them, taps in the written order, skipped taps
-add nothing.  numpy evaluates each array operation in float32 with one rounding and never fuses,
+add nothing, and a texel that is not live for a launch (§4.15) is a MISS texel.  numpy evaluates each array operation in float32 with one rounding and never fuses,
 so the kernels' outputs are reproduced bit for bit.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from denoise_ref import GBUFFER_DTYPE, KERNEL, filterable       # noqa: F401
+from denoise_ref import GBUFFER_DTYPE, KERNEL, filterable, live  # noqa: F401
 import temporal_ref as T
 
 F = np.float32
@@ -73,10 +73,11 @@ def accumulate(c, g, prev_c, prev_g, prev_len, prev_m, view, tp, sp):
     SVGF parameter records.  Returns (colour, length, moments)."""
     c = np.ascontiguousarray(c, dtype=F)
     H, W = c.shape[:2]
-    filt = filterable(g)
+    filt = live(g, c)                  # §4.15: any other texel is a MISS texel, here and below
     pos, nrm, mat = g["position"], g["normal"], g["material"]
-    l1 = lum(c)
-    mu = np.stack([l1, l1 * l1], axis=-1)
+    with np.errstate(all="ignore"):
+        l1 = lum(c)
+        mu = np.stack([l1, l1 * l1], axis=-1)
     assert mu.dtype == F
     wsum = np.zeros((H, W), dtype=F)
     sc = np.zeros((H, W, 3), dtype=F)
@@ -105,7 +106,7 @@ def accumulate(c, g, prev_c, prev_g, prev_len, prev_m, view, tp, sp):
             inside = ok & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
             Q = (np.clip(qy, 0, H - 1), np.clip(qx, 0, W - 1))
             gq = prev_g[Q]
-            a = inside & filt & filterable(gq) & (gq["material"] == mat)
+            a = inside & filt & live(gq, prev_c[Q], prev_m[Q]) & (gq["material"] == mat)
             a &= _dot3(nrm, gq["normal"]) >= n_min
             a &= np.abs(_dot3(nrm, gq["position"] - pos)) <= s_plane
             lq = prev_len[Q].astype(np.int64)
@@ -132,11 +133,20 @@ def accumulate(c, g, prev_c, prev_g, prev_len, prev_m, view, tp, sp):
 
 
 # ------------------------------------------------------------------------ B. variance
-def spatial_variance(m, g, sp):
-    """The unboosted 7 x 7 estimate of every filterable pixel (0 elsewhere)."""
+def variance_live(m, length, g):
+    """The live texels of the variance launch (§4.15): filterable, a finite position, normal and
+    moments, and a history of at least one frame -- the accumulation leaves length 0 and zero
+    moments on a texel that was not live for it."""
+    ok = live(g, m)
+    return ok if length is None else ok & (np.asarray(length) >= 1)
+
+
+def spatial_variance(m, g, sp, length=None):
+    """The unboosted 7 x 7 estimate of every live pixel over its live taps (0 elsewhere);
+    length None: every history counts as at least one frame long."""
     m = np.ascontiguousarray(m, dtype=F)
     H, W = m.shape[:2]
-    filt, pos, nrm = filterable(g), g["position"], g["normal"]
+    filt, pos, nrm = variance_live(m, length, g), g["position"], g["normal"]
     ws = np.zeros((H, W), dtype=F)
     a1 = np.zeros((H, W), dtype=F)
     a2 = np.zeros((H, W), dtype=F)
@@ -156,14 +166,15 @@ def spatial_variance(m, g, sp):
         e1, e2 = a1 / ws, a2 / ws
         v = e2 - e1 * e1
         v = np.where(v > 0, v, F(0))
-    return np.where(filt, v, F(0)).astype(F)
+    # weights that sum to nothing (a zero normal): no estimate
+    return np.where(filt & (ws > 0), v, F(0)).astype(F)
 
 
 def variance(m, length, g, sp):
     """v [H, W]: the temporal estimate where the history is at least spatial_below long, the
-    boosted 7 x 7 estimate below that, 0 on a non-filterable pixel."""
+    boosted 7 x 7 estimate below that, 0 on a pixel that is not live."""
     m = np.ascontiguousarray(m, dtype=F)
-    filt = filterable(g)
+    filt = variance_live(m, length, g)
     below = int(sp["spatial_below"])
     with np.errstate(all="ignore"):
         vt = m[..., 1] - m[..., 0] * m[..., 0]
@@ -172,17 +183,19 @@ def variance(m, length, g, sp):
         v = vt
         if short.any():
             boost = F(below) / length.astype(F)
-            vs = spatial_variance(m, g, sp) * boost
+            vs = spatial_variance(m, g, sp, length) * boost
             assert vs.dtype == F
             v = np.where(short, vs, vt)
     return np.where(filt, v, F(0)).astype(F)
 
 
 # ------------------------------------------------------------------------ C. guided a-trous
-def prefilter(v, g):
-    """vbar: the 3 x 3 Gaussian of v at distance 1 over the filterable taps inside the frame."""
+def prefilter(v, g, c=None):
+    """vbar: the 3 x 3 Gaussian of v at distance 1 over the live taps inside the frame (live for
+    a pass over colour c: §4.15), 0 where no tap is live."""
+    v = np.ascontiguousarray(v, dtype=F)
     H, W = v.shape
-    filt = filterable(g)
+    filt = live(g, v) if c is None else live(g, c, v)
     gs = np.zeros((H, W), dtype=F)
     vs = np.zeros((H, W), dtype=F)
     for dy in range(-1, 2):
@@ -194,9 +207,10 @@ def prefilter(v, g):
             valid = filt[P] & filt[Q]
             k = GAUSS3[dy + 1][dx + 1]
             gs[P] = np.where(valid, gs[P] + k, gs[P])
-            vs[P] = np.where(valid, vs[P] + k * v[Q], vs[P])
+            with np.errstate(all="ignore"):
+                vs[P] = np.where(valid, vs[P] + k * v[Q], vs[P])
     with np.errstate(all="ignore"):
-        return (vs / gs).astype(F)
+        return np.where(gs > 0, vs / gs, F(0)).astype(F)
 
 
 def guided_pass(c, v, g, i, sp):
@@ -205,7 +219,7 @@ def guided_pass(c, v, g, i, sp):
     v = np.ascontiguousarray(v, dtype=F)
     H, W = v.shape
     step = 1 << i
-    pos, nrm, filt = g["position"], g["normal"], filterable(g)
+    pos, nrm, filt = g["position"], g["normal"], live(g, c, v)
     sl = F(sp["sigma_luminance"])
     use_l = not np.isinf(sl)
     sw = np.zeros((H, W), dtype=F)
@@ -213,7 +227,7 @@ def guided_pass(c, v, g, i, sp):
     sv = np.zeros((H, W), dtype=F)
     with np.errstate(all="ignore"):
         if use_l:
-            den = F(sl * sl) * prefilter(v, g) + F(sp["epsilon"])
+            den = F(sl * sl) * prefilter(v, g, c) + F(sp["epsilon"])
             lc = lum(c)
             assert den.dtype == F and lc.dtype == F
         for dy in range(-2, 3):
@@ -233,8 +247,12 @@ def guided_pass(c, v, g, i, sp):
                 sw[P] = np.where(valid, sw[P] + w, sw[P])
                 acc[P] = np.where(valid[..., None], acc[P] + w[..., None] * c[Q], acc[P])
                 sv[P] = np.where(valid, sv[P] + (w * w) * v[Q], sv[P])
-        co = np.where(filt[..., None], acc / sw[..., None], c)
-        vo = np.where(filt, sv / (sw * sw), F(0))
+        # a texel that is not live, or whose weights sum to nothing (a zero normal), passes its
+        # colour through with variance 0; so does the variance where sw^2 underflows
+        ok = filt & (sw > 0)
+        sw2 = sw * sw
+        co = np.where(ok[..., None], acc / sw[..., None], c)
+        vo = np.where(ok & (sw2 > 0), sv / sw2, F(0))
     return np.ascontiguousarray(co, dtype=F), np.ascontiguousarray(vo, dtype=F)
 
 

@@ -5,7 +5,9 @@ by the package).
 
 It shares no code with csrc/rvcp_temporal.hip, only the contract: float32 throughout, every
 operation rounded once, in the order DESIGN.md §4.10 writes them, the taps visited in the order
-(x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), and a rejected tap adds nothing.  numpy
+(x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), a rejected tap adds nothing, and a texel
+that is not live (§4.15: not filterable, or a non-finite position, normal or colour) is a MISS
+texel, as the current pixel and as a history tap.  numpy
 evaluates each array operation in float32 with one rounding and never fuses, so the kernel's
 output is reproduced bit for bit, thresholds and floor included.
 """
@@ -13,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from denoise_ref import EMISSIVE, GBUFFER_DTYPE, MISS, filterable
+from denoise_ref import EMISSIVE, GBUFFER_DTYPE, MISS, filterable, live
 
 F = np.float32
 PARAMS_DTYPE = np.dtype([("alpha_min", "<f4"), ("max_history", "<u4"),
@@ -87,7 +89,7 @@ def accumulate(c, g, prev_c, prev_g, prev_len, view, p, want_taps=False):
     [, the number of accepted taps per pixel]."""
     c = np.ascontiguousarray(c, dtype=F)
     H, W = c.shape[:2]
-    filt = filterable(g)
+    filt = live(g, c)                  # §4.15: any other texel is a MISS texel, here and below
     pos, nrm, mat = g["position"], g["normal"], g["material"]
     wsum = np.zeros((H, W), dtype=F)
     acc = np.zeros((H, W, 3), dtype=F)
@@ -117,7 +119,7 @@ def accumulate(c, g, prev_c, prev_g, prev_len, view, p, want_taps=False):
             inside = ok & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
             Q = (np.clip(qy, 0, H - 1), np.clip(qx, 0, W - 1))
             gq = prev_g[Q]
-            a = inside & filt & filterable(gq) & (gq["material"] == mat)
+            a = inside & filt & live(gq, prev_c[Q]) & (gq["material"] == mat)
             a &= _dot3(nrm, gq["normal"]) >= nm
             a &= np.abs(_dot3(nrm, gq["position"] - pos)) <= sp
             lq = prev_len[Q].astype(np.int64)

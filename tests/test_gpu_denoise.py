@@ -99,6 +99,14 @@ CASES = [  # W, H, params
     (8, 8, dict(iterations=1, normal_power_log2=1, sigma_color=0.3, sigma_plane=10.0)),
     (8, 8, dict(iterations=8, normal_power_log2=3, sigma_color=float("inf"), sigma_plane=1.0)),
     (1, 1, dict(iterations=3, normal_power_log2=5, sigma_color=1.0, sigma_plane=1.0)),
+    # the reach of the passes: at eight passes the steps 32, 64 and 128 have taps inside the frame
+    # at both distances, along a row and along a column
+    (261, 5, dict(iterations=8, normal_power_log2=2, sigma_color=50.0, sigma_plane=100.0)),
+    (5, 261, dict(iterations=8, normal_power_log2=2, sigma_color=50.0, sigma_plane=100.0)),
+    # frames exactly on and one past the 32 x 8 and the 64 x 4 tiles
+    (64, 8, dict(iterations=5, normal_power_log2=2, sigma_color=50.0, sigma_plane=100.0)),
+    (65, 9, dict(iterations=5, normal_power_log2=2, sigma_color=50.0, sigma_plane=100.0)),
+    (33, 5, dict(iterations=5, normal_power_log2=2, sigma_color=50.0, sigma_plane=100.0)),
 ]
 
 

@@ -91,7 +91,11 @@ def assert_same(got, want, what):
 
 
 # ---------------------------------------------------------------------------- 1. kernel parity
-SIZES = [(67, 45), (130, 3), (70, 5), (8, 8), (5, 5), (1, 1)]
+# ... and frames exactly on and one past the 32 x 8 and the 64 x 4 tiles
+SIZES = [(67, 45), (130, 3), (70, 5), (8, 8), (5, 5), (1, 1), (64, 8), (65, 9), (33, 5)]
+# the filter: every size at 1, 3 and 5 passes, and the reach of the passes -- at the API's maximum
+# of eight the steps 32, 64 and 128 have taps inside the frame at both distances
+FILTER_SIZES = [(W, H, i) for W, H in SIZES for i in (1, 3, 5)] + [(261, 5, 8), (5, 261, 8)]
 
 
 def one_filterable_pixel(g):
@@ -154,8 +158,7 @@ def filter_case(W, H, seed):
 
 @pytest.mark.parametrize("sigma", [2.0, float("inf")], ids=["sigma2", "sigma_inf"])
 @pytest.mark.parametrize("below", [1, 4])
-@pytest.mark.parametrize("iterations", [1, 3, 5])
-@pytest.mark.parametrize("W,H", SIZES)
+@pytest.mark.parametrize("W,H,iterations", FILTER_SIZES)
 def test_filter_matches_numpy_restatement(tracers, W, H, iterations, below, sigma):
     c, m, n, g, tx = filter_case(W, H, seed=W * 100 + H)
     filt = R.filterable(g)

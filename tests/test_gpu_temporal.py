@@ -61,7 +61,7 @@ def gpu_accumulate(rt, c, g, pc, pg, pl, view, params, want_rgba=True):
 
 
 # ---------------------------------------------------------------------------- 1. kernel parity
-SIZES = [(67, 45), (130, 3), (70, 5), (8, 8), (1, 1)]
+SIZES = [(67, 45), (130, 3), (70, 5), (8, 8), (1, 1), (64, 8), (65, 9)]   # .. on / past the tile
 PARAM_SETS = {"max_history_1": dict(max_history=1),
               "alpha_min_0": dict(alpha_min=0.0, max_history=40, normal_min=0.8, sigma_plane=0.25)}
 
