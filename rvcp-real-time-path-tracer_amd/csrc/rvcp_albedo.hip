@@ -19,9 +19,7 @@
 // numpy float32 restatement, reproduces every output bit.
 #include <hip/hip_runtime.h>
 
-#include <stdint.h>
-
-#include "../../include/rvcp.h"
+#include "rvcp_post.h"
 #include "rvcp_tonemap.h"
 
 namespace {
@@ -38,8 +36,7 @@ __device__ __forceinline__ bool pixel_albedo(const uint32_t *__restrict__ gw, si
                                              uint32_t n_materials, float4 &a) {
     const uint32_t face = gw[8 * i + 3], material = gw[8 * i + 7];
     const uint32_t m = material & ~RVCP_GBUFFER_EMISSIVE;
-    if (face == RVCP_GBUFFER_MISS || (material & RVCP_GBUFFER_EMISSIVE) || m >= n_materials)
-        return false;
+    if (!rvcp::filterable_w(face, material) || m >= n_materials) return false;
     a = albedo[m];
     return true;
 }

@@ -21,38 +21,16 @@
 // float32 restatement, reproduces every output bit.
 #include <hip/hip_runtime.h>
 
-#include <stdint.h>
+#include "rvcp_post.h"
 
-#include "../../include/rvcp.h"
+using namespace rvcp;
 
 namespace {
 
-// a pixel takes part in the filter when its primary ray hit a non-emissive surface
-__device__ __forceinline__ bool filterable(float4 g0, float4 g1) {
-    return __float_as_uint(g0.w) != RVCP_GBUFFER_MISS &&
-           !(__float_as_uint(g1.w) & RVCP_GBUFFER_EMISSIVE);
-}
-
-struct v3 { float x, y, z; };
-
-// neither an infinity nor a NaN: the exponent field is not all ones
-__device__ __forceinline__ bool finite1(float a) {
-    return (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
-}
-__device__ __forceinline__ bool finite3(float a, float b, float c) {
-    return finite1(a) && finite1(b) && finite1(c);
-}
-
-// A texel is live for a pass when it is filterable and its position, its normal and its colour
-// in the pass's input are finite.  Any other texel is treated as a MISS texel:
-// as a tap it adds nothing, as the centre it passes its colour through.
+// live for a pass: position, normal and the colour in the pass's input
 __device__ __forceinline__ bool live(float4 g0, float4 g1, v3 c) {
-    return filterable(g0, g1) && finite3(g0.x, g0.y, g0.z) && finite3(g1.x, g1.y, g1.z) &&
-           finite3(c.x, c.y, c.z);
+    return live_g(g0, g1) && finite3(c.x, c.y, c.z);
 }
-
-// (a.x b.x + a.y b.y) + a.z b.z, each operation rounded
-__device__ __forceinline__ float dot3(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
 // the wave-uniform parameters of a pass
 struct PassArgs {
@@ -64,16 +42,12 @@ struct PassArgs {
 struct Sums { float w, r, g, b; };
 
 // One tap q of pixel p: w = ((h w_n) w_z) w_c added to the sums, in this order.
-//   w_n = max(0, n_p . n_q), squared normal_power_log2 times
-//   w_z = 1 / (1 + d^2), d = n_p . (pos_q - pos_p) / sigma_plane
+//   w_n, w_z: rvcp_post.h's weight_n, weight_z
 //   w_c = 1 / (1 + |c_p - c_q|^2 / sigma_i^2)          (1 when the colour weight is off)
 __device__ __forceinline__ void tap(Sums &s, float h, const PassArgs &A, v3 pn, v3 pp, v3 pc,
                                     v3 qn, v3 qp, v3 qc) {
-    const float dn = dot3(pn, qn);
-    float wn = dn > 0.0f ? dn : 0.0f;
-    for (uint32_t i = 0; i < A.normal_power_log2; ++i) wn = wn * wn;
-    const float d = dot3(pn, v3{qp.x - pp.x, qp.y - pp.y, qp.z - pp.z}) / A.sigma_plane;
-    const float wz = 1.0f / (1.0f + d * d);
+    const float wn = weight_n(pn, qn, A.normal_power_log2);
+    const float wz = weight_z(pn, pp, qp, A.sigma_plane);
     float wc = 1.0f;
     if (A.use_color) {
         const v3 e = v3{pc.x - qc.x, pc.y - qc.y, pc.z - qc.z};
@@ -86,24 +60,15 @@ __device__ __forceinline__ void tap(Sums &s, float h, const PassArgs &A, v3 pn, 
     s.b = s.b + w * qc.z;
 }
 
-// the B3 spline (1/16, 1/4, 3/8, 1/4, 1/16): every product of two entries is exact in f32
-__device__ __forceinline__ constexpr float b3(int i) {
-    return i == 0 ? 0.375f : (i == 1 || i == -1) ? 0.25f : 0.0625f;
-}
-
 // Steps >= 4: every tap straight from memory.  A wave covers 64 consecutive pixels of a row.
-constexpr uint32_t kTileX = 64, kTileY = 4;
-
 __global__ __launch_bounds__(kTileX * kTileY) void atrous_kernel(
     const float *__restrict__ in, const float4 *__restrict__ guide, float *__restrict__ out,
     uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t step, PassArgs A)
 {
-    const uint32_t by = blockIdx.x / tiles_x, bx = blockIdx.x - by * tiles_x;
-    const uint32_t x = bx * kTileX + (threadIdx.x & (kTileX - 1u));
-    const uint32_t y = by * kTileY + (threadIdx.x / kTileX);
+    const auto [bx, by, x, y] = tile_pixel(tiles_x);
     if (x >= width || y >= height) return;
     const size_t p = (size_t)y * width + x;
-    const v3 pc = v3{in[3 * p], in[3 * p + 1], in[3 * p + 2]};
+    const v3 pc = load3(in, p);
     const float4 p0 = guide[2 * p], p1 = guide[2 * p + 1];
     v3 o = pc;                                   // a pixel that is not live passes through
     if (live(p0, p1, pc)) {
@@ -118,7 +83,7 @@ __global__ __launch_bounds__(kTileX * kTileY) void atrous_kernel(
                 if (qx >= width || qy >= height) continue;
                 const size_t q = (size_t)qy * width + qx;
                 const float4 q0 = guide[2 * q], q1 = guide[2 * q + 1];
-                const v3 qc = v3{in[3 * q], in[3 * q + 1], in[3 * q + 2]};
+                const v3 qc = load3(in, q);
                 if (!live(q0, q1, qc)) continue;
                 tap(s, b3(dy) * b3(dx), A, pn, pp, pc, v3{q1.x, q1.y, q1.z}, v3{q0.x, q0.y, q0.z},
                     qc);
@@ -130,17 +95,13 @@ __global__ __launch_bounds__(kTileX * kTileY) void atrous_kernel(
         // finite values whose products overflow, included) leave the colour as it came.
         if (s.w > 0.0f) o = v3{s.r / s.w, s.g / s.w, s.b / s.w};
     }
-    out[3 * p] = o.x;
-    out[3 * p + 1] = o.y;
-    out[3 * p + 2] = o.z;
+    store3(out, p, o);
 }
 
 // Steps 1 and 2: the tile and its halo in LDS.  (32 + 4 STEP) x (8 + 4 STEP) texels, 40 B each:
 // 17.3 KB (STEP 1) and 25.6 KB (STEP 2) per workgroup.  A halo texel outside the frame only gets
 // its flag cleared; of an unflagged texel nothing but the flag is read, except by its own pixel
 // (inside the frame, so loaded), which passes its colour through.
-constexpr uint32_t kLX = 32, kLY = 8;
-
 template <uint32_t STEP>
 __global__ __launch_bounds__(kLX * kLY) void atrous_lds_kernel(
     const float *__restrict__ in, const float4 *__restrict__ guide, float *__restrict__ out,
@@ -162,7 +123,7 @@ __global__ __launch_bounds__(kLX * kLY) void atrous_lds_kernel(
             const float4 q0 = guide[2 * q], q1 = guide[2 * q + 1];
             s_px[i] = q0.x; s_py[i] = q0.y; s_pz[i] = q0.z;
             s_nx[i] = q1.x; s_ny[i] = q1.y; s_nz[i] = q1.z;
-            const v3 qc = v3{in[3 * q], in[3 * q + 1], in[3 * q + 2]};
+            const v3 qc = load3(in, q);
             s_r[i] = qc.x; s_g[i] = qc.y; s_b[i] = qc.z;
             ok = live(q0, q1, qc) ? 1u : 0u;     // the live flag, once per staged texel
         }
@@ -192,9 +153,7 @@ __global__ __launch_bounds__(kLX * kLY) void atrous_lds_kernel(
         if (s.w > 0.0f) o = v3{s.r / s.w, s.g / s.w, s.b / s.w};      // as atrous_kernel
     }
     const size_t p = (size_t)y * width + x;
-    out[3 * p] = o.x;
-    out[3 * p + 1] = o.y;
-    out[3 * p + 2] = o.z;
+    store3(out, p, o);
 }
 
 }  // namespace

@@ -368,7 +368,7 @@ int rvcp_launch_temporal(const float *cur_c, const void *cur_g, const float *pre
                          const struct rvcp_temporal_view *view,
                          const struct rvcp_temporal_params *params, void *stream);
 // SVGF (rvcp_svgf.hip): the accumulation step with moments (modes as
-// rvcp_launch_temporal), moments -> variance, and one variance-guided a-trous pass (step = 2^i,
+// rvcp_launch_temporal, whose body it shares in rvcp_temporal.hip), moments -> variance, and one variance-guided a-trous pass (step = 2^i,
 // sigma_l2 = sigma_luminance^2; use_lum = 0: the luminance weight is 1; force_direct: steps 1
 // and 2 through the direct kernel too)
 int rvcp_launch_svgf_temporal(const float *cur_c, const void *cur_g, const float *prev_c,

@@ -1,12 +1,10 @@
-// rvcp_svgf.hip -- spatiotemporal variance-guided filtering behind rvcp_svgf_accumulate_async and
-// rvcp_svgf_filter_async (Schied et al.: "Spatiotemporal Variance-Guided Filtering", HPG 2017;
-// DESIGN.md §4.11).  The reference has no counterpart (it stores the raw frame,
-// ray_tracer_games101_branch.comp:497-500).
+// rvcp_svgf.hip -- spatiotemporal variance-guided filtering behind rvcp_svgf_filter_async
+// (Schied et al.: "Spatiotemporal Variance-Guided Filtering", HPG 2017).
+// The reference has no counterpart (it stores the raw frame,
+// ray_tracer_games101_branch.comp:497-500).  The accumulation with moments (§4.11 A,
+// svgf_temporal_kernel) shares its body with temporal_kernel and lives in rvcp_temporal.hip.
 //
-// Three kinds of kernel, one lane per pixel each:
-//   svgf_temporal_kernel   the accumulation step of rvcp_temporal.hip (§4.10; the same taps, the
-//     same acceptance rules, the same colour and length bits) which also carries the first two
-//     moments of the luminance through the taps: 8 B more per tap and per pixel.
+// Two kinds of kernel, one lane per pixel each:
 //   svgf_variance_kernel   moments -> variance.  A pixel whose history is at least spatial_below
 //     frames long takes m2 - m1^2; a younger one the same statistic over its 7 x 7 neighbourhood
 //     under the geometric weights, scaled by spatial_below / len.  The workgroup's 32 x 8 pixels
@@ -26,178 +24,15 @@
 // restatement, reproduces every output bit.
 #include <hip/hip_runtime.h>
 
-#include <stdint.h>
+#include "rvcp_post.h"
 
-#include "../../include/rvcp.h"
+using namespace rvcp;
 
 namespace {
-
-// a pixel takes part when its primary ray hit a non-emissive surface (as rvcp_denoise.hip)
-__device__ __forceinline__ bool filterable_w(uint32_t face, uint32_t material) {
-    return face != RVCP_GBUFFER_MISS && !(material & RVCP_GBUFFER_EMISSIVE);
-}
-__device__ __forceinline__ bool filterable(float4 g0, float4 g1) {
-    return filterable_w(__float_as_uint(g0.w), __float_as_uint(g1.w));
-}
-
-struct v3 { float x, y, z; };
-
-// neither an infinity nor a NaN: the exponent field is not all ones
-__device__ __forceinline__ bool finite1(float a) {
-    return (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;
-}
-__device__ __forceinline__ bool finite3(float a, float b, float c) {
-    return finite1(a) && finite1(b) && finite1(c);
-}
-
-// A texel is live for a launch when it is filterable and every float the launch reads from it is
-// finite: position and normal here, plus the colour, the moments or the variance
-// where a kernel reads them.  Any other texel is treated as a MISS texel.
-__device__ __forceinline__ bool live_g(float4 g0, float4 g1) {
-    return filterable(g0, g1) && finite3(g0.x, g0.y, g0.z) && finite3(g1.x, g1.y, g1.z);
-}
-
-// (a.x b.x + a.y b.y) + a.z b.z, each operation rounded
-__device__ __forceinline__ float dot3(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-
-// l(c) = (0.2126 r + 0.7152 g) + 0.0722 b, each operation rounded
-__device__ __forceinline__ float lum(v3 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
-
-// w_n = max(0, n_p . n_q), squared npl2 times (§4.9)
-__device__ __forceinline__ float weight_n(v3 pn, v3 qn, uint32_t npl2) {
-    const float dn = dot3(pn, qn);
-    float wn = dn > 0.0f ? dn : 0.0f;
-    for (uint32_t i = 0; i < npl2; ++i) wn = wn * wn;
-    return wn;
-}
-
-// w_z = 1 / (1 + d^2), d = n_p . (pos_q - pos_p) / sigma_plane (§4.9)
-__device__ __forceinline__ float weight_z(v3 pn, v3 pp, v3 qp, float sigma_plane) {
-    const float d = dot3(pn, v3{qp.x - pp.x, qp.y - pp.y, qp.z - pp.z}) / sigma_plane;
-    return 1.0f / (1.0f + d * d);
-}
-
-// ---------------------------------------------------------------------------------------------
-// A. accumulation with moments
-// ---------------------------------------------------------------------------------------------
-
-// running sums over the accepted taps: sum w, sum w c, sum w m, the shortest history
-struct HistSums { float w, r, g, b, m1, m2; uint32_t nmin; };
-
-// One history tap q = (qx, qy) of weight w (rvcp_temporal.hip's tap, plus the moments).  A tap
-// that is not live (position, normal, colour, moments) is rejected; the length of a rejected tap
-// is not read.
-__device__ __forceinline__ void hist_tap(HistSums &s, float w, int qx, int qy, uint32_t width,
-                                         uint32_t height, v3 pn, v3 pp, uint32_t pm,
-                                         float normal_min, float sigma_plane,
-                                         const float *__restrict__ prev_c,
-                                         const float4 *__restrict__ prev_g,
-                                         const uint32_t *__restrict__ prev_len,
-                                         const float2 *__restrict__ prev_m)
-{
-    // unsigned: -1 wraps to 2^32 - 1 >= width, height
-    if ((uint32_t)qx >= width || (uint32_t)qy >= height) return;
-    const size_t q = (size_t)(uint32_t)qy * width + (uint32_t)qx;
-    const float4 q0 = prev_g[2 * q], q1 = prev_g[2 * q + 1];
-    if (!live_g(q0, q1) || __float_as_uint(q1.w) != pm) return;
-    if (!(dot3(pn, v3{q1.x, q1.y, q1.z}) >= normal_min)) return;
-    const float d = dot3(pn, v3{q0.x - pp.x, q0.y - pp.y, q0.z - pp.z});
-    if (!(fabsf(d) <= sigma_plane)) return;
-    const v3 qc = v3{prev_c[3 * q], prev_c[3 * q + 1], prev_c[3 * q + 2]};
-    const float2 m = prev_m[q];
-    if (!finite3(qc.x, qc.y, qc.z) || !finite1(m.x) || !finite1(m.y)) return;
-    const uint32_t n = prev_len[q];
-    if (n < 1u) return;
-    s.w = s.w + w;
-    s.r = s.r + w * qc.x;
-    s.g = s.g + w * qc.y;
-    s.b = s.b + w * qc.z;
-    s.m1 = s.m1 + w * m.x;
-    s.m2 = s.m2 + w * m.y;
-    s.nmin = n < s.nmin ? n : s.nmin;
-}
-
-constexpr uint32_t kTileX = 64, kTileY = 4;      // direct kernels: a wave covers 64 pixels of a row
-
-// mode: 0 no history, 1 identity (the camera did not move), 2 reprojection through `view`
-__global__ __launch_bounds__(kTileX * kTileY) void svgf_temporal_kernel(
-    const float *__restrict__ cur_c, const float4 *__restrict__ cur_g,
-    const float *__restrict__ prev_c, const float4 *__restrict__ prev_g,
-    const uint32_t *__restrict__ prev_len, const float2 *__restrict__ prev_m,
-    float *__restrict__ out_c, uint32_t *__restrict__ out_len, float2 *__restrict__ out_m,
-    uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t mode, rvcp_temporal_view_t view,
-    rvcp_temporal_params_t P, float alpha_moments_min)
-{
-    const uint32_t by = blockIdx.x / tiles_x, bx = blockIdx.x - by * tiles_x;
-    const uint32_t x = bx * kTileX + (threadIdx.x & (kTileX - 1u));
-    const uint32_t y = by * kTileY + (threadIdx.x / kTileX);
-    if (x >= width || y >= height) return;
-    const size_t p = (size_t)y * width + x;
-    const v3 c = v3{cur_c[3 * p], cur_c[3 * p + 1], cur_c[3 * p + 2]};
-    const float4 p0 = cur_g[2 * p], p1 = cur_g[2 * p + 1];
-    v3 o = c;                                    // no usable history: the current colour
-    float2 om = make_float2(0.0f, 0.0f);         // a pixel that is not live keeps no moments
-    uint32_t len = 0;                            // ... and no history
-    if (live_g(p0, p1) && finite3(c.x, c.y, c.z)) {
-        len = 1;
-        const float l1 = lum(c);
-        const float2 mu = make_float2(l1, l1 * l1);
-        om = mu;
-        const v3 pp = v3{p0.x, p0.y, p0.z}, pn = v3{p1.x, p1.y, p1.z};
-        const uint32_t pm = __float_as_uint(p1.w);
-        HistSums s = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0xFFFFFFFFu};
-        if (mode == 1u) {
-            hist_tap(s, 1.0f, (int)x, (int)y, width, height, pn, pp, pm, P.normal_min,
-                     P.sigma_plane, prev_c, prev_g, prev_len, prev_m);
-        } else if (mode == 2u) {
-            const v3 e = v3{pp.x - view.position[0], pp.y - view.position[1], pp.z - view.position[2]};
-            const float z = dot3(e, v3{view.forward[0], view.forward[1], view.forward[2]});
-            const float a = dot3(e, v3{view.right[0], view.right[1], view.right[2]});
-            const float b = dot3(e, v3{view.down[0], view.down[1], view.down[2]});
-            const float fw = (float)width, fh = (float)height;
-            const float fx = ((a / z) * view.k + 0.5f * fw) - 0.5f;
-            const float fy = ((b / z) * view.k + 0.5f * fh) - 0.5f;
-            // (a NaN fails every comparison) -- the floats become integers only inside the range
-            if (z > 0.0f && fx >= -1.0f && fx < fw && fy >= -1.0f && fy < fh) {
-                const float xf = floorf(fx), yf = floorf(fy);
-                const float tx = fx - xf, ty = fy - yf;
-                const int x0 = (int)xf, y0 = (int)yf;
-                const float ux = 1.0f - tx, uy = 1.0f - ty;
-                hist_tap(s, ux * uy, x0, y0, width, height, pn, pp, pm, P.normal_min,
-                         P.sigma_plane, prev_c, prev_g, prev_len, prev_m);
-                hist_tap(s, tx * uy, x0 + 1, y0, width, height, pn, pp, pm, P.normal_min,
-                         P.sigma_plane, prev_c, prev_g, prev_len, prev_m);
-                hist_tap(s, ux * ty, x0, y0 + 1, width, height, pn, pp, pm, P.normal_min,
-                         P.sigma_plane, prev_c, prev_g, prev_len, prev_m);
-                hist_tap(s, tx * ty, x0 + 1, y0 + 1, width, height, pn, pp, pm, P.normal_min,
-                         P.sigma_plane, prev_c, prev_g, prev_len, prev_m);
-            }
-        }
-        if (s.w > 0.0f) {
-            const v3 h = v3{s.r / s.w, s.g / s.w, s.b / s.w};
-            const float2 hm = make_float2(s.m1 / s.w, s.m2 / s.w);
-            // min(nmin + 1, max_history) without the overflow of nmin + 1
-            const uint32_t n = s.nmin >= P.max_history ? P.max_history : s.nmin + 1u;
-            const float inv = 1.0f / (float)n;
-            const float alpha = inv < P.alpha_min ? P.alpha_min : inv;
-            const float am = inv < alpha_moments_min ? alpha_moments_min : inv;
-            o = v3{h.x + alpha * (c.x - h.x), h.y + alpha * (c.y - h.y), h.z + alpha * (c.z - h.z)};
-            om = make_float2(hm.x + am * (mu.x - hm.x), hm.y + am * (mu.y - hm.y));
-            len = n;
-        }
-    }
-    out_c[3 * p] = o.x;
-    out_c[3 * p + 1] = o.y;
-    out_c[3 * p + 2] = o.z;
-    out_len[p] = len;
-    out_m[p] = om;
-}
 
 // ---------------------------------------------------------------------------------------------
 // B. variance
 // ---------------------------------------------------------------------------------------------
-constexpr uint32_t kLX = 32, kLY = 8;            // LDS kernels: a 32 x 8 tile
-
 __global__ __launch_bounds__(kLX * kLY) void svgf_variance_kernel(
     const float2 *__restrict__ mom, const uint32_t *__restrict__ len,
     const float4 *__restrict__ guide, float *__restrict__ out_v, uint32_t width, uint32_t height,
@@ -337,10 +172,6 @@ __device__ __forceinline__ bool live(float4 g0, float4 g1, v3 c, float v) {
     return live_g(g0, g1) && finite3(c.x, c.y, c.z) && finite1(v);
 }
 
-// the B3 spline (1/16, 1/4, 3/8, 1/4, 1/16): every product of two entries is exact in f32
-__device__ __forceinline__ constexpr float b3(int i) {
-    return i == 0 ? 0.375f : (i == 1 || i == -1) ? 0.25f : 0.0625f;
-}
 // the 3 x 3 prefilter of the variance: 1/4 centre, 1/8 edges, 1/16 corners
 __device__ __forceinline__ constexpr float g3(int dy, int dx) {
     return (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
@@ -352,12 +183,10 @@ __global__ __launch_bounds__(kTileX * kTileY) void svgf_atrous_kernel(
     const float4 *__restrict__ guide, float *__restrict__ out_c, float *__restrict__ out_v,
     uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t step, GuideArgs A)
 {
-    const uint32_t by = blockIdx.x / tiles_x, bx = blockIdx.x - by * tiles_x;
-    const uint32_t x = bx * kTileX + (threadIdx.x & (kTileX - 1u));
-    const uint32_t y = by * kTileY + (threadIdx.x / kTileX);
+    const auto [bx, by, x, y] = tile_pixel(tiles_x);
     if (x >= width || y >= height) return;
     const size_t p = (size_t)y * width + x;
-    const v3 pc = v3{in_c[3 * p], in_c[3 * p + 1], in_c[3 * p + 2]};
+    const v3 pc = load3(in_c, p);
     const float4 p0 = guide[2 * p], p1 = guide[2 * p + 1];
     v3 o = pc;                                   // a pixel that is not live passes through
     float ov = 0.0f;
@@ -376,7 +205,7 @@ __global__ __launch_bounds__(kTileX * kTileY) void svgf_atrous_kernel(
                     const size_t q = (size_t)qy * width + qx;
                     const float qv = in_v[q];
                     if (!live(guide[2 * q], guide[2 * q + 1],
-                              v3{in_c[3 * q], in_c[3 * q + 1], in_c[3 * q + 2]}, qv)) continue;
+                              load3(in_c, q), qv)) continue;
                     gs = gs + g3(dy, dx);
                     vs = vs + g3(dy, dx) * qv;
                 }
@@ -394,7 +223,7 @@ __global__ __launch_bounds__(kTileX * kTileY) void svgf_atrous_kernel(
                 if (qx >= width || qy >= height) continue;
                 const size_t q = (size_t)qy * width + qx;
                 const float4 q0 = guide[2 * q], q1 = guide[2 * q + 1];
-                const v3 qc = v3{in_c[3 * q], in_c[3 * q + 1], in_c[3 * q + 2]};
+                const v3 qc = load3(in_c, q);
                 const float qv = in_v[q];
                 if (!live(q0, q1, qc, qv)) continue;
                 tap(s, b3(dy) * b3(dx), A, den, lp, pn, pp, v3{q1.x, q1.y, q1.z},
@@ -403,9 +232,7 @@ __global__ __launch_bounds__(kTileX * kTileY) void svgf_atrous_kernel(
         }
         finish(s, o, ov);
     }
-    out_c[3 * p] = o.x;
-    out_c[3 * p + 1] = o.y;
-    out_c[3 * p + 2] = o.z;
+    store3(out_c, p, o);
     out_v[p] = ov;
 }
 
@@ -436,7 +263,7 @@ __global__ __launch_bounds__(kLX * kLY) void svgf_atrous_lds_kernel(
             const float4 q0 = guide[2 * q], q1 = guide[2 * q + 1];
             s_px[i] = q0.x; s_py[i] = q0.y; s_pz[i] = q0.z;
             s_nx[i] = q1.x; s_ny[i] = q1.y; s_nz[i] = q1.z;
-            const v3 qc = v3{in_c[3 * q], in_c[3 * q + 1], in_c[3 * q + 2]};
+            const v3 qc = load3(in_c, q);
             const float qv = in_v[q];
             s_r[i] = qc.x; s_g[i] = qc.y; s_b[i] = qc.z;
             s_v[i] = qv;
@@ -486,31 +313,11 @@ __global__ __launch_bounds__(kLX * kLY) void svgf_atrous_lds_kernel(
         finish(s, o, ov);
     }
     const size_t p = (size_t)y * width + x;
-    out_c[3 * p] = o.x;
-    out_c[3 * p + 1] = o.y;
-    out_c[3 * p + 2] = o.z;
+    store3(out_c, p, o);
     out_v[p] = ov;
 }
 
 }  // namespace
-
-extern "C" int rvcp_launch_svgf_temporal(const float *cur_c, const void *cur_g, const float *prev_c,
-                                         const void *prev_g, const uint32_t *prev_len,
-                                         const float *prev_m, float *out_c, uint32_t *out_len,
-                                         float *out_m, uint32_t width, uint32_t height,
-                                         uint32_t mode, const rvcp_temporal_view_t *view,
-                                         const rvcp_temporal_params_t *params,
-                                         float alpha_moments_min, void *stream)
-{
-    const uint32_t tx = (width + kTileX - 1) / kTileX, ty = (height + kTileY - 1) / kTileY;
-    rvcp_temporal_view_t V = {};
-    if (view) V = *view;
-    hipLaunchKernelGGL(svgf_temporal_kernel, dim3(tx * ty), dim3(kTileX * kTileY), 0,
-                       (hipStream_t)stream, cur_c, (const float4 *)cur_g, prev_c,
-                       (const float4 *)prev_g, prev_len, (const float2 *)prev_m, out_c, out_len,
-                       (float2 *)out_m, width, height, tx, mode, V, *params, alpha_moments_min);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
 
 extern "C" int rvcp_launch_svgf_variance(const float *moments, const uint32_t *len,
                                          const void *gbuffer, float *out_v, uint32_t width,

@@ -23,34 +23,12 @@
 // restatement, reproduces every output bit.
 #include <hip/hip_runtime.h>
 
-#include <stdint.h>
-
-#include "../../include/rvcp.h"
+#include "rvcp_post.h"
 #include "rvcp_tonemap.h"
 
 namespace rvcp {
 
 namespace {
-
-struct v3 { float x, y, z; };
-
-// (a.x b.x + a.y b.y) + a.z b.z, each operation rounded
-__device__ __forceinline__ float dot3(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ v3 vec(const float a[3]) { return v3{a[0], a[1], a[2]}; }
-
-// gamma_u8's own clamp: the displayed value of a linear channel (a NaN displays as 0)
-__device__ __forceinline__ float sat(float c) { return (c > 0.0f) ? ((c < 1.0f) ? c : 1.0f) : 0.0f; }
-
-// min(max(h, lo), hi) written as selections, so that a NaN history takes lo and no rule about
-// signed zeros is needed: max(h, lo) = h >= lo ? h : lo, min(m, hi) = m <= hi ? m : hi
-__device__ __forceinline__ float clamp_to(float h, float lo, float hi) {
-    const float m = (h >= lo) ? h : lo;
-    return (m <= hi) ? m : hi;
-}
-
-__device__ __forceinline__ v3 load_sat(const float *__restrict__ c, size_t p) {
-    return v3{sat(c[3 * p]), sat(c[3 * p + 1]), sat(c[3 * p + 2])};
-}
 
 // running sums over the accepted taps: sum w, sum w c, the shortest history
 struct Sums { float w, r, g, b; uint32_t nmin; };
@@ -72,21 +50,6 @@ __device__ __forceinline__ void tap(Sums &s, float w, int qx, int qy, uint32_t w
     s.nmin = n < s.nmin ? n : s.nmin;
 }
 
-// the pixel coordinates of world point x under view V (§4.10's e, z, a, b, fx, fy)
-__device__ __forceinline__ bool project(const rvcp_temporal_view_t &V, v3 x, float fw, float fh,
-                                        float &fx, float &fy)
-{
-    const v3 e = v3{x.x - V.position[0], x.y - V.position[1], x.z - V.position[2]};
-    const float z = dot3(e, vec(V.forward));
-    const float a = dot3(e, vec(V.right));
-    const float b = dot3(e, vec(V.down));
-    fx = ((a / z) * V.k + 0.5f * fw) - 0.5f;
-    fy = ((b / z) * V.k + 0.5f * fh) - 0.5f;
-    return z > 0.0f;
-}
-
-constexpr uint32_t kTileX = 64, kTileY = 4;
-
 }  // namespace
 
 // mode: 0 no history, 1 identity (the camera is at rest), 2 reprojection from `cur` into `prev`
@@ -97,58 +60,24 @@ __global__ __launch_bounds__(kTileX * kTileY) void taa_resolve_kernel(
     const float *__restrict__ gamma_t, uint32_t width, uint32_t height, uint32_t tiles_x,
     uint32_t mode, rvcp_temporal_view_t cur, rvcp_temporal_view_t prev, rvcp_taa_params_t P)
 {
-    const uint32_t by = blockIdx.x / tiles_x, bx = blockIdx.x - by * tiles_x;
-    const uint32_t x = bx * kTileX + (threadIdx.x & (kTileX - 1u));
-    const uint32_t y = by * kTileY + (threadIdx.x / kTileX);
+    const auto [bx, by, x, y] = tile_pixel(tiles_x);
     if (x >= width || y >= height) return;
     const size_t p = (size_t)y * width + x;
     const v3 c = load_sat(cur_c, p);
     v3 o = c;                                    // no usable history: the displayed current colour
     uint32_t len = 1;
     Sums s = {0.0f, 0.0f, 0.0f, 0.0f, 0xFFFFFFFFu};
+    const auto hist = [&](float w, int qx, int qy) {
+        tap(s, w, qx, qy, width, height, prev_c, prev_len);
+    };
     if (mode == 1u) {
-        tap(s, 1.0f, (int)x, (int)y, width, height, prev_c, prev_len);
+        hist(1.0f, (int)x, (int)y);
     } else if (mode == 2u) {
         const float fw = (float)width, fh = (float)height;
-        const float4 g0 = cur_g[2 * p];          // position and face: the texel's first 16 bytes
         float fx, fy;
-        bool ok;
-        if (__float_as_uint(g0.w) != RVCP_GBUFFER_MISS) {
-            const v3 pos = v3{g0.x, g0.y, g0.z};
-            float ux, uy, vx, vy;
-            const bool oku = project(cur, pos, fw, fh, ux, uy);
-            const bool okv = project(prev, pos, fw, fh, vx, vy);
-            ok = oku && okv;
-            fx = (float)x + (vx - ux);
-            fy = (float)y + (vy - uy);
-        } else {
-            // the background is at infinity: the pixel's direction through the current camera,
-            // projected by the previous one (only the rotation moves it)
-            const float ff = dot3(vec(cur.forward), vec(cur.forward));
-            const v3 fwd = v3{cur.forward[0] / ff, cur.forward[1] / ff, cur.forward[2] / ff};
-            const float sx = (((float)x + 0.5f) - 0.5f * fw) / cur.k;
-            const float sy = (((float)y + 0.5f) - 0.5f * fh) / cur.k;
-            const v3 d = v3{(fwd.x + sx * cur.right[0]) + sy * cur.down[0],
-                            (fwd.y + sx * cur.right[1]) + sy * cur.down[1],
-                            (fwd.z + sx * cur.right[2]) + sy * cur.down[2]};
-            const float z = dot3(d, vec(prev.forward));
-            const float a = dot3(d, vec(prev.right));
-            const float b = dot3(d, vec(prev.down));
-            ok = z > 0.0f;
-            fx = ((a / z) * prev.k + 0.5f * fw) - 0.5f;
-            fy = ((b / z) * prev.k + 0.5f * fh) - 0.5f;
-        }
-        // (a NaN fails every comparison) -- the floats become integers only inside the range
-        if (ok && fx >= -1.0f && fx < fw && fy >= -1.0f && fy < fh) {
-            const float xf = floorf(fx), yf = floorf(fy);
-            const float tx = fx - xf, ty = fy - yf;
-            const int x0 = (int)xf, y0 = (int)yf;
-            const float ux = 1.0f - tx, uy = 1.0f - ty;
-            tap(s, ux * uy, x0, y0, width, height, prev_c, prev_len);
-            tap(s, tx * uy, x0 + 1, y0, width, height, prev_c, prev_len);
-            tap(s, ux * ty, x0, y0 + 1, width, height, prev_c, prev_len);
-            tap(s, tx * ty, x0 + 1, y0 + 1, width, height, prev_c, prev_len);
-        }
+        // cur_g[2 * p]: position and face, the texel's first 16 bytes
+        const bool ok = history_point(cur_g[2 * p], (float)x, (float)y, cur, prev, fw, fh, fx, fy);
+        bilinear_taps(ok, fx, fy, fw, fh, hist);
     }
     if (s.w > 0.0f) {
         v3 h = v3{s.r / s.w, s.g / s.w, s.b / s.w};
@@ -174,9 +103,7 @@ __global__ __launch_bounds__(kTileX * kTileY) void taa_resolve_kernel(
         o = v3{h.x + alpha * (c.x - h.x), h.y + alpha * (c.y - h.y), h.z + alpha * (c.z - h.z)};
         len = n;
     }
-    out_c[3 * p] = o.x;
-    out_c[3 * p + 1] = o.y;
-    out_c[3 * p + 2] = o.z;
+    store3(out_c, p, o);
     out_len[p] = len;
     if (out_rgba) out_rgba[p] = pack_rgb8(o.x, o.y, o.z, gamma_t);
 }

@@ -31,38 +31,17 @@
 // restatement, reproduces every output bit.
 #include <hip/hip_runtime.h>
 
-#include <stdint.h>
-
-#include "../../include/rvcp.h"
+#include "rvcp_post.h"
 #include "rvcp_tonemap.h"
 
 namespace rvcp {
 
 namespace {
 
-struct v3 { float x, y, z; };
-
-// (a.x b.x + a.y b.y) + a.z b.z, each operation rounded
-__device__ __forceinline__ float dot3(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ v3 vec(const float a[3]) { return v3{a[0], a[1], a[2]}; }
-
-// gamma_u8's own clamp: the displayed value of a linear channel (a NaN displays as 0)
-__device__ __forceinline__ float sat(float c) { return (c > 0.0f) ? ((c < 1.0f) ? c : 1.0f) : 0.0f; }
-
-// §4.13's two selections: a NaN history takes lo
-__device__ __forceinline__ float clamp_to(float h, float lo, float hi) {
-    const float m = (h >= lo) ? h : lo;
-    return (m <= hi) ? m : hi;
-}
-
 // 1 - |t| where that is positive, else 0 (a NaN gives 0)
 __device__ __forceinline__ float tent(float t) {
     const float u = 1.0f - fabsf(t);
     return (u > 0.0f) ? u : 0.0f;
-}
-
-__device__ __forceinline__ v3 load_sat(const float *__restrict__ c, size_t p) {
-    return v3{sat(c[3 * p]), sat(c[3 * p + 1]), sat(c[3 * p + 2])};
 }
 
 // running sums over the accepted history taps: sum w, sum w c, sum w weight
@@ -85,41 +64,6 @@ __device__ __forceinline__ void tap(Sums &s, float w, int qx, int qy, uint32_t w
     s.wt = s.wt + w * n;
 }
 
-// the pixel coordinates of world point x under view V (§4.10's e, z, a, b, fx, fy)
-__device__ __forceinline__ bool project(const rvcp_temporal_view_t &V, v3 x, float fw, float fh,
-                                        float &fx, float &fy)
-{
-    const v3 e = v3{x.x - V.position[0], x.y - V.position[1], x.z - V.position[2]};
-    const float z = dot3(e, vec(V.forward));
-    const float a = dot3(e, vec(V.right));
-    const float b = dot3(e, vec(V.down));
-    fx = ((a / z) * V.k + 0.5f * fw) - 0.5f;
-    fy = ((b / z) * V.k + 0.5f * fh) - 0.5f;
-    return z > 0.0f;
-}
-
-// §4.13's miss-pixel mapping: where the centre direction of pixel (x, y) of V's gw x gh grid
-// falls in P's fw x fh grid (only the rotation between the two moves it)
-__device__ __forceinline__ bool direction_to(const rvcp_temporal_view_t &V, float x, float y,
-                                             float gw, float gh, const rvcp_temporal_view_t &P,
-                                             float fw, float fh, float &fx, float &fy)
-{
-    const float ff = dot3(vec(V.forward), vec(V.forward));
-    const v3 fwd = v3{V.forward[0] / ff, V.forward[1] / ff, V.forward[2] / ff};
-    const float sx = ((x + 0.5f) - 0.5f * gw) / V.k;
-    const float sy = ((y + 0.5f) - 0.5f * gh) / V.k;
-    const v3 d = v3{(fwd.x + sx * V.right[0]) + sy * V.down[0],
-                    (fwd.y + sx * V.right[1]) + sy * V.down[1],
-                    (fwd.z + sx * V.right[2]) + sy * V.down[2]};
-    const float z = dot3(d, vec(P.forward));
-    const float a = dot3(d, vec(P.right));
-    const float b = dot3(d, vec(P.down));
-    fx = ((a / z) * P.k + 0.5f * fw) - 0.5f;
-    fy = ((b / z) * P.k + 0.5f * fh) - 0.5f;
-    return z > 0.0f;
-}
-
-constexpr uint32_t kTileX = 64, kTileY = 4;
 // the staged traced pixels of a tile: kTileX / 2 + 2 columns by kTileY / 2 + 2 rows at scale 2,
 // fewer at scales 3 and 4 (the row stride stays)
 constexpr uint32_t kStageW = kTileX / 2 + 2, kStageH = kTileY / 2 + 2, kStageN = kStageW * kStageH;
@@ -156,9 +100,7 @@ __global__ __launch_bounds__(kTileX * kTileY) void taa_upsample_kernel(
     uint32_t tiles_x, uint32_t mode, rvcp_temporal_view_t jit, rvcp_temporal_view_t cur,
     rvcp_temporal_view_t prev, rvcp_taau_params_t P)
 {
-    const uint32_t by = blockIdx.x / tiles_x, bx = blockIdx.x - by * tiles_x;
-    const uint32_t x = bx * kTileX + (threadIdx.x & (kTileX - 1u));
-    const uint32_t y = by * kTileY + (threadIdx.x / kTileX);
+    const auto [bx, by, x, y] = tile_pixel(tiles_x);
     const uint32_t lw = width / scale, lh = height / scale;
     const float fw = (float)width, fh = (float)height, flw = (float)lw, flh = (float)lh;
     // the traced pixel left of and above the tile's first one: staged entry (0, 0); -1 on the
@@ -214,34 +156,16 @@ __global__ __launch_bounds__(kTileX * kTileY) void taa_upsample_kernel(
     const float Wn = t.Wn, Ww = t.Ww;
     const v3 Sn = t.Sn, Sw = t.Sw, lo = t.lo, hi = t.hi;
     Sums s = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    const auto hist = [&](float w, int qx, int qy) {
+        tap(s, w, qx, qy, width, height, prev_c, prev_w);
+    };
     if (mode == 1u) {
-        tap(s, 1.0f, (int)x, (int)y, width, height, prev_c, prev_w);
+        hist(1.0f, (int)x, (int)y);
     } else if (mode == 2u) {
-        const float4 g0 = g_hi[2 * p];           // position and face: the texel's first 16 bytes
         float fx, fy;
-        bool ok;
-        if (__float_as_uint(g0.w) != RVCP_GBUFFER_MISS) {
-            const v3 pos = v3{g0.x, g0.y, g0.z};
-            float ux, uy, vx, vy;
-            const bool oku = project(cur, pos, fw, fh, ux, uy);
-            const bool okv = project(prev, pos, fw, fh, vx, vy);
-            ok = oku && okv;
-            fx = fpx + (vx - ux);
-            fy = fpy + (vy - uy);
-        } else {
-            ok = direction_to(cur, fpx, fpy, fw, fh, prev, fw, fh, fx, fy);
-        }
-        // (a NaN fails every comparison) -- the floats become integers only inside the range
-        if (ok && fx >= -1.0f && fx < fw && fy >= -1.0f && fy < fh) {
-            const float xf = floorf(fx), yf = floorf(fy);
-            const float tx = fx - xf, ty = fy - yf;
-            const int x0 = (int)xf, y0 = (int)yf;
-            const float ux = 1.0f - tx, uy = 1.0f - ty;
-            tap(s, ux * uy, x0, y0, width, height, prev_c, prev_w);
-            tap(s, tx * uy, x0 + 1, y0, width, height, prev_c, prev_w);
-            tap(s, ux * ty, x0, y0 + 1, width, height, prev_c, prev_w);
-            tap(s, tx * ty, x0 + 1, y0 + 1, width, height, prev_c, prev_w);
-        }
+        // g_hi[2 * p]: position and face, the texel's first 16 bytes
+        const bool ok = history_point(g_hi[2 * p], fpx, fpy, cur, prev, fw, fh, fx, fy);
+        bilinear_taps(ok, fx, fy, fw, fh, hist);
     }
     v3 o;
     float wt;
@@ -259,9 +183,7 @@ __global__ __launch_bounds__(kTileX * kTileY) void taa_upsample_kernel(
         o = (Ww > 0.0f) ? v3{Sw.x / Ww, Sw.y / Ww, Sw.z / Ww} : c0;
         wt = P.init_weight;
     }
-    out_c[3 * p] = o.x;
-    out_c[3 * p + 1] = o.y;
-    out_c[3 * p + 2] = o.z;
+    store3(out_c, p, o);
     out_w[p] = wt;
     if (out_rgba) out_rgba[p] = pack_rgb8(o.x, o.y, o.z, gamma_t);
 }
