@@ -5,7 +5,10 @@
  * a binary PPM and prints one JSON line of stats per frame.
  *
  *   make -C examples            # gcc, links ../rvcp-real-time-path-tracer_amd/csrc/build/librvcp.so
- *   examples/build/rvcp_render scene.rvcpscn W H SPP TIME FRAMES out.ppm
+ *   examples/build/rvcp_render scene.rvcpscn W H SPP TIME FRAMES out.ppm [--cosine]
+ *
+ * --cosine: trace with the cosine-weighted bounce (rvcp_set_sampling) instead of
+ * the shader's uniform one: less noise per sample, frames no longer the reference's bit for bit.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -22,8 +25,9 @@ static int die(rvcp_ctx_t *ctx, const char *what, int rc)
 
 int main(int argc, char **argv)
 {
-    if (argc != 8) {
-        fprintf(stderr, "usage: %s scene.rvcpscn W H SPP TIME FRAMES out.ppm\n", argv[0]);
+    const int cosine = argc == 9 && strcmp(argv[8], "--cosine") == 0;
+    if (argc != 8 && !cosine) {
+        fprintf(stderr, "usage: %s scene.rvcpscn W H SPP TIME FRAMES out.ppm [--cosine]\n", argv[0]);
         return 2;
     }
     const uint32_t W = (uint32_t)strtoul(argv[2], NULL, 10);
@@ -45,6 +49,10 @@ int main(int argc, char **argv)
     rvcp_ctx_t *ctx = NULL;
     rc = rvcp_create(&cfg, &ctx);             /* == create_compute_pipeline (vulkan.rs:576) */
     if (rc) return die(ctx, "rvcp_create", rc);
+    if (cosine) {                             /* no counterpart in the reference */
+        rc = rvcp_set_sampling(ctx, RVCP_SAMPLING_COSINE);
+        if (rc) return die(ctx, "rvcp_set_sampling", rc);
+    }
 
     rvcp_push_constant_t push;
     memset(&push, 0, sizeof(push));

@@ -1039,6 +1039,36 @@ int rvcp_set_taa_upsample(rvcp_ctx_t *ctx, uint32_t scale);
 /* *scale = the context's upsampling scale.  No counterpart in the reference. */
 int rvcp_get_taa_upsample(rvcp_ctx_t *ctx, uint32_t *scale);
 
+/* ---------------------------------------------------------------------------------------
+ * Bounce sampling of the games101 integrator (opt-in).  The reference's README
+ * lists "Important Sampling" as a TODO; its shader has no counterpart.
+ * ------------------------------------------------------------------------------------- */
+
+/* RVCP_SAMPLING_UNIFORM (the default): the shader's uniform hemisphere direction, weighted
+ * f cos / (max(0.1, pdf) rr); every frame is bit-identical to the oracle.
+ * RVCP_SAMPLING_COSINE: the continuation direction is normalize(n + normalize(p)), p the same
+ * accepted unit-ball sample (n where the sum vanishes), drawn with density cos / pi, and the
+ * path weight is the constant albedo / rr.  Everything else -- the primary ray, light sampling,
+ * Russian roulette, the attenuation stop, the miss and light terms, the number and order of
+ * rand() calls -- is unchanged.  The frames are NOT the oracle's: less noise per sample, more
+ * traversals per frame (paths live longer), and on a scene that rays can leave a slightly
+ * brighter expectation, because the shader adds its miss term unattenuated. */
+#define RVCP_SAMPLING_UNIFORM 0
+#define RVCP_SAMPLING_COSINE 1
+
+/* Set the context's bounce sampling; it holds from the next render on, through every entry point
+ * that renders (frames, shards, batches, the denoised / temporal / SVGF chains, the sub-contexts
+ * of n_gpus > 1) and across rvcp_upload_scene.  Scene-specialised kernels are compiled for the
+ * new mode by the first render after a change (cached per mode, in the process and on disk).
+ * Changing the value drops the histories of rvcp_render_temporal and rvcp_render_svgf; setting
+ * the value it has does nothing.  RVCP_E_INVALID: a null context, an unknown value, a frame
+ * pending.  RVCP_E_UNSUPPORTED: RVCP_SAMPLING_COSINE on a RVCP_INTEGRATOR_LEGACY context
+ * (ray_tracer.comp's diffuse scatter is cosine-weighted already). */
+int rvcp_set_sampling(rvcp_ctx_t *ctx, int32_t sampling);
+
+/* *sampling = the context's bounce sampling. */
+int rvcp_get_sampling(rvcp_ctx_t *ctx, int32_t *sampling);
+
 #ifdef __cplusplus
 }
 #endif

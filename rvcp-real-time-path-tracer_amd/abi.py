@@ -104,7 +104,8 @@ EXPORTED = ["rvcp_version", "rvcp_config_default", "rvcp_config_default_for", "r
             "rvcp_taa_resolve_async", "rvcp_taa_wait", "rvcp_set_taa", "rvcp_get_taa",
             "rvcp_taa_reset",
             "rvcp_taau_params_default", "rvcp_taa_upsample_async", "rvcp_taau_wait",
-            "rvcp_set_taa_upsample", "rvcp_get_taa_upsample"]
+            "rvcp_set_taa_upsample", "rvcp_get_taa_upsample",
+            "rvcp_set_sampling", "rvcp_get_sampling"]
 
 
 # Integrator mode 2 (ray_tracer.comp ray_trace): its own #defines (ray_tracer.comp:5-13).
@@ -116,6 +117,8 @@ INTEGRATOR_GAMES101, INTEGRATOR_LEGACY = 0, 1
 ACCEL_NONE, ACCEL_BVH = 0, 1
 UNORM_DRIVER, UNORM_NEAREST = 0, 1
 SPECIALIZE_AUTO, SPECIALIZE_OFF = 0, 1
+# rvcp_set_sampling: the games101 bounce
+SAMPLING_UNIFORM, SAMPLING_COSINE = 0, 1
 
 
 def make_config(**kw) -> np.ndarray:
@@ -328,6 +331,8 @@ def load():
     L.rvcp_taau_wait.argtypes = [P, P]
     L.rvcp_set_taa_upsample.argtypes = [P, u32]
     L.rvcp_get_taa_upsample.argtypes = [P, P]
+    L.rvcp_set_sampling.argtypes = [P, ctypes.c_int32]
+    L.rvcp_get_sampling.argtypes = [P, P]
     for name in ("rvcp_config_default", "rvcp_config_default_for", "rvcp_create", "rvcp_destroy", "rvcp_upload_scene",
                  "rvcp_render", "rvcp_render_shard_async", "rvcp_sync_stats",
                  "rvcp_assemble_frame_async", "rvcp_upload_scene_file", "rvcp_mandelbrot",
@@ -346,7 +351,8 @@ def load():
                  "rvcp_taa_jitter", "rvcp_taa_jitter_push", "rvcp_taa_params_default",
                  "rvcp_taa_resolve_async", "rvcp_taa_wait", "rvcp_set_taa", "rvcp_get_taa",
                  "rvcp_taa_reset", "rvcp_taau_params_default", "rvcp_taa_upsample_async",
-                 "rvcp_taau_wait", "rvcp_set_taa_upsample", "rvcp_get_taa_upsample"):
+                 "rvcp_taau_wait", "rvcp_set_taa_upsample", "rvcp_get_taa_upsample",
+                 "rvcp_set_sampling", "rvcp_get_sampling"):
         getattr(L, name).restype = ctypes.c_int
     if L.rvcp_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI revision {L.rvcp_abi_version()}, this binding "

@@ -134,6 +134,9 @@ struct rvcp_ctx {
     int grid_capacity[kMaxVariant + 1] = {};   // resident workgroups per kernel variant
     int legacy_capacity = 0;                   // ... of the RVCP_INTEGRATOR_LEGACY kernel
     int bvh_capacity = 0;                      // ... of the RVCP_ACCEL_BVH path kernel
+    // the same for the cosine builds of the games101 kernels (rvcp_kernels_cosine.hip)
+    int grid_capacity_cos[kMaxVariant + 1] = {};
+    int bvh_capacity_cos = 0;
     uint32_t n_simds = 1024;
 
     // scene (device)
@@ -163,6 +166,14 @@ struct rvcp_ctx {
     // scene-specialised path kernels (rvcp_jit.cpp), or null: generic kernels
     std::shared_ptr<JitKernels> jit;
     std::string jit_err;
+    // bounce sampling (rvcp_set_sampling).  A games101 module is compiled for
+    // one mode: jit_sampling is the mode ctx->jit was asked for, jit_tri / jit_bvh what upload
+    // asked it with (empty: the scene gets no module), so that the first render after a switch
+    // can ask again for the other mode (jit_for_sampling)
+    int32_t sampling = RVCP_SAMPLING_UNIFORM;
+    int32_t jit_sampling = RVCP_SAMPLING_UNIFORM;
+    std::vector<TriRecord> jit_tri;
+    bool jit_bvh = false;
     float light_total = 0.0f, light_pdf = 0.0f;
     bool has_scene = false;
 
@@ -691,6 +702,10 @@ static int impl_create(const rvcp_config_t *cfg, rvcp_ctx_t **out_ctx)
         if (rvcp_games101_occupancy(v, &per_cu) != 0 || per_cu <= 0) per_cu = 1;
         if (cap > 0 && cap < per_cu) per_cu = cap;
         ctx->grid_capacity[v] = per_cu * cus;
+        per_cu = 0;
+        if (rvcp_games101_occupancy_cosine(v, &per_cu) != 0 || per_cu <= 0) per_cu = 1;
+        if (cap > 0 && cap < per_cu) per_cu = cap;
+        ctx->grid_capacity_cos[v] = per_cu * cus;
     }
     {
         int per_cu = 0;
@@ -701,6 +716,10 @@ static int impl_create(const rvcp_config_t *cfg, rvcp_ctx_t **out_ctx)
         if (rvcp_games101_occupancy(kOccupancyBvh, &per_cu) != 0 || per_cu <= 0) per_cu = 1;
         if (cap > 0 && cap < per_cu) per_cu = cap;
         ctx->bvh_capacity = per_cu * cus;
+        per_cu = 0;
+        if (rvcp_games101_occupancy_cosine(kOccupancyBvh, &per_cu) != 0 || per_cu <= 0) per_cu = 1;
+        if (cap > 0 && cap < per_cu) per_cu = cap;
+        ctx->bvh_capacity_cos = per_cu * cus;
     }
     if (cfg->n_gpus > 1) {   // one sub-context per further GPU (shards 1..N-1)
         for (int i = 1; i < cfg->n_gpus; i++) {
@@ -928,7 +947,7 @@ static int upload_one(rvcp_ctx_t *ctx, const rvcp_material_t *materials, uint32_
             if (K) {
                 std::string jerr;
                 bvh_jit = jit_path_kernels(ctx->device, tri.data(), K, jerr, false, n_spheres == 0,
-                                           false, true);
+                                           false, true, nullptr, 0, 64, ctx->sampling);
                 HIP_TRY(ctx, hipSetDevice(ctx->device));
                 if (!bvh_jit || !bvh_jit->bvh_path || !bvh_jit->bvh_primary) {
                     K = 0;
@@ -978,15 +997,23 @@ static int upload_one(rvcp_ctx_t *ctx, const rvcp_material_t *materials, uint32_
     // scene-specialised scan: compiled here, once per scene and process
     ctx->jit.reset();
     ctx->jit_err.clear();
-    if (bvh_jit) ctx->jit = bvh_jit;          // the BVH hybrid's module (above)
+    ctx->jit_tri.clear();
+    ctx->jit_bvh = false;
+    ctx->jit_sampling = ctx->sampling;
+    if (bvh_jit) {                            // the BVH hybrid's module (above)
+        ctx->jit = bvh_jit;
+        ctx->jit_tri.assign(tri.begin(), tri.begin() + ctx->bvh_prefix);
+        ctx->jit_bvh = true;
+    }
     if (ctx->cfg.specialize == RVCP_SPECIALIZE_AUTO && ctx->cfg.accel == RVCP_ACCEL_NONE &&
         n_faces >= 1 && n_faces <= kJitMaxFaces && jit_scene_in_range(tri.data(), n_faces) &&
         !RVCP_KNOB("RVCP_NO_SPECIALIZE")) {
-        ctx->jit = jit_path_kernels(ctx->device, tri.data(), n_faces, ctx->jit_err,
-                                    ctx->cfg.integrator == RVCP_INTEGRATOR_LEGACY,
+        const bool legacy = ctx->cfg.integrator == RVCP_INTEGRATOR_LEGACY;
+        ctx->jit = jit_path_kernels(ctx->device, tri.data(), n_faces, ctx->jit_err, legacy,
                                     n_spheres == 0, n_spheres <= 64 && n_materials <= 64, false,
-                                    spheres, n_spheres, n_materials);
+                                    spheres, n_spheres, n_materials, ctx->sampling);
         HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (!legacy) ctx->jit_tri = tri;      // (mode 2 has one sampling: nothing to ask again)
     }
     ctx->rcp_fast = scan_rcp_fast_scene(tri.data(), n_faces);
     ctx->n_faces = n_faces;
@@ -1028,6 +1055,24 @@ uint32_t rvcp_shard_rows(uint32_t height, uint32_t shard_index, uint32_t shard_c
     for (uint32_t s = shard_index; s < stripes; s += shard_count)
         rows += (s + 1) * 8 <= height ? 8 : height - s * 8;
     return rows;
+}
+
+// The scene's specialised module for the context's bounce sampling, asked for again with what
+// upload asked (jit_tri, jit_bvh) by the first render after rvcp_set_sampling changed the mode:
+// from the process's module cache, the disk cache, or hipRTC.  Without one (no module for this
+// scene, or the compilation failed) the generic kernels of the mode run; a module of the other
+// mode is never kept.
+static void jit_for_sampling(rvcp_ctx_t *ctx)
+{
+    ctx->jit_sampling = ctx->sampling;
+    if (ctx->jit_tri.empty()) return;
+    ctx->jit.reset();
+    ctx->jit_err.clear();
+    ctx->jit = jit_path_kernels(ctx->device, ctx->jit_tri.data(), (uint32_t)ctx->jit_tri.size(),
+                                ctx->jit_err, false, false, false, ctx->jit_bvh, nullptr, 0, 64,
+                                ctx->sampling);
+    (void)hipSetDevice(ctx->device);
+    if (ctx->jit_bvh && ctx->jit && (!ctx->jit->bvh_path || !ctx->jit->bvh_primary)) ctx->jit.reset();
 }
 
 // n_frames consecutive frames of one shard (pushes[k] for frame k) into outputs laid out frame
@@ -1091,6 +1136,11 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
         A.brdf_rcp[1] = 1.0f / A.brdf_den[1];
         A.brdf_rcp[0] = 1.0f / A.brdf_den[0];
     }
+    // the cosine-weighted bounce (rvcp_set_sampling): its kernels, its factor
+    // k = PI_F / rr, and a specialised module compiled for it
+    const bool cosine = ctx->sampling == RVCP_SAMPLING_COSINE;
+    A.cos_k = 3.1415926f / A.rr;
+    if (ctx->jit_sampling != ctx->sampling) jit_for_sampling(ctx);
     A.want_linear = d_linear_rgb ? 1u : 0u;
     // automatic schedule: 10 / 5 (LDS tiles; the workgroup's rays pooled into full passes on
     // large frames, one ray per lane on small ones) for large meshes, 10 also for mid-size
@@ -1190,8 +1240,9 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
             const bool spec_bvh = !legacy && A.accel && A.bvh_prefix > 0 && jk && jk->bvh_path &&
                                   jk->bvh_primary && jk->blocks_per_cu_bvh > 0 && A.t_min > 0.0f;
             uint32_t cap = (uint32_t)(legacy ? ctx->legacy_capacity
-                                     : A.accel ? ctx->bvh_capacity
-                                               : ctx->grid_capacity[A.variant]);
+                                     : A.accel ? (cosine ? ctx->bvh_capacity_cos : ctx->bvh_capacity)
+                                     : cosine ? ctx->grid_capacity_cos[A.variant]
+                                              : ctx->grid_capacity[A.variant]);
             if (spec) cap = (uint32_t)jit_per_cu * (ctx->n_simds / 4u);
             if (spec_bvh) cap = (uint32_t)jk->blocks_per_cu_bvh * (ctx->n_simds / 4u);
             if (spec_legacy) cap = (uint32_t)jk->blocks_per_cu_legacy * (ctx->n_simds / 4u);
@@ -1274,7 +1325,8 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
                         camera_constants(pushes[k], width, height, FA[k]);
                         FA[k].pix_base = k * stride;
                     }
-                    rc = rvcp_launch_games101_v3(FA.data(), n_frames, stride, ctx->d_tri,
+                    rc = (cosine ? rvcp_launch_games101_v3_cosine : rvcp_launch_games101_v3)(
+                                                 FA.data(), n_frames, stride, ctx->d_tri,
                                                  ctx->d_faces, ctx->d_verts,
                                                  ctx->d_mats, ctx->d_lights, ctx->d_gamma,
                                                  (uint32_t *)d_rgba8, lin,
@@ -1291,9 +1343,10 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
                 if (spec || spec_bvh) ctx->last_spec = true;
             } else {
                 HIP_TRY(ctx, hipEventRecord(ctx->evm, s));
-                rc = rvcp_launch_games101(&A, ctx->d_tri, ctx->d_faces, ctx->d_verts, ctx->d_mats,
-                                          ctx->d_lights, ctx->d_gamma, (uint32_t *)d_rgba8,
-                                          (float *)d_linear_rgb, ctx->d_counters, blocks, s);
+                rc = (cosine ? rvcp_launch_games101_cosine : rvcp_launch_games101)(
+                    &A, ctx->d_tri, ctx->d_faces, ctx->d_verts, ctx->d_mats, ctx->d_lights,
+                    ctx->d_gamma, (uint32_t *)d_rgba8, (float *)d_linear_rgb, ctx->d_counters,
+                    blocks, s);
             }
         }
         if (rc != 0) return fail(ctx, RVCP_E_HIP, std::string("kernel launch failed: ") +
@@ -2052,6 +2105,39 @@ static int impl_get_taa(rvcp_ctx_t *ctx, int *on)
     if (!ctx) return RVCP_E_INVALID;
     if (!on) return fail(ctx, RVCP_E_INVALID, "invalid get_taa arguments");
     *on = ctx->taa ? 1 : 0;
+    return RVCP_OK;
+}
+
+// ---- bounce sampling: the switch -------------------------------------------
+
+static int impl_set_sampling(rvcp_ctx_t *ctx, int32_t sampling)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (sampling != RVCP_SAMPLING_UNIFORM && sampling != RVCP_SAMPLING_COSINE)
+        return fail(ctx, RVCP_E_INVALID, "unknown sampling");
+    if (sampling == RVCP_SAMPLING_COSINE && ctx->cfg.integrator == RVCP_INTEGRATOR_LEGACY)
+        return fail(ctx, RVCP_E_UNSUPPORTED, "RVCP_SAMPLING_COSINE is for the games101 integrator "
+                    "(mode 2's diffuse scatter is cosine-weighted already)");
+    if (ctx->pending)
+        return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    for (rvcp_ctx *sub : ctx->subs)
+        if (sub->pending)
+            return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    if (sampling == ctx->sampling) return RVCP_OK;
+    ctx->sampling = sampling;
+    for (rvcp_ctx *sub : ctx->subs) sub->sampling = sampling;
+    // histories of frames with another expectation and another noise do not mix
+    ctx->tp_hist.valid = ctx->sv_hist.valid = false;
+    ctx->taa_tp.hist.valid = ctx->taa_sv.hist.valid = false;
+    ctx->taau_tp.hist.valid = ctx->taau_sv.hist.valid = false;
+    return RVCP_OK;
+}
+
+static int impl_get_sampling(rvcp_ctx_t *ctx, int32_t *sampling)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!sampling) return fail(ctx, RVCP_E_INVALID, "invalid get_sampling arguments");
+    *sampling = ctx->sampling;
     return RVCP_OK;
 }
 
@@ -3565,6 +3651,16 @@ int rvcp_set_taa_upsample(rvcp_ctx_t *ctx, uint32_t scale)
 int rvcp_get_taa_upsample(rvcp_ctx_t *ctx, uint32_t *scale)
 {
     return barrier(ctx, [&] { return impl_get_taa_upsample(ctx, scale); });
+}
+
+int rvcp_set_sampling(rvcp_ctx_t *ctx, int32_t sampling)
+{
+    return barrier(ctx, [&] { return impl_set_sampling(ctx, sampling); });
+}
+
+int rvcp_get_sampling(rvcp_ctx_t *ctx, int32_t *sampling)
+{
+    return barrier(ctx, [&] { return impl_get_sampling(ctx, sampling); });
 }
 
 }  // extern "C"

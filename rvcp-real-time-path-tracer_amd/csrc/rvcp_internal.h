@@ -288,12 +288,17 @@ struct FrameArgs {
     // t_near, t_far, time) and whose outputs start frame_stride pixels after the previous
     // frame's; batch_cams == nullptr for a single frame
     uint32_t frame_pixels, frame_stride;
+    // cosine-weighted bounce sampling (RVCP_SAMPLING_COSINE): the attenuation
+    // update's factor PI_F / rr, one IEEE division on the host; read by the cosine builds of the
+    // kernels only.  It fills the padding in front of the pointer: no other member moves.
+    float cos_k;
     const float *batch_cams;
     // debug build of the library only: per-wave {start, queue exhausted, end, iterations,
     // shader-clock start, shader-clock end}
     // of the path kernel, s_memrealtime ticks (100 MHz); nullptr otherwise
     unsigned long long *timeline;
 };
+static_assert(sizeof(FrameArgs) == 256, "FrameArgs is 256 B (cos_k sits in former padding)");
 
 #ifndef __HIPCC_RTC__
 // rvcp_bvh.cpp: build the BVH over n faces (three vertex positions each); returns the depth.
@@ -336,6 +341,24 @@ int rvcp_launch_games101_v3(const rvcp::FrameArgs *args, uint32_t n_frames, uint
                             const rvcp::Bvh4Node *bvh_nodes, const rvcp::TriRecord *bvh_tris,
                             uint32_t grid_blocks, void *stream, void *main_event,
                             void *spec_path_fn, const float *cams, void *spec_pre_fn = nullptr);
+// The same three for RVCP_SAMPLING_COSINE (rvcp_kernels_cosine.hip: the games101 kernels built
+// with the cosine-weighted bounce); a specialised module passed to the second
+// must have been compiled for that mode too (jit_path_kernels' `sampling`).
+int rvcp_launch_games101_cosine(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
+                                const void *faces, const void *verts, const rvcp::MatRecord *mats,
+                                const rvcp::LightRecord *lights, const float *gamma_t,
+                                uint32_t *out_rgba, float *out_lin, unsigned long long *counters,
+                                uint32_t grid_blocks, void *stream);
+int rvcp_launch_games101_v3_cosine(const rvcp::FrameArgs *args, uint32_t n_frames,
+                                   uint32_t frame_stride, const rvcp::TriRecord *tri,
+                                   const void *faces, const void *verts, const rvcp::MatRecord *mats,
+                                   const rvcp::LightRecord *lights, const float *gamma_t,
+                                   uint32_t *out_rgba, float *out_lin, unsigned long long *counters,
+                                   rvcp::SurfRecord *surf, const rvcp::FaceShade *shade,
+                                   const rvcp::Bvh4Node *bvh_nodes, const rvcp::TriRecord *bvh_tris,
+                                   uint32_t grid_blocks, void *stream, void *main_event,
+                                   void *spec_path_fn, const float *cams, void *spec_pre_fn);
+int rvcp_games101_occupancy_cosine(int variant, int *blocks_per_cu);
 // Integrator RVCP_INTEGRATOR_LEGACY (ray_tracer.comp): materials / spheres are the raw
 // rvcp_material_t / rvcp_sphere_t arrays, unorm_t the UNORM8 threshold table.
 int rvcp_launch_legacy(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,

@@ -779,7 +779,16 @@ unsigned jit_scan_opts()
     return opts;
 }
 
-std::vector<std::string> jit_options(bool legacy, int legacy_waves, bool lds_scene, bool bvh);
+std::vector<std::string> jit_options(bool legacy, int legacy_waves, bool lds_scene, bool bvh,
+                                     int sampling = 0);
+
+// The line a module's source ends with for a bounce sampling other than the default: the
+// process-wide module cache is keyed by the source text, so the two modes' modules differ in it.
+std::string jit_sampling_tag(int sampling)
+{
+    return sampling == RVCP_SAMPLING_UNIFORM ? std::string()
+                                             : "// +sampling " + std::to_string(sampling) + "\n";
+}
 
 namespace {
 
@@ -930,13 +939,13 @@ void disk_write(const std::string &dir, const std::string &key, const std::vecto
 // With g_mu held.
 int jit_cached_code(const std::string &scan, std::vector<char> &code, std::string &err,
                     bool legacy, int legacy_waves, bool lds_scene, bool bvh, bool *from_disk,
-                    bool force_compile)
+                    bool force_compile, int sampling)
 {
     *from_disk = false;
     const std::string dir = cache_dir();
     std::string key;
     if (!dir.empty()) {
-        key = code_key(scan, jit_options(legacy, legacy_waves, lds_scene, bvh));
+        key = code_key(scan, jit_options(legacy, legacy_waves, lds_scene, bvh, sampling));
         if (force_compile) {
             g_disk_rejects++;
         } else {
@@ -949,7 +958,7 @@ int jit_cached_code(const std::string &scan, std::vector<char> &code, std::strin
             if (r < 0) g_disk_rejects++;
         }
     }
-    if (jit_compile_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh) != 0) return -1;
+    if (jit_compile_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, sampling) != 0) return -1;
     g_disk_compiles++;
     if (!dir.empty()) disk_write(dir, key, code);
     return 0;
@@ -968,7 +977,8 @@ JitKernels::~JitKernels()
 
 // The hipRTC options of a module: the flags of the static build (Makefile), on which the
 // numeric contract depends, and the module's variant defines.
-std::vector<std::string> jit_options(bool legacy, int legacy_waves, bool lds_scene, bool bvh)
+std::vector<std::string> jit_options(bool legacy, int legacy_waves, bool lds_scene, bool bvh,
+                                     int sampling)
 {
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17",
                                      "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
@@ -976,6 +986,9 @@ std::vector<std::string> jit_options(bool legacy, int legacy_waves, bool lds_sce
                                      "-DRVCP_SPEC_SCAN=\"rvcp_spec_scan.inc\""};
     if (legacy) opts.push_back("-DRVCP_JIT_LEGACY");
     if (bvh) opts.push_back("-DRVCP_JIT_BVH");
+    // the games101 kernels' bounce (rvcp_set_sampling): the default modules get no define, so
+    // their options and keys are the ones they always had
+    if (sampling != RVCP_SAMPLING_UNIFORM) opts.push_back("-DRVCP_SAMPLING=" + std::to_string(sampling));
 #ifdef RVCP_TIMELINE
     opts.push_back("-DRVCP_TIMELINE");      // the debug library's modules keep the per-wave timeline
 #endif
@@ -986,7 +999,7 @@ std::vector<std::string> jit_options(bool legacy, int legacy_waves, bool lds_sce
 }
 
 int jit_compile_code(const std::string &scan, std::vector<char> &code, std::string &err,
-                     bool legacy, int legacy_waves, bool lds_scene, bool bvh)
+                     bool legacy, int legacy_waves, bool lds_scene, bool bvh, int sampling)
 {
     const RtcApi &api = rtc();
     if (!api.ok) {
@@ -1001,7 +1014,7 @@ int jit_compile_code(const std::string &scan, std::vector<char> &code, std::stri
         err = "hiprtcCreateProgram failed";
         return -1;
     }
-    const std::vector<std::string> opt_s = jit_options(legacy, legacy_waves, lds_scene, bvh);
+    const std::vector<std::string> opt_s = jit_options(legacy, legacy_waves, lds_scene, bvh, sampling);
     std::vector<const char *> opts;
     for (const std::string &x : opt_s) opts.push_back(x.c_str());
     const int rc = api.compile(prog, (int)opts.size(), opts.data());
@@ -1025,7 +1038,7 @@ int jit_compile_code(const std::string &scan, std::vector<char> &code, std::stri
 std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, uint32_t n,
                                              std::string &err, bool legacy, bool sphereless,
                                              bool lds_fits, bool bvh, const rvcp_sphere_t *spheres,
-                                             uint32_t n_spheres, uint32_t n_materials)
+                                             uint32_t n_spheres, uint32_t n_materials, int sampling)
 {
     // Mode 2 on a scene without spheres (the Cornell frame): 6 waves per SIMD measured 2.5 %
     // faster than 5, with spheres 5 % slower (profiles/history/r02_legacy_waves_ab.log).  With the
@@ -1051,7 +1064,8 @@ std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, u
                       + (lds_scene ? jit_legacy_lds_source(n, n_spheres, n_materials) : std::string())
                 : std::string()) +
         (key_flags.empty() ? std::string() : "// +flags" + key_flags + "\n") +
-        (bvh ? "// +bvh\n" : "");
+        (bvh ? "// +bvh\n" : "") +
+        jit_sampling_tag(sampling);
     const uint64_t h = fnv1a(scan);
     std::lock_guard<std::mutex> lock(g_mu);
     for (auto it = g_cache.begin(); it != g_cache.end(); ++it) {
@@ -1084,9 +1098,9 @@ std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, u
     };
     std::vector<char> code;
     bool from_disk = false;
-    if (jit_cached_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, &from_disk, false) != 0)
+    if (jit_cached_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, &from_disk, false, sampling) != 0)
         return nullptr;
-    const uint64_t key_hash = fnv1a(code_key(scan, jit_options(legacy, legacy_waves, lds_scene, bvh)));
+    const uint64_t key_hash = fnv1a(code_key(scan, jit_options(legacy, legacy_waves, lds_scene, bvh, sampling)));
     auto k = std::make_shared<JitKernels>();
     k->device = device;
     k->key_hash = key_hash;
@@ -1097,7 +1111,7 @@ std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, u
         k = std::make_shared<JitKernels>();
         k->device = device;
         k->key_hash = key_hash;
-        if (jit_cached_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, &from_disk, true) != 0)
+        if (jit_cached_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, &from_disk, true, sampling) != 0)
             return nullptr;
         why = load(*k, code);
     }
@@ -1221,6 +1235,63 @@ extern "C" size_t rvcp_internal_jit_scan_source(const void *tri_records, uint32_
                                                 size_t cap)
 {
     return rvcp_internal_jit_scan_source_opt(tri_records, n, 0, out, cap);
+}
+
+// Self-test hooks for the bounce sampling (rvcp_set_sampling), none needing a
+// GPU: the source text a games101 module of n triangle records is cached under in the process
+// (the scan plus jit_sampling_tag), ...
+extern "C" size_t rvcp_internal_jit_module_source(const void *tri_records, uint32_t n,
+                                                  int sampling, char *out, size_t cap)
+{
+    try {
+        const std::string s =
+            rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n) +
+            rvcp::jit_sampling_tag(sampling);
+        if (out && cap) {
+            std::strncpy(out, s.c_str(), cap - 1);
+            out[cap - 1] = '\0';
+        }
+        return s.size();
+    } catch (...) {
+        return 0;
+    }
+}
+
+// ... the hash of its whole compile input (JitKernels::key_hash, the disk-cache key), ...
+extern "C" uint64_t rvcp_internal_jit_module_key_for(const void *tri_records, uint32_t n,
+                                                     int sampling)
+{
+    try {
+        const std::string scan =
+            rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n) +
+            rvcp::jit_sampling_tag(sampling);
+        return rvcp::fnv1a(rvcp::code_key(scan, rvcp::jit_options(false, 0, false, false, sampling)));
+    } catch (...) {
+        return 0;
+    }
+}
+
+// ... and its compilation (as rvcp_internal_jit_compile_check).
+extern "C" int rvcp_internal_jit_compile_check_sampling(const void *tri_records, uint32_t n,
+                                                         int sampling, size_t *code_bytes,
+                                                         char *err, size_t err_cap)
+{
+    try {
+        std::string e;
+        std::vector<char> code;
+        const std::string scan =
+            rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n) +
+            rvcp::jit_sampling_tag(sampling);
+        const int rc = rvcp::jit_compile_code(scan, code, e, false, 0, false, false, sampling);
+        if (code_bytes) *code_bytes = code.size();
+        if (err && err_cap) {
+            std::strncpy(err, e.c_str(), err_cap - 1);
+            err[err_cap - 1] = '\0';
+        }
+        return rc;
+    } catch (...) {
+        return -1;
+    }
 }
 
 // ---- the on-disk code-object cache's C-ABI (rvcp.h) ----

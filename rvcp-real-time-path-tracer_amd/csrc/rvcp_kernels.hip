@@ -28,6 +28,29 @@
 #include <hip/hip_runtime.h>
 #endif
 
+// RVCP_SAMPLING (rvcp.h RVCP_SAMPLING_*): the bounce the continuation half of a surface event
+// draws, chosen when this file is compiled -- 0, the default: the shader's
+// uniform hemisphere; 1: the cosine-weighted bounce (brdf_continue, brdf_finish).  The cosine
+// build is a translation unit of its own (rvcp_kernels_cosine.hip: this file with
+// RVCP_SAMPLING = 1) holding only the games101 kernels and their launchers under the names
+// below, so the default object is compiled from the text it always was; the scene-specialised
+// modules get the define from rvcp_jit.cpp.
+#ifndef RVCP_SAMPLING
+#define RVCP_SAMPLING 0
+#endif
+#if RVCP_SAMPLING && !defined(RVCP_JIT)
+#define games101_kernel games101_cosine_kernel
+#define games101_dual_kernel games101_cosine_dual_kernel
+#define games101_path_kernel games101_cosine_path_kernel
+#define games101_bvh_path_kernel games101_cosine_bvh_path_kernel
+#define games101_tiled_kernel games101_cosine_tiled_kernel
+#define games101_tiled_pool_kernel games101_cosine_tiled_pool_kernel
+#define games101_tiled_single_kernel games101_cosine_tiled_single_kernel
+#define rvcp_launch_games101 rvcp_launch_games101_cosine
+#define rvcp_launch_games101_v3 rvcp_launch_games101_v3_cosine
+#define rvcp_games101_occupancy rvcp_games101_occupancy_cosine
+#endif
+
 #include "rvcp_internal.h"
 #include "../../include/rvcp.h"
 #include "rvcp_sqrt.h"
@@ -980,6 +1003,23 @@ __device__ __forceinline__ bool nee_sample(const FrameArgs &A, const LightRecord
     return true;
 }
 
+#if RVCP_SAMPLING
+// The cosine-weighted bounce (RVCP_SAMPLING_COSINE) from the accepted unit-ball
+// sample p: the direction n + normalize(p), normalised (a point of the unit sphere tangent to the
+// surface, whose direction from the hit has density cos / pi), or n where the two cancel; the
+// path weight f cos / (pdf rr) is then albedo / rr whatever the direction, written f * k with
+// f = albedo / PI_F (the hit's alb_pi) and k = PI_F / rr (FrameArgs::cos_k).  No cosine test, no
+// max(0.1, pdf) clamp, no division: none of §4.2's arguments about the divisor is needed.
+__device__ __forceinline__ void cosine_bounce(const FrameArgs &A, f3 alb_pi, f3 S_nrm, f3 p,
+                                              f3 &att, f3 &wi) {
+    const f3 h = add(S_nrm, normalize(p));
+    const float hh = dot(h, h);
+    const f3 hn = normalize(h);
+    wi = hh < 1e-12f ? S_nrm : hn;
+    att = mulv(att, muls(alb_pi, A.cos_k));
+}
+#endif
+
 // Continuation half of a surface event (:461-471): Russian roulette, the uniform hemisphere
 // direction and the attenuation update.  Returns false when the path ends at RR.
 __device__ __forceinline__ bool brdf_continue(const FrameArgs &A, const MatRecord &m, f3 S_nrm,
@@ -992,6 +1032,9 @@ __device__ __forceinline__ bool brdf_continue(const FrameArgs &A, const MatRecor
         const float rz = rnd(seed, ridx);
         p = mk(cube_coord(rx), cube_coord(ry), cube_coord(rz));
     } while (dot(p, p) >= 1.0f);
+#if RVCP_SAMPLING
+    cosine_bounce(A, ld3(m.alb_pi), S_nrm, p, att, wi);
+#else
     const f3 h = dot(p, S_nrm) > 0.0f ? p : neg(p);                                // :207-210
     wi = normalize(h);                                                             // :212-214
     const float cosw = dot(S_nrm, wi);
@@ -999,6 +1042,7 @@ __device__ __forceinline__ bool brdf_continue(const FrameArgs &A, const MatRecor
     const float pdf = dot(wi, S_nrm) > 0.0f ? 0.5f / 3.1415926f : 0.0f;            // :358-365
     const float denom = __builtin_fmaxf(0.1f, pdf) * A.rr;
     att = mulv(att, divs_pos(muls(f, cosw), denom));                                   // :465-471
+#endif
     return true;
 }
 
@@ -1009,6 +1053,9 @@ __device__ __forceinline__ bool brdf_continue(const FrameArgs &A, const MatRecor
 // reciprocals the host computed: divs_y with them is divs_pos).
 __device__ __forceinline__ void brdf_finish(const FrameArgs &A, f3 alb_pi, f3 S_nrm, f3 p,
                                             f3 &att, f3 &wi) {
+#if RVCP_SAMPLING
+    cosine_bounce(A, alb_pi, S_nrm, p, att, wi);
+#else
     const f3 h = dot(p, S_nrm) > 0.0f ? p : neg(p);
     wi = normalize(h);
     const float cosw = dot(S_nrm, wi);
@@ -1016,6 +1063,7 @@ __device__ __forceinline__ void brdf_finish(const FrameArgs &A, f3 alb_pi, f3 S_
     const f3 f = pos ? alb_pi : mk(0, 0, 0);
     att = mulv(att, divs_y(muls(f, cosw), pos ? A.brdf_den[1] : A.brdf_den[0],
                            pos ? A.brdf_rcp[1] : A.brdf_rcp[0]));
+#endif
 }
 
 // random_in_unit_sphere (:195-201) for every lane with `need`, cooperatively: each round the
@@ -2719,6 +2767,7 @@ __global__ __launch_bounds__(kBlock, kTiledMinWaves) void games101_tiled_single_
                            shade, tail_tab, tile);
 }
 
+#if !RVCP_SAMPLING  // (the cosine build holds the games101 kernels only)
 // Frame assembly after the RCCL gather: slot k holds shard k's stripes packed.
 __global__ void assemble_kernel(const uint32_t *__restrict__ gathered, uint32_t slot_rows,
                                 uint32_t width, uint32_t height, uint32_t shard_count,
@@ -2757,9 +2806,10 @@ __global__ void fill_kernel(uint32_t *__restrict__ out_rgba, float *__restrict__
         if (out_lin) { out_lin[3 * i] = 0.0f; out_lin[3 * i + 1] = 0.0f; out_lin[3 * i + 2] = 0.0f; }
     }
 }
+#endif  // !RVCP_SAMPLING
 
 #endif  // RVCP_JIT
-#if !defined(RVCP_JIT) || defined(RVCP_JIT_LEGACY)
+#if (!defined(RVCP_JIT) && !RVCP_SAMPLING) || defined(RVCP_JIT_LEGACY)
 // ======================================================================================
 // Integrator RVCP_INTEGRATOR_LEGACY: ray_trace of assets/shaders/ray_tracer.comp
 // (:618-694, main :802-822) -- spheres then triangles, Lambertian / metal / dielectric
@@ -3535,13 +3585,18 @@ extern "C" int rvcp_launch_games101_v3(const rvcp::FrameArgs *args, uint32_t n_f
     // the frame's UNORM8 store from the linear colours (out_lin is never null here); a batch's
     // frames lie frame_stride pixels apart (the rows of a smaller shard's slot are padding)
     const uint32_t n_tone = n_frames > 1 ? n_frames * frame_stride : args->n_pixels;
+#if RVCP_SAMPLING
+    return rvcp_launch_tonemap(out_lin, n_tone, gamma_t, out_rgba, stream);   // the default object's
+#else
     uint32_t tb = (n_tone + rvcp::kToneBlock - 1) / rvcp::kToneBlock;
     if (tb > 8192u) tb = 8192u;
     hipLaunchKernelGGL(rvcp::tonemap_kernel, dim3(tb), dim3(rvcp::kToneBlock), 0, (hipStream_t)stream,
                        out_lin, n_tone, gamma_t, out_rgba);
     return hipGetLastError() == hipSuccess ? 0 : -2;
+#endif
 }
 
+#if !RVCP_SAMPLING
 extern "C" int rvcp_launch_gbuffer(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
                                    const rvcp::FaceShade *shade, const rvcp::Bvh4Node *bvh_nodes,
                                    const rvcp::TriRecord *bvh_tris, void *out, void *stream)
@@ -3589,6 +3644,7 @@ extern "C" int rvcp_launch_fill(uint32_t *out_rgba, float *out_lin, uint32_t n, 
                        out_rgba, out_lin, n, rgba);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
+#endif  // !RVCP_SAMPLING
 
 extern "C" int rvcp_games101_occupancy(int variant, int *blocks_per_cu)
 {
@@ -3613,6 +3669,7 @@ extern "C" int rvcp_games101_occupancy(int variant, int *blocks_per_cu)
     return 0;
 }
 
+#if !RVCP_SAMPLING
 extern "C" int rvcp_launch_legacy(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
                                   const rvcp::FaceShade *shade, const void *spheres,
                                   const void *materials, const float *unorm_t, uint32_t *out_rgba,
@@ -3653,4 +3710,5 @@ extern "C" int rvcp_legacy_occupancy(int *blocks_per_cu)
     *blocks_per_cu = b;
     return 0;
 }
+#endif  // !RVCP_SAMPLING
 #endif  // RVCP_JIT

@@ -158,7 +158,7 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
                  dump_dir: Optional[str] = None, dump_format: str = "ppm",
                  on_fps: Optional[Callable[[int], None]] = None, denoise=None,
                  temporal=None, svgf=None, demodulate: Optional[bool] = None,
-                 taa: Optional[bool] = None) -> dict:
+                 taa: Optional[bool] = None, sampling: Optional[int] = None) -> dict:
     """``main_loop`` (ray_tracer.rs:22-100) without a window.
 
     Per frame: apply this frame's scripted events, count FPS (printed once a second as
@@ -180,11 +180,16 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
     ``taa``: True / False sets ``tracer.taa`` before the loop, so that the ``temporal`` / ``svgf``
     chains render through a jittered camera and return the anti-aliased resolve (DESIGN.md
     §4.13); None (default) leaves the tracer's switch as it is.
+    ``sampling``: abi.SAMPLING_UNIFORM / abi.SAMPLING_COSINE sets ``tracer.sampling`` before the
+    loop, so that every frame, through whichever chain, is traced with that bounce (DESIGN.md
+    §4.17); None (default) leaves the tracer's mode as it is.
     Returns per-frame render times and the final camera."""
     if demodulate is not None:
         tracer.demodulation = bool(demodulate)
     if taa is not None:
         tracer.taa = bool(taa)
+    if sampling is not None:
+        tracer.sampling = int(sampling)
     info = RuntimeInfo(window_size=(width, height))
     by_frame: Dict[int, List[Event]] = {}
     for ev in events:

@@ -491,6 +491,23 @@ class RayTracer:
     def taa_upsample(self, scale: int):
         self._check(self._lib.rvcp_set_taa_upsample(self._ctx, int(scale)))
 
+    # bounce sampling of the games101 integrator
+    @property
+    def sampling(self) -> int:
+        """The context's bounce sampling (rvcp_get_sampling / rvcp_set_sampling):
+        abi.SAMPLING_UNIFORM (the default: the shader's bounce, frames bit-identical to the
+        oracle) or abi.SAMPLING_COSINE (cosine-weighted directions with the constant weight
+        albedo / rr: less noise per sample, frames no longer the oracle's).  It holds from the
+        next render on, across upload_scene; changing it drops the temporal chains' histories."""
+        mode = ctypes.c_int32(0)
+        self._check(self._lib.rvcp_get_sampling(self._ctx, ctypes.cast(ctypes.byref(mode),
+                                                                      ctypes.c_void_p)))
+        return int(mode.value)
+
+    @sampling.setter
+    def sampling(self, mode: int):
+        self._check(self._lib.rvcp_set_sampling(self._ctx, int(mode)))
+
     def _traced_size(self, width, height):
         """(rows, columns) of the frame render_temporal / render_svgf trace for a width x height
         call: the optional outputs other than the frame itself have this size."""
