@@ -3,7 +3,8 @@ by frame, bit-identical to rendering each frame alone -- with a different time s
 (the reference's per-frame `time`, vulkan.rs:418-421), for whole frames and for shards whose
 rows differ (the padded slot layout), on the schedules that share one surface list; the stats
 cover the whole batch; integrator mode 2 batches too (per-frame cameras); the schedules
-without a pre-pass refuse a batch."""
+without a pre-pass refuse a batch.  Per-frame cameras on every route, against the oracle:
+tests/test_gpu_batch_matrix.py."""
 import numpy as np
 import pytest
 

@@ -1,0 +1,425 @@
+"""rvcp_render_frames_async against the CPU oracle: every route, per-frame cameras, both forms
+of the pre-pass, frames smaller than a wave, padded and empty shards.
+
+include/rvcp.h promises that frame k of a batch is rendered with pushes[k] -- its camera and
+its time seed -- and equals rvcp_render_shard_async with that push.  tests/test_gpu_batch.py
+checks the times; here every frame of every batch has a camera of its own (tests/batch_cases.py;
+tests/test_batch_cases_cpu.py holds the conditions on them) and is compared with the oracle's
+frame of the same push, with the project's own tolerance:
+
+    linear RGB bits equal, RGBA8 bytes equal, `traversals` equal to the sum of the oracle's;
+    samples == frames x rows x W x spp; the kernel_variant that ran is the route asked for.
+
+Every call's outputs end in a guard tail of 4096 sentinel words after the batch's n_frames x
+slot pixels, in the RGBA buffer and in the linear buffer, which must come back untouched.
+
+Routes (kernel_variant; +16 = VARIANT_SPECIALIZED):
+    r3g / r3s  schedule 3, generic (3) / the scene's module (19)      r4, r5, r10  tiled (4, 5, 10)
+    r6g / r6s  schedule 6, generic (6) / the scene's module (22)      bvh          BVH kernels (7)
+    hybrid     BVH with the specialised prefix scan (23)              m2g / m2s    mode 2 (8 / 24)
+    auto       the host's own choice, on these frames 19
+
+Groups: A per-frame cameras (47 x 39, five cameras; sky-only batches; a refused batch);
+B frames of 63 pixels and of one pixel, 70 of them; C padded and empty shards; D both pre-pass
+forms on either side of kPrepassBatchMaxPixels, whole frames and padded shards; E one context
+through growing and shrinking calls; F adversarial scenes; G cosine mode against schedule 1;
+H traversals_executed against single renders.
+
+Scratch-build trials (the library rebuilt with one mutation, only this file run on it; every
+mutation misreads a camera or misplaces a pixel inside the caller's buffers; 76 cases):
+ 1. primary_body reads `cam_load(cams)`, frame 0's record, for every grid row: 52 fail -- every
+    games101 case of A, B, C, E, F (the time is in the record), G and H, the refused-batch
+    cases' following batch, and the one-launch half of D; all of mode 2, the per-frame half of
+    D and the sky-only batches (one camera, and a miss draws no random number) pass.
+ 2. render_frames drops `camera_constants(pushes[k], ..., FA[k])`: the 7 per-frame cases of D
+    fail (whole frames and the padded shard, every route), the other 69 pass.
+ 3. the host packs t_far into c[13] and t_near into c[14]: 63 fail, everything but the
+    sky-only batches and the per-frame half of D (which does not read the table).  A control
+    rather than a finding: frame 0 reads the table too, so tests/test_gpu_batch.py's
+    equal-camera cases fail as well (12 of 13, all but the refusal test).
+ 4. start_batch_pixel passes `pix`, not `pix - f * A.frame_pixels`, to pixel_uv: the 11
+    mode-2 cases fail (A, B, C, E, and the batches that follow the refused and the empty
+    one), every games101 case passes.
+ 5. rvcp_launch_games101_v3 passes 0 for frame_stride to the batched specialised pre-pass
+    (all frames land in slot 0): 27 fail -- r3s, r6s, hybrid and auto in A (sky-only batches
+    included), B, C, E, F, G, H and the one-launch half of D; the generic routes, mode 2 and
+    the per-frame half of D pass.
+ 6. (added, since the sky-only batches of the generic routes r3g, r10 and bvh fail under none
+    of the five) the same zero stride in the generic batched pre-pass: 31 fail -- every
+    generic games101 case of A (those three sky-only batches included), B, C, F, G, H and the
+    one-launch half of D; the specialised routes, mode 2 and the per-frame half of D pass.
+Every group, and every case, fails under at least one of the six.
+"""
+import numpy as np
+import pytest
+
+import batch_cases as B
+import rvcp_amd
+from rvcp_amd import abi
+
+pytestmark = pytest.mark.gpu
+SPEC = abi.VARIANT_SPECIALIZED
+OFF = abi.SPECIALIZE_OFF
+BVH = abi.ACCEL_BVH
+LEGACY = abi.INTEGRATOR_LEGACY
+GUARD = 4096
+SENTINEL = 0x5EA7BEEF                   # a finite float, a positive int32
+
+# route -> (config, schedule reported, specialised)
+ROUTES = {
+    "r3g": (dict(kernel_variant=3, specialize=OFF), 3, False),
+    "r3s": (dict(kernel_variant=3), 3, True),
+    "r6g": (dict(kernel_variant=6, specialize=OFF), 6, False),
+    "r6s": (dict(kernel_variant=6), 6, True),
+    "r4": (dict(kernel_variant=4, specialize=OFF), 4, False),
+    "r5": (dict(kernel_variant=5, specialize=OFF), 5, False),
+    "r10": (dict(kernel_variant=10, specialize=OFF), 10, False),
+    "bvh": (dict(accel=BVH, specialize=OFF), 7, False),
+    "hybrid": (dict(accel=BVH), 7, True),
+    "m2g": (dict(integrator=LEGACY, specialize=1), 8, False),
+    "m2s": (dict(integrator=LEGACY, specialize=0), 8, True),
+    "auto": (dict(), 3, True),
+}
+# the scene of a route where the issue leaves it to the route: the specialised modules need
+# at most 64 faces, the tiled schedules, the BVH and the hybrid more than the box
+SCENE_OF = {"r3g": "cornell", "r3s": "cornell", "r6g": "cornell", "r6s": "cornell", "auto": "cornell",
+            "r4": "c6", "r5": "c6", "r10": "c6", "bvh": "c6", "hybrid": "c6",
+            "m2g": "spheres", "m2s": "spheres"}
+
+
+def _pushes(scene_name):
+    return B.sphere_pushes() if scene_name == "spheres" else B.cornell_pushes()
+
+
+def _cams(scene_name):
+    return B.SPHERE_CAMS if scene_name == "spheres" else B.CORNELL_CAMS
+
+
+def _tracer(route, scene_name, **more):
+    cfg = dict(B.scene_config(scene_name))
+    cfg.update(ROUTES[route][0])
+    cfg.update(more)
+    rt = rvcp_amd.RayTracer(**cfg)
+    rt.upload_scene(B.scene(scene_name))
+    return rt, cfg
+
+
+def _batch(rt, pushes, w, h, k=0, n=1, linear=True):
+    """One rvcp_render_frames_async call into guarded buffers: (rgba words, linear words or
+    None, stats), the words as uint32 with their tails."""
+    import torch
+    px = len(pushes) * rvcp_amd.shard_rows(h, 0, n) * w
+    out = torch.full((px + GUARD,), SENTINEL, dtype=torch.int32, device="cuda")
+    lin = torch.full((3 * px + GUARD,), SENTINEL, dtype=torch.int32, device="cuda") if linear else None
+    torch.cuda.synchronize()
+    rt.render_frames_async(pushes, w, h, k, n, out.data_ptr(), lin.data_ptr() if linear else 0)
+    st = rt.sync_stats().copy()
+    torch.cuda.synchronize()
+    return (out.cpu().numpy().view(np.uint32), lin.cpu().numpy().view(np.uint32) if linear else None, st)
+
+
+def _compare(problems, label, got, orcs, w, h, k, n, spp, variant, spec):
+    """Append to `problems` what the batch `got` = (rgba words, linear words, stats) misses:
+    untouched guard tails, the route, every frame equal to the oracle's, the batch's stats."""
+    out, lin, st = got
+    nf = len(orcs)
+    slot, rows = rvcp_amd.shard_rows(h, 0, n), rvcp_amd.shard_rows(h, k, n)
+    px = nf * slot * w
+    for name, buf, words in (("RGBA", out, px), ("linear", lin, 3 * px)):
+        if buf is not None and not (buf[words:] == SENTINEL).all():
+            bad = np.flatnonzero(buf[words:] != SENTINEL)
+            problems.append(f"{label}: {len(bad)} words of the {name} guard tail written, first at +{int(bad[0])}")
+    kv = int(st["kernel_variant"])
+    want = 0 if rows == 0 else variant | (SPEC if spec else 0)
+    if kv != want:
+        problems.append(f"{label}: kernel_variant {kv}, wanted {want}")
+    rgba = out[:px].view(np.uint8).reshape(nf, slot, w, 4)[:, :rows]
+    lin3 = None if lin is None else lin[:3 * px].reshape(nf, slot, w, 3)[:, :rows]
+    for f, (o_lin, o_rgba, _) in enumerate(orcs):
+        if lin3 is not None:
+            diff = np.any(lin3[f] != o_lin.view(np.uint32), axis=-1)
+            if diff.any():
+                problems.append(f"{label}, frame {f}: {int(diff.sum())} pixels differ in linear RGB, "
+                                f"first at {np.argwhere(diff)[:3].tolist()}")
+        if not np.array_equal(rgba[f], o_rgba):
+            problems.append(f"{label}, frame {f}: {int(np.any(rgba[f] != o_rgba, axis=-1).sum())} "
+                            f"pixels differ in RGBA8")
+    trav = sum(int(o[2]) for o in orcs)
+    if int(st["traversals"]) != trav:
+        problems.append(f"{label}: traversals {int(st['traversals'])}, the oracle's {trav}")
+    if int(st["samples"]) != nf * rows * w * spp:
+        problems.append(f"{label}: samples {int(st['samples'])}, wanted {nf * rows * w * spp}")
+
+
+def _run(problems, label, rt, cfg, route, scene_name, pushes, w, h, k=0, n=1, linear=True):
+    orcs = B.oracle_frames(scene_name, cfg, pushes, w, h, k, n)
+    got = _batch(rt, pushes, w, h, k, n, linear)
+    _compare(problems, label, got, orcs, w, h, k, n, cfg["spp"], ROUTES[route][1], ROUTES[route][2])
+    return got, orcs
+
+
+# ------------------------------------------------------------------- A: per-frame cameras
+A_CASES = [("r3g", "cornell"), ("r3s", "cornell"), ("r6g", "cornell"), ("r6s", "cornell"),
+           ("r4", "c6"), ("r5", "c6"), ("r10", "c6"), ("bvh", "c6"), ("hybrid", "c6"),
+           ("m2g", "spheres"), ("m2s", "spheres")]
+
+
+@pytest.mark.parametrize("route,scene_name", A_CASES)
+def test_a_per_frame_cameras(route, scene_name):
+    """Five cameras (four in the sphere room) in one batch, the sky frame in the middle and two
+    frames with one time: each frame is the oracle's of its own push, with and without the
+    caller's linear buffer."""
+    rt, cfg = _tracer(route, scene_name)
+    problems = []
+    with rt:
+        for linear in (True, False):
+            _run(problems, f"{route} linear={linear}", rt, cfg, route, scene_name, _pushes(scene_name),
+                 B.W, B.H, linear=linear)
+    assert not problems, problems
+
+
+@pytest.mark.parametrize("route,scene_name", [("r3g", "cornell"), ("r3s", "cornell"), ("r6s", "cornell"),
+                                              ("r10", "c6"), ("bvh", "c6"), ("hybrid", "c6")])
+def test_a_sky_only_batch(route, scene_name):
+    """Three frames that see only sky: the surface list stays empty, every pixel is the miss
+    colour, every sample is one traversal."""
+    pushes = [B.push(B.cornell_camera("sky"), t) for t in (3.0, 7.5, 301.25)]
+    rt, cfg = _tracer(route, scene_name)
+    problems = []
+    with rt:
+        for linear in (True, False):
+            got, orcs = _run(problems, f"{route} linear={linear}", rt, cfg, route, scene_name, pushes,
+                             B.W, B.H, linear=linear)
+            assert sum(o[2] for o in orcs) == 3 * B.W * B.H * cfg["spp"] == int(got[2]["samples"])
+            px = got[0][:3 * B.W * B.H]
+            assert (px == px[0]).all()
+    assert not problems, problems
+
+
+@pytest.mark.parametrize("route,scene_name", [("r3s", "cornell"), ("r10", "c6"), ("m2g", "spheres")])
+def test_a_t_range_checked_on_every_push(route, scene_name):
+    """A batch whose LAST push breaks the t-range rule (t_far = 2^24) is refused whole, leaves
+    nothing pending, and the next batch on the context is correct."""
+    import torch
+    pushes = _pushes(scene_name)
+    bad = [p.copy() for p in pushes]
+    bad[-1]["camera"]["t_far"] = 2.0 ** 24
+    assert not B.t_range_ok(bad[-1], B.W, B.H) and all(B.t_range_ok(p, B.W, B.H) for p in bad[:-1])
+    rt, cfg = _tracer(route, scene_name)
+    problems = []
+    with rt:
+        out = torch.full((len(bad) * B.W * B.H + GUARD,), SENTINEL, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        with pytest.raises(abi.RvcpError) as e:
+            rt.render_frames_async(bad, B.W, B.H, 0, 1, out.data_ptr())
+        assert e.value.code == abi.RVCP_E_INVALID
+        torch.cuda.synchronize()
+        assert (out.cpu().numpy().view(np.uint32) == SENTINEL).all()      # nothing was enqueued
+        _run(problems, route, rt, cfg, route, scene_name, pushes, B.W, B.H)
+    assert not problems, problems
+
+
+# ------------------------------------------------------------- B: frames smaller than a wave
+@pytest.mark.parametrize("w,h,frames", [(9, 7, 5), (1, 1, 70)])
+@pytest.mark.parametrize("route", ["r3s", "r6g", "r10", "hybrid", "m2g", "m2s"])
+def test_b_frames_smaller_than_a_wave(route, w, h, frames):
+    """63-pixel frames and 70 one-pixel frames, the cameras in turn at times 100 + k: a wave
+    of the pre-pass, a 64-pixel grab of mode 2's queue and a wave of the path kernel hold
+    pixels of several frames -- of more frames than a grab has slots."""
+    scene_name = SCENE_OF[route]
+    pushes = B.cycled_pushes(_cams(scene_name), frames)
+    rt, cfg = _tracer(route, scene_name)
+    problems = []
+    with rt:
+        _run(problems, route, rt, cfg, route, scene_name, pushes, w, h)
+    assert not problems, problems
+
+
+# ------------------------------------------------------------- C: padded and empty shards
+@pytest.mark.parametrize("k", [1, 2])
+@pytest.mark.parametrize("route", ["r3s", "r5", "r10", "bvh", "m2g"])
+def test_c_padded_shards(route, k):
+    """50 x 83 over three shards: the slot is shard 0's 32 rows, shard 1 has 27 (its last
+    stripe 3 rows) and shard 2 has 24; three frames with three cameras.  The slots' padding
+    rows are the library's to scribble on; the guard tails are not."""
+    scene_name = SCENE_OF[route]
+    pushes = _pushes(scene_name)
+    pushes = [pushes[0], pushes[3], pushes[1]]    # default, rolled, inside (the room: default, narrow, away)
+    rt, cfg = _tracer(route, scene_name)
+    problems = []
+    with rt:
+        _run(problems, f"{route} shard {k}", rt, cfg, route, scene_name, pushes, 50, 83, k, 3)
+    assert not problems, problems
+
+
+@pytest.mark.parametrize("route", ["r3s", "m2g"])
+def test_c_empty_shard(route):
+    """50 x 12 over three shards: shard 2 has no rows.  The batch is accepted, counts nothing
+    and writes nothing; the next batch on the context (shard 0) is correct."""
+    scene_name = SCENE_OF[route]
+    pushes = _pushes(scene_name)[:3]
+    rt, cfg = _tracer(route, scene_name)
+    problems = []
+    with rt:
+        assert rvcp_amd.shard_rows(12, 2, 3) == 0
+        got, _ = _run(problems, f"{route} empty", rt, cfg, route, scene_name, pushes, 50, 12, 2, 3)
+        assert int(got[2]["samples"]) == 0 and int(got[2]["traversals"]) == 0
+        assert (got[0] == SENTINEL).all() and (got[1] == SENTINEL).all()
+        _run(problems, f"{route} shard 0", rt, cfg, route, scene_name, pushes, 50, 12, 0, 3)
+    assert not problems, problems
+
+
+# --------------------------------------------------- D: both pre-pass forms at the threshold
+D_PUSHES = [B.push(B.cornell_camera("default"), 3.0), B.push(B.cornell_camera("rolled"), 7.5)]
+D_CFG = dict(spp=1, max_bounces=3)
+
+
+@pytest.mark.parametrize("above", [False, True], ids=["one_launch", "per_frame"])
+@pytest.mark.parametrize("route", ["r3g", "r3s", "r6s", "r10", "bvh"])
+def test_d_threshold_whole_frames(route, above):
+    """Two frames of exactly kPrepassBatchMaxPixels pixels (one pre-pass launch, a frame per
+    grid row, the cameras from the device table) and of one row more (a launch per frame, the
+    camera in each launch's arguments)."""
+    h = B.threshold_heights()[above]
+    p = B.prepass_batch_max_pixels()
+    assert (h * B.THRESHOLD_W > p) == above and (h - above) * B.THRESHOLD_W == p
+    rt, cfg = _tracer(route, "cornell", **D_CFG)
+    problems = []
+    with rt:
+        _run(problems, f"{route} {B.THRESHOLD_W} x {h}", rt, cfg, route, "cornell", D_PUSHES,
+             B.THRESHOLD_W, h)
+    assert not problems, problems
+
+
+@pytest.mark.parametrize("above", [False, True], ids=["one_launch", "per_frame"])
+@pytest.mark.parametrize("route", ["r3s", "r10"])
+def test_d_threshold_padded_shards(route, above):
+    """The threshold is taken on this shard's pixels, the stride on shard 0's: shard 2 of 3
+    with exactly the threshold's pixels in a larger slot (one launch, padded), and shard 1 of 3
+    with one stripe more (a launch per frame, padded)."""
+    h, k = B.threshold_shards()[above]
+    p = B.prepass_batch_max_pixels()
+    px = rvcp_amd.shard_rows(h, k, 3) * B.THRESHOLD_W
+    assert (px > p) == above and rvcp_amd.shard_rows(h, 0, 3) * B.THRESHOLD_W > px
+    rt, cfg = _tracer(route, "cornell", **D_CFG)
+    problems = []
+    with rt:
+        _run(problems, f"{route} {B.THRESHOLD_W} x {h} shard {k}", rt, cfg, route, "cornell", D_PUSHES,
+             B.THRESHOLD_W, h, k, 3)
+    assert not problems, problems
+
+
+# ------------------------------------------------------------- E: one context, many calls
+@pytest.mark.parametrize("route", ["auto", "m2s"])
+def test_e_one_context_many_calls(route):
+    """A small batch, a larger one (the camera table, the surface list and the linear scratch
+    grow), a single frame, a batch without the caller's linear buffer, a shard, and the first
+    batch again: every frame of every call against the oracle."""
+    import torch
+    scene_name = SCENE_OF[route]
+    cams, pushes = _cams(scene_name), _pushes(scene_name)
+    small = B.cycled_pushes(cams, 2)
+    rt, cfg = _tracer(route, scene_name)
+    problems = []
+    with rt:
+        _run(problems, "1: 2 of 9 x 7", rt, cfg, route, scene_name, small, 9, 7)
+        _run(problems, "2: all of 47 x 39", rt, cfg, route, scene_name, pushes, B.W, B.H)
+        # 3: one frame through rvcp_render_shard_async
+        one = pushes[1]
+        out = torch.full((B.W * B.H + GUARD,), SENTINEL, dtype=torch.int32, device="cuda")
+        lin = torch.full((3 * B.W * B.H + GUARD,), SENTINEL, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        rt.render_shard_async(one, B.W, B.H, 0, 1, out.data_ptr(), lin.data_ptr())
+        st = rt.sync_stats().copy()
+        torch.cuda.synchronize()
+        _compare(problems, "3: a single frame", (out.cpu().numpy().view(np.uint32),
+                                                 lin.cpu().numpy().view(np.uint32), st),
+                 B.oracle_frames(scene_name, cfg, [one], B.W, B.H), B.W, B.H, 0, 1, cfg["spp"],
+                 ROUTES[route][1], ROUTES[route][2])
+        _run(problems, "4: 3 without linear", rt, cfg, route, scene_name, pushes[:3], B.W, B.H, linear=False)
+        _run(problems, "5: 2 on shard 1 of 2", rt, cfg, route, scene_name, pushes[2:4], B.W, B.H, 1, 2)
+        _run(problems, "6: 2 of 9 x 7 again", rt, cfg, route, scene_name, small, 9, 7)
+    assert not problems, problems
+
+
+# ------------------------------------------------------------------ F: adversarial scenes
+@pytest.mark.parametrize("route", ["r3s", "r6g", "r6s", "hybrid"])
+@pytest.mark.parametrize("seed", B.FUZZ_SEEDS)
+def test_f_adversarial_scenes(seed, route):
+    """Fuzz scenes 2 (scale 1) and 3 (2^22, moved by 2^38) of tests/fuzz_scenes.py, each with
+    its own configuration, three frames at times 100 + seed + k; the hybrid on the scene with
+    160 specks, where it engages."""
+    scene_name = f"fuzz{seed}" + ("s" if route == "hybrid" else "")
+    sc = B.scene(scene_name)
+    pushes = [sc.push_constant(100.0 + seed + k) for k in range(3)]
+    rt, cfg = _tracer(route, scene_name)
+    problems = []
+    with rt:
+        _run(problems, f"{route} seed {seed}", rt, cfg, route, scene_name, pushes, B.FUZZ_W, B.FUZZ_H)
+    assert not problems, problems
+
+
+# ------------------------------------------------------------------------- G: cosine mode
+_cosine_refs = {}
+
+
+def _cosine_reference(scene_name):
+    """The five pushes rendered one by one on schedule 1 with the generic scan in cosine mode,
+    in a context of their own: the reference test_gpu_importance ties to its restatement."""
+    if scene_name not in _cosine_refs:
+        cfg = dict(B.scene_config(scene_name), kernel_variant=1, specialize=OFF)
+        refs = []
+        with rvcp_amd.RayTracer(**cfg) as rt:
+            rt.sampling = abi.SAMPLING_COSINE
+            rt.upload_scene(B.scene(scene_name))
+            for p in B.cornell_pushes():
+                rgba, lin = rt.render_push(p, B.W, B.H, want_linear=True)
+                assert int(rt.last_stats["kernel_variant"]) == 1
+                lin.setflags(write=False)
+                rgba.setflags(write=False)
+                refs.append((lin, rgba, int(rt.last_stats["traversals"])))
+        _cosine_refs[scene_name] = refs
+    return _cosine_refs[scene_name]
+
+
+@pytest.mark.parametrize("route", ["r3s", "r6g", "r10", "hybrid"])
+def test_g_cosine_batch(route):
+    """Group A's batch with cosine-weighted bounces (rvcp_set_sampling): bits, bytes and
+    traversals of every frame equal schedule 1's single render of the same push."""
+    scene_name = SCENE_OF[route]
+    refs = _cosine_reference(scene_name)
+    uniform = B.oracle_frames(scene_name, B.scene_config(scene_name), B.cornell_pushes(), B.W, B.H)
+    assert any(not np.array_equal(r[1], u[1]) for r, u in zip(refs, uniform))      # another estimator
+    rt, cfg = _tracer(route, scene_name)
+    problems = []
+    with rt:
+        rt.sampling = abi.SAMPLING_COSINE
+        for linear in (True, False):
+            got = _batch(rt, B.cornell_pushes(), B.W, B.H, linear=linear)
+            _compare(problems, f"{route} linear={linear}", got, refs, B.W, B.H, 0, 1, cfg["spp"],
+                     ROUTES[route][1], ROUTES[route][2])
+    assert not problems, problems
+
+
+# ------------------------------------------------------------------------------- H: stats
+@pytest.mark.parametrize("route", ["auto", "r4", "r10", "r3g"])
+def test_h_traversals_executed(route):
+    """The routes on which test_gpu_batch.py asserts it for equal cameras, here with five: the
+    batch's traversals_executed (and traversals) are the sums over single renders of the same
+    pushes on the same context."""
+    import torch
+    pushes = B.cornell_pushes()
+    rt, cfg = _tracer(route, "cornell")
+    problems = []
+    with rt:
+        singles = []
+        out = torch.zeros((B.W * B.H,), dtype=torch.int32, device="cuda")
+        for p in pushes:
+            rt.render_shard_async(p, B.W, B.H, 0, 1, out.data_ptr())
+            singles.append(rt.sync_stats().copy())
+        got, _ = _run(problems, route, rt, cfg, route, "cornell", pushes, B.W, B.H)
+    assert not problems, problems
+    for key in ("traversals", "traversals_executed"):
+        assert int(got[2][key]) == sum(int(s[key]) for s in singles), key
+    # primary hits are reused across a pixel's samples (rvcp.h): fewer ran than the reference's
+    assert 0 < int(got[2]["traversals_executed"]) < int(got[2]["traversals"])
