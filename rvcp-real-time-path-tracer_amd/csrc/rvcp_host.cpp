@@ -30,6 +30,7 @@
 
 #include "../../include/rvcp.h"
 #include "rvcp_internal.h"
+#include "rvcp_frame_plan.h"
 #include "rvcp_jit.h"
 #include "rvcp_scene_prep.h"
 #include "build/rvcp_build_id.h"     // kRvcpSourceHash (Makefile)
@@ -206,7 +207,7 @@ struct rvcp_ctx {
     size_t cap_dn[2] = {0, 0};
     void *d_gbuf = nullptr;
     float *d_dn_in = nullptr, *d_dn_out = nullptr;
-    size_t cap_gbuf = 0, cap_dn_io = 0;
+    size_t cap_gbuf = 0, cap_dn_in = 0, cap_dn_out = 0;
 
     // rvcp_render_temporal keeps its history here: accumulated colour, history length and
     // G-buffer ping-pong between the slots of tp_hist; d_tp_cur is the raw frame, d_tp_show the
@@ -285,7 +286,6 @@ struct rvcp_ctx {
     // last launch
     bool pending = false;
     bool last_trivial = false;
-    bool last_spec = false;
     int32_t last_variant = 0;
     uint64_t last_pixels = 0;
     uint32_t last_spp = 0;
@@ -408,6 +408,36 @@ void camera_constants(const rvcp_push_constant_t &pc, uint32_t W, uint32_t H, Fr
     A.time = pc.time;
 }
 
+// One frame's FrameCam record, the 16 floats a batch's kernels read per frame
+// (FrameArgs::batch_cams, the batched pre-pass): cam_pos, u, v, pos, base_len, t_near, t_far, time
+void pack_frame_cam(const FrameArgs &A, float *c)
+{
+    std::memcpy(c, A.cam_pos, 12);
+    std::memcpy(c + 3, A.u, 12);
+    std::memcpy(c + 6, A.v, 12);
+    std::memcpy(c + 9, A.pos, 12);
+    c[12] = A.base_len;
+    c[13] = A.t_near;
+    c[14] = A.t_far;
+    c[15] = A.time;
+}
+
+// The fields of FrameArgs the primary ray and its scan read: the camera, the frame's size, the
+// face count and the BVH (render_frames, rvcp_render_gbuffer_async)
+void primary_frame_args(const rvcp_ctx *ctx, const rvcp_push_constant_t &pc, uint32_t W, uint32_t H,
+                        FrameArgs &A)
+{
+    camera_constants(pc, W, H, A);
+    A.width = W;
+    A.height = H;
+    A.n_faces = ctx->n_faces;
+    A.accel = resolved_accel(ctx->cfg.accel, ctx->n_faces);
+    A.bvh_root = ctx->bvh_root;
+    A.bvh_n4 = ctx->bvh_n4;
+    A.bvh_slots = ctx->bvh_slots;
+    A.bvh_prefix = A.accel == RVCP_ACCEL_BVH ? ctx->bvh_prefix : 0u;
+}
+
 // The primary ray's range is [t_near, t_far] x t_coef (sample_ray, :226-233), and a miss is
 // written as t_max + 1 (:287) and detected as t > t_max (:424): once t_max reaches 2^24 the +1
 // is lost and the shader takes a miss for a hit on uninitialised data.  The kernels detect a
@@ -431,6 +461,50 @@ int dev_upload(rvcp_ctx *ctx, T **dst, const void *src, size_t n)
     const size_t bytes = n ? n * sizeof(T) : sizeof(T);
     HIP_TRY(ctx, hipMalloc((void **)dst, bytes));
     if (n) HIP_TRY(ctx, hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return RVCP_OK;
+}
+
+// *buf holds at least n elements of `elem` bytes: a buffer too small is freed and allocated anew
+int grow(rvcp_ctx *ctx, void **buf, size_t *cap, size_t n, size_t elem)
+{
+    if (*cap >= n) return RVCP_OK;
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    HIP_TRY(ctx, hipMalloc(buf, n * elem));
+    *cap = n;
+    return RVCP_OK;
+}
+
+// ... a batch's n FrameCam records (64 B each): the device buffer and its pinned staging
+int grow_cams(rvcp_ctx *ctx, uint32_t n)
+{
+    if (ctx->cap_cams >= n) return RVCP_OK;
+    (void)hipFree(ctx->d_cams);
+    (void)hipHostFree(ctx->h_cams);
+    ctx->d_cams = ctx->h_cams = nullptr;
+    ctx->cap_cams = 0;
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_cams, (size_t)n * 64));
+    HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_cams, (size_t)n * 64));
+    ctx->cap_cams = n;
+    return RVCP_OK;
+}
+
+// ... a packed shard's bytes and linear colours on `device` (render_multi), px pixels each and one
+// pixel of slack; both are made anew when the linear buffer is wanted and missing
+int grow_packed(rvcp_ctx *ctx, int device, uint32_t **rgba, float **lin, size_t *cap, size_t px,
+                bool want_lin)
+{
+    if (*cap >= px && !(want_lin && !*lin)) return RVCP_OK;
+    HIP_TRY(ctx, hipSetDevice(device));
+    (void)hipFree(*rgba);
+    (void)hipFree(*lin);
+    *rgba = nullptr;
+    *lin = nullptr;
+    *cap = 0;
+    HIP_TRY(ctx, hipMalloc((void **)rgba, px * 4 + 4));
+    HIP_TRY(ctx, hipMalloc((void **)lin, px * 12 + 12));
+    *cap = px;
     return RVCP_OK;
 }
 
@@ -696,31 +770,21 @@ static int impl_create(const rvcp_config_t *cfg, rvcp_ctx_t **out_ctx)
     const char *cap_env = RVCP_KNOB("RVCP_DEBUG_BLOCKS_PER_CU");
     const int cap = cap_env ? std::atoi(cap_env) : 0;
     ctx->n_simds = (uint32_t)cus * 4u;
+    // resident workgroups of a kernel: its occupancy per CU (1 when the query fails), capped
+    auto capacity = [&](auto &&occupancy) {
+        int per_cu = 0;
+        if (occupancy(&per_cu) != 0 || per_cu <= 0) per_cu = 1;
+        if (cap > 0 && cap < per_cu) per_cu = cap;
+        return per_cu * cus;
+    };
     for (int v = 1; v <= kMaxVariant; v++) {
         if (v == 7 || v == 8 || v == 9) continue;
-        int per_cu = 0;
-        if (rvcp_games101_occupancy(v, &per_cu) != 0 || per_cu <= 0) per_cu = 1;
-        if (cap > 0 && cap < per_cu) per_cu = cap;
-        ctx->grid_capacity[v] = per_cu * cus;
-        per_cu = 0;
-        if (rvcp_games101_occupancy_cosine(v, &per_cu) != 0 || per_cu <= 0) per_cu = 1;
-        if (cap > 0 && cap < per_cu) per_cu = cap;
-        ctx->grid_capacity_cos[v] = per_cu * cus;
+        ctx->grid_capacity[v] = capacity([v](int *n) { return rvcp_games101_occupancy(v, n); });
+        ctx->grid_capacity_cos[v] = capacity([v](int *n) { return rvcp_games101_occupancy_cosine(v, n); });
     }
-    {
-        int per_cu = 0;
-        if (rvcp_legacy_occupancy(&per_cu) != 0 || per_cu <= 0) per_cu = 1;
-        if (cap > 0 && cap < per_cu) per_cu = cap;
-        ctx->legacy_capacity = per_cu * cus;
-        per_cu = 0;
-        if (rvcp_games101_occupancy(kOccupancyBvh, &per_cu) != 0 || per_cu <= 0) per_cu = 1;
-        if (cap > 0 && cap < per_cu) per_cu = cap;
-        ctx->bvh_capacity = per_cu * cus;
-        per_cu = 0;
-        if (rvcp_games101_occupancy_cosine(kOccupancyBvh, &per_cu) != 0 || per_cu <= 0) per_cu = 1;
-        if (cap > 0 && cap < per_cu) per_cu = cap;
-        ctx->bvh_capacity_cos = per_cu * cus;
-    }
+    ctx->legacy_capacity = capacity(rvcp_legacy_occupancy);
+    ctx->bvh_capacity = capacity([](int *n) { return rvcp_games101_occupancy(kOccupancyBvh, n); });
+    ctx->bvh_capacity_cos = capacity([](int *n) { return rvcp_games101_occupancy_cosine(kOccupancyBvh, n); });
     if (cfg->n_gpus > 1) {   // one sub-context per further GPU (shards 1..N-1)
         for (int i = 1; i < cfg->n_gpus; i++) {
             rvcp_config_t sub_cfg = *cfg;
@@ -1075,6 +1139,45 @@ static void jit_for_sampling(rvcp_ctx_t *ctx)
     if (ctx->jit_bvh && ctx->jit && (!ctx->jit->bvh_path || !ctx->jit->bvh_primary)) ctx->jit.reset();
 }
 
+// What plan_frame (rvcp_frame_plan.cpp) decides a render from: the config, the scene, the device's
+// capacities for the context's bounce sampling, the scene's specialised module and the frames
+static FramePlanIn frame_plan_input(const rvcp_ctx_t *ctx, uint32_t n_frames, uint32_t frame_px,
+                                    uint32_t stride)
+{
+    const bool cosine = ctx->sampling == RVCP_SAMPLING_COSINE;
+    FramePlanIn in;
+    in.integrator = ctx->cfg.integrator;
+    in.kernel_variant = ctx->cfg.kernel_variant;
+    in.accel = ctx->cfg.accel;
+    in.spp = ctx->cfg.spp;
+    in.max_bounces = ctx->cfg.max_bounces;
+    in.attenuation_stop_eps = ctx->cfg.attenuation_stop_eps;
+    in.ray_t_min = ctx->cfg.ray_t_min;
+    in.grid_waves_per_simd = ctx->cfg.grid_waves_per_simd;
+    in.n_faces = ctx->n_faces;
+    in.bvh_prefix = ctx->bvh_prefix;
+    in.n_simds = ctx->n_simds;
+    std::memcpy(in.grid_capacity, cosine ? ctx->grid_capacity_cos : ctx->grid_capacity,
+                sizeof(in.grid_capacity));
+    in.bvh_capacity = cosine ? ctx->bvh_capacity_cos : ctx->bvh_capacity;
+    in.legacy_capacity = ctx->legacy_capacity;
+    if (const JitKernels *jk = ctx->jit.get()) {
+        in.module = true;
+        in.blocks_per_cu5 = jk->blocks_per_cu5;
+        in.blocks_per_cu6 = jk->blocks_per_cu6;
+        in.blocks_per_cu_bvh = jk->blocks_per_cu_bvh;
+        in.blocks_per_cu_legacy = jk->blocks_per_cu_legacy;
+        in.has_legacy = jk->legacy != nullptr;
+        in.has_bvh_path = jk->bvh_path != nullptr;
+        in.has_bvh_primary = jk->bvh_primary != nullptr;
+    }
+    in.n_frames = n_frames;
+    in.frame_px = frame_px;
+    in.stride = stride;
+    if (const char *c = RVCP_KNOB("RVCP_DEBUG_SPREAD")) in.spread_min = (uint32_t)std::atoi(c);
+    return in;
+}
+
 // n_frames consecutive frames of one shard (pushes[k] for frame k) into outputs laid out frame
 // after frame, `slot` = the largest shard's rows apart (rvcp_render_frames_async); n_frames = 1
 // is rvcp_render_shard_async.
@@ -1106,15 +1209,29 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
 
-    const uint32_t rows = rvcp_shard_rows(height, shard_index, shard_count);
+    // the cosine-weighted bounce (rvcp_set_sampling): its kernels, and a
+    // specialised module compiled for it
+    const bool cosine = ctx->sampling == RVCP_SAMPLING_COSINE;
+    if (ctx->jit_sampling != ctx->sampling) jit_for_sampling(ctx);
+
+    // the plan: schedule, specialised kernels and grid (rvcp_frame_plan.cpp)
+    const uint32_t frame_px = rvcp_shard_rows(height, shard_index, shard_count) * width;
+    const uint32_t split_px = frame_px * n_frames;          // the queue of the whole batch
+    const JitKernels *jk = ctx->jit.get();
+    const FramePlanIn in = frame_plan_input(ctx, n_frames, frame_px, stride);
+    const FramePlan P = plan_frame(in);
+    if (P.status != RVCP_OK)
+        return fail(ctx, P.status, "frame batches need a pre-pass schedule of the games101 "
+                    "integrator (schedules 3-6, 10, or the BVH path kernel) or mode 2");
+    const bool launches = !P.trivial && frame_px > 0;           // a path kernel runs
+    const bool lin_staged = P.legacy || P.variant >= 3;         // ... that leaves linear colours
+
     FrameArgs A;
     std::memset(&A, 0, sizeof(A));
-    camera_constants(*push, width, height, A);
-    A.width = width;
-    A.height = height;
+    primary_frame_args(ctx, *push, width, height, A);
     A.shard_index = shard_index;
     A.shard_count = shard_count;
-    A.n_pixels = rows * width;
+    A.n_pixels = frame_px;
     A.spp = ctx->cfg.spp;
     A.max_bounces = ctx->cfg.max_bounces;
     A.att_stop = ctx->cfg.attenuation_stop_eps;
@@ -1122,7 +1239,6 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
     A.t_max = ctx->cfg.ray_t_max;
     A.rr = ctx->cfg.rr_probability;
     A.eps = ctx->cfg.eps;
-    A.n_faces = ctx->n_faces;
     A.n_lights = ctx->n_lights;
     A.lights_same = ctx->lights_same ? 1u : 0u;
     A.rcp_fast = ctx->rcp_fast ? 1u : 0u;
@@ -1136,231 +1252,114 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
         A.brdf_rcp[1] = 1.0f / A.brdf_den[1];
         A.brdf_rcp[0] = 1.0f / A.brdf_den[0];
     }
-    // the cosine-weighted bounce (rvcp_set_sampling): its kernels, its factor
-    // k = PI_F / rr, and a specialised module compiled for it
-    const bool cosine = ctx->sampling == RVCP_SAMPLING_COSINE;
-    A.cos_k = 3.1415926f / A.rr;
-    if (ctx->jit_sampling != ctx->sampling) jit_for_sampling(ctx);
+    A.cos_k = 3.1415926f / A.rr;        // the cosine-weighted bounce's factor k = PI_F / rr
     A.want_linear = d_linear_rgb ? 1u : 0u;
-    // automatic schedule: 10 / 5 (LDS tiles; the workgroup's rays pooled into full passes on
-    // large frames, one ray per lane on small ones) for large meshes, 10 also for mid-size
-    // meshes on large frames, else 3, or 6 (6 waves/SIMD) for
-    // large frames -- with the scene-specialised scan only for very large frames
-    // (kSpecWideMinSamples: its 6-wave build is slower below)
-    const bool jit_ok = ctx->jit && ctx->cfg.ray_t_min > 0.0f;
-    const bool big_frame = (uint64_t)A.n_pixels * A.spp >= kTiledDualMinSamples;
-    A.variant = ctx->cfg.kernel_variant != 0 ? ctx->cfg.kernel_variant
-              : ctx->n_faces >= kTiledMinFaces ? (big_frame ? kTiledPoolVariant : 5)
-              : (!jit_ok && ctx->n_faces > kTiledWideMinFaces && big_frame) ? kTiledPoolVariant
-              : ((uint64_t)A.n_pixels * A.spp >= (jit_ok ? kSpecWideMinSamples : kWideMinSamples)) ? 6
-              : kDefaultVariant;
-    A.accel = (ctx->cfg.accel == RVCP_ACCEL_BVH && ctx->n_faces > 0) ? RVCP_ACCEL_BVH : RVCP_ACCEL_NONE;
-    if (A.accel == RVCP_ACCEL_BVH) A.variant = 3;    // the BVH traversal lives in the v3 kernels
-    A.bvh_root = ctx->bvh_root;
-    A.bvh_n4 = ctx->bvh_n4;
-    A.bvh_slots = ctx->bvh_slots;
-    A.bvh_prefix = A.accel == RVCP_ACCEL_BVH ? ctx->bvh_prefix : 0u;
-    const bool legacy = ctx->cfg.integrator == RVCP_INTEGRATOR_LEGACY;
-    A.n_spheres = legacy ? ctx->n_spheres : 0u;
+    A.variant = P.variant;
+    A.n_spheres = P.legacy ? ctx->n_spheres : 0u;
     A.n_mats = ctx->n_mats;
-
-    // With MAX_BOUNCES == 0 or ATTENUATION_STOP_EPS > 1 every sample returns 0 before its
-    // first traversal (:413-419): the frame is black.  ray_tracer.comp has no attenuation
-    // test before its first traversal (:629-634).
-    const bool trivial = A.max_bounces == 0 || (!legacy && 1.0f < A.att_stop);
-    // a batch shares one surface list and one path kernel: the pre-pass schedules (3-6, 10 and
-    // the persistent BVH path kernel) only
-    if (n_frames > 1 && !trivial && !legacy && A.variant < 3)
-        return fail(ctx, RVCP_E_UNSUPPORTED, "frame batches need a pre-pass schedule of the games101 "
-                    "integrator (schedules 3-6, 10, or the BVH path kernel) or mode 2");
-    std::vector<FrameArgs> FA;          // per frame of the batch (camera, time, pixel base)
-    const uint32_t frame_px = A.n_pixels;
-    const uint32_t split_px = frame_px * n_frames;          // the queue of the whole batch
-    // a batch's cameras and times in device memory: mode 2's one kernel and the pre-pass
-    // schedules' one pre-pass launch read them per frame
-    const bool cams = n_frames > 1 && !trivial && frame_px > 0 && (legacy || A.variant >= 3);
-    if (cams) {
-        if (ctx->cap_cams < n_frames) {
-            (void)hipFree(ctx->d_cams);
-            (void)hipHostFree(ctx->h_cams);
-            ctx->d_cams = ctx->h_cams = nullptr;
-            ctx->cap_cams = 0;
-            HIP_TRY(ctx, hipMalloc((void **)&ctx->d_cams, (size_t)n_frames * 64));
-            HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_cams, (size_t)n_frames * 64));
-            ctx->cap_cams = n_frames;
-        }
-        for (uint32_t k = 0; k < n_frames; ++k) {
-            FrameArgs C;
-            std::memset(&C, 0, sizeof(C));
-            camera_constants(pushes[k], width, height, C);
-            float *c = ctx->h_cams + 16 * (size_t)k;
-            std::memcpy(c, C.cam_pos, 12);
-            std::memcpy(c + 3, C.u, 12);
-            std::memcpy(c + 6, C.v, 12);
-            std::memcpy(c + 9, C.pos, 12);
-            c[12] = C.base_len;
-            c[13] = C.t_near;
-            c[14] = C.t_far;
-            c[15] = C.time;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cams, ctx->h_cams, (size_t)n_frames * 64,
-                                    hipMemcpyHostToDevice, s));
+    A.n_simds = ctx->n_simds;
+    A.static_chunk = P.static_chunk;
+    A.static_chunks = P.static_chunks;
+    A.dyn_chunk = kDynChunk;
+    A.chunk_min = kMinChunk;
+    A.chunk_window = kChunkWindow;
+    if (const char *c = RVCP_KNOB("RVCP_DEBUG_CHUNK")) {   // fixed grab (experiments)
+        const int v = std::atoi(c);
+        if (v >= 1 && v <= (int)kDynChunk) A.dyn_chunk = A.chunk_min = (uint32_t)v;   // <= 64: mode 2 prefills a grab into 64 LDS slots
     }
-    if (cams && legacy) {
+    if (const char *c = RVCP_KNOB("RVCP_DEBUG_CHUNK_WINDOW")) {
+        const int v = std::atoi(c);
+        if (v >= 1) A.chunk_window = (uint32_t)v;
+    }
+    A.spread_min = in.spread_min;
+    if (const char *c = RVCP_KNOB("RVCP_DEBUG_EARLY_TAIL")) A.early_tail = (uint32_t)std::atoi(c);
+    if (P.cams && P.legacy) {
         // mode 2 has no pre-pass: its one kernel queues the batch's pixels frame after frame
         // and reads each frame's camera and time from d_cams (FrameArgs::batch_cams)
-        A.batch_cams = ctx->d_cams;
         A.frame_pixels = frame_px;
         A.frame_stride = stride;
         A.n_pixels = split_px;
     }
-    ctx->last_spec = false;
+
+    // the buffers the launch needs.  A batch's cameras and times in device memory: mode 2's one
+    // kernel and the pre-pass schedules' one pre-pass launch read them per frame
+    int rc;
+    if (P.cams) {
+        if ((rc = grow_cams(ctx, n_frames)) != RVCP_OK) return rc;
+        if (P.legacy) A.batch_cams = ctx->d_cams;
+    }
+    ctx->last_timeline_waves = 0;
+    if (launches && lin_staged && RVCP_KNOB("RVCP_DEBUG_TIMELINE")) {
+        const size_t waves = (size_t)P.blocks * P.wpb;
+        if ((rc = grow(ctx, (void **)&ctx->d_timeline, &ctx->cap_timeline, waves, 64)) != RVCP_OK)
+            return rc;
+        A.timeline = ctx->d_timeline;
+        ctx->last_timeline_waves = waves;
+    }
+    // the mode-2 and v3-family kernels leave linear colours and tonemap_kernel stores
+    // the bytes: into the caller's linear buffer, else the context's scratch
+    float *lin = (float *)d_linear_rgb;
+    if (launches && lin_staged && !lin) {
+        if ((rc = grow(ctx, (void **)&ctx->d_acc, &ctx->cap_acc, P.out_px, 12)) != RVCP_OK) return rc;
+        lin = ctx->d_acc;
+    }
+    // the surface list of the pre-pass schedules, shared by the batch
+    if (launches && !P.legacy && P.variant >= 3 &&
+        (rc = grow(ctx, (void **)&ctx->d_surf, &ctx->cap_surf, split_px, sizeof(SurfRecord))) != RVCP_OK)
+        return rc;
+
+    // per frame of the batch: camera, time, pixel base
+    std::vector<FrameArgs> FA(n_frames, A);
+    for (uint32_t k = 1; k < n_frames; ++k) {
+        camera_constants(pushes[k], width, height, FA[k]);
+        FA[k].pix_base = k * stride;
+    }
+    if (P.cams) {
+        for (uint32_t k = 0; k < n_frames; ++k) pack_frame_cam(FA[k], ctx->h_cams + 16 * (size_t)k);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cams, ctx->h_cams, (size_t)n_frames * 64,
+                                    hipMemcpyHostToDevice, s));
+    }
+
     // a gather of this context's previous frame may still read the caller's shard buffer
     if (ctx->gather_on_gstream) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evg1, 0));
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, kCounterWords * sizeof(unsigned long long), s));
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
-    if (A.n_pixels > 0) {
-        int rc;
-        if (trivial) {
-            HIP_TRY(ctx, hipEventRecord(ctx->evm, s));
-            rc = rvcp_launch_fill((uint32_t *)d_rgba8, (float *)d_linear_rgb,
-                                  n_frames > 1 ? n_frames * stride : A.n_pixels, 0xFF000000u, s);
-        } else {
-            // the scene-specialised path kernel (§4.7) replaces schedules 3 and 6 when the
-            // upload compiled one; its exactness argument needs t_min > 0
-            const JitKernels *jk = ctx->jit.get();
-            const int jit_per_cu = !jk ? 0 : A.variant == 6 ? jk->blocks_per_cu6
-                                 : A.variant == 3 ? jk->blocks_per_cu5 : 0;
-            const bool spec = !legacy && !A.accel && jit_per_cu > 0 && A.t_min > 0.0f;
-            // mode 2 with the specialised triangle scan (its kernel also checks per wave
-            // that every ray is finite and has t_min > 0)
-            const bool spec_legacy = legacy && jk && jk->legacy && jk->blocks_per_cu_legacy > 0;
-            // the BVH hybrid's kernels (the prefix faces by the specialised scan); without them
-            // (t_min <= 0) the built-in BVH kernels test the prefix with the generic test
-            const bool spec_bvh = !legacy && A.accel && A.bvh_prefix > 0 && jk && jk->bvh_path &&
-                                  jk->bvh_primary && jk->blocks_per_cu_bvh > 0 && A.t_min > 0.0f;
-            uint32_t cap = (uint32_t)(legacy ? ctx->legacy_capacity
-                                     : A.accel ? (cosine ? ctx->bvh_capacity_cos : ctx->bvh_capacity)
-                                     : cosine ? ctx->grid_capacity_cos[A.variant]
-                                              : ctx->grid_capacity[A.variant]);
-            if (spec) cap = (uint32_t)jit_per_cu * (ctx->n_simds / 4u);
-            if (spec_bvh) cap = (uint32_t)jk->blocks_per_cu_bvh * (ctx->n_simds / 4u);
-            if (spec_legacy) cap = (uint32_t)jk->blocks_per_cu_legacy * (ctx->n_simds / 4u);
-            A.n_simds = ctx->n_simds;
-            uint32_t waves = 0, chunk = 0;
-            const uint32_t wpb = (uint32_t)((legacy || A.accel ? kBlock : variant_block(A.variant)) / kWave);
-            if (ctx->cfg.grid_waves_per_simd > 0) {     // the caller's grid per frame (rvcp.h)
-                const uint64_t lim = (uint64_t)ctx->cfg.grid_waves_per_simd * ctx->n_simds / wpb;
-                if (lim < cap) cap = lim > 0 ? (uint32_t)lim : 1u;
-            }
-            rvcp_static_split(split_px, cap * wpb, A.n_simds, &waves, &chunk);
-            uint32_t blocks = (waves + wpb - 1) / wpb;
-            if (blocks > cap) blocks = cap;
-            if (blocks == 0) blocks = 1;
-            A.static_chunk = chunk;
-            A.static_chunks = waves * chunk;
-            A.dyn_chunk = kDynChunk;
-            A.chunk_min = kMinChunk;
-            A.chunk_window = kChunkWindow;
-            if (const char *c = RVCP_KNOB("RVCP_DEBUG_CHUNK")) {   // fixed grab (experiments)
-                const int v = std::atoi(c);
-                if (v >= 1 && v <= (int)kDynChunk) A.dyn_chunk = A.chunk_min = (uint32_t)v;   // <= 64: mode 2 prefills a grab into 64 LDS slots
-            }
-            if (const char *c = RVCP_KNOB("RVCP_DEBUG_CHUNK_WINDOW")) {
-                const int v = std::atoi(c);
-                if (v >= 1) A.chunk_window = (uint32_t)v;
-            }
-            A.spread_min = 0;
-            A.early_tail = 0;
-            if (const char *c = RVCP_KNOB("RVCP_DEBUG_SPREAD")) A.spread_min = (uint32_t)std::atoi(c);
-            if (const char *c = RVCP_KNOB("RVCP_DEBUG_EARLY_TAIL")) A.early_tail = (uint32_t)std::atoi(c);
-            // schedules 3/6 spreading a small surface list run the full resident grid
-            if (A.spread_min && !legacy && !A.accel && (A.variant == 3 || A.variant == 6)) blocks = cap;
-            ctx->last_timeline_waves = 0;
-            if (RVCP_KNOB("RVCP_DEBUG_TIMELINE") && (legacy || A.variant >= 3)) {
-                const size_t waves = (size_t)blocks * wpb;
-                if (ctx->cap_timeline < waves) {
-                    (void)hipFree(ctx->d_timeline);
-                    ctx->d_timeline = nullptr;
-                    ctx->cap_timeline = 0;
-                    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_timeline, waves * 64));
-                    ctx->cap_timeline = waves;
-                }
-                A.timeline = ctx->d_timeline;
-                ctx->last_timeline_waves = waves;
-            }
-            // the mode-2 and v3-family kernels leave linear colours and tonemap_kernel stores
-            // the bytes: into the caller's linear buffer, else the context's scratch
-            float *lin = (float *)d_linear_rgb;
-            const uint32_t n_lin = n_frames > 1 ? n_frames * stride : A.n_pixels;
-            if (!lin && (legacy || A.variant >= 3)) {
-                if (ctx->cap_acc < n_lin) {
-                    (void)hipFree(ctx->d_acc);
-                    ctx->d_acc = nullptr;
-                    ctx->cap_acc = 0;
-                    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_acc, (size_t)n_lin * 12));
-                    ctx->cap_acc = n_lin;
-                }
-                lin = ctx->d_acc;
-            }
-            if (legacy) {
-                HIP_TRY(ctx, hipEventRecord(ctx->evm, s));
-                rc = rvcp_launch_legacy(&A, ctx->d_tri, ctx->d_shade, ctx->d_spheres,
-                                        ctx->d_rawmats, ctx->d_unorm, (uint32_t *)d_rgba8,
-                                        lin, ctx->d_counters, blocks, s,
-                                        spec_legacy ? (void *)jk->legacy : nullptr);
-                if (spec_legacy) ctx->last_spec = true;
-            } else if (A.variant >= 3) {
-                const uint32_t n_surf = split_px;
-                if (ctx->cap_surf < n_surf) {
-                    (void)hipFree(ctx->d_surf);
-                    ctx->d_surf = nullptr;
-                    ctx->cap_surf = 0;
-                    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_surf, (size_t)n_surf * sizeof(SurfRecord)));
-                    ctx->cap_surf = n_surf;
-                }
-                {
-                    FA.assign(n_frames, A);
-                    for (uint32_t k = 1; k < n_frames; ++k) {
-                        camera_constants(pushes[k], width, height, FA[k]);
-                        FA[k].pix_base = k * stride;
-                    }
-                    rc = (cosine ? rvcp_launch_games101_v3_cosine : rvcp_launch_games101_v3)(
-                                                 FA.data(), n_frames, stride, ctx->d_tri,
-                                                 ctx->d_faces, ctx->d_verts,
-                                                 ctx->d_mats, ctx->d_lights, ctx->d_gamma,
-                                                 (uint32_t *)d_rgba8, lin,
-                                                 ctx->d_counters, ctx->d_surf, ctx->d_shade,
-                                                 ctx->d_bvh_nodes, ctx->d_bvh_tris,
-                                                 blocks, s, ctx->evm,
-                                                 spec ? (void *)(A.variant == 6 ? jk->path6 : jk->path5)
-                                                      : spec_bvh ? (void *)jk->bvh_path : nullptr,
-                                                 cams && frame_px <= kPrepassBatchMaxPixels
-                                                     ? ctx->d_cams : nullptr,
-                                                 spec && jit_spec_prepass() ? (void *)jk->primary
-                                                 : spec_bvh ? (void *)jk->bvh_primary : nullptr);
-                }
-                if (spec || spec_bvh) ctx->last_spec = true;
-            } else {
-                HIP_TRY(ctx, hipEventRecord(ctx->evm, s));
-                rc = (cosine ? rvcp_launch_games101_cosine : rvcp_launch_games101)(
-                    &A, ctx->d_tri, ctx->d_faces, ctx->d_verts, ctx->d_mats, ctx->d_lights,
-                    ctx->d_gamma, (uint32_t *)d_rgba8, (float *)d_linear_rgb, ctx->d_counters,
-                    blocks, s);
-            }
-        }
-        if (rc != 0) return fail(ctx, RVCP_E_HIP, std::string("kernel launch failed: ") +
-                                                      hipGetErrorString(hipGetLastError()));
+    int launch_rc = 0;
+    if (frame_px == 0) {
+        HIP_TRY(ctx, hipEventRecord(ctx->evm, s));
+    } else if (P.trivial) {
+        HIP_TRY(ctx, hipEventRecord(ctx->evm, s));
+        launch_rc = rvcp_launch_fill((uint32_t *)d_rgba8, (float *)d_linear_rgb, P.out_px,
+                                     0xFF000000u, s);
+    } else if (P.legacy) {
+        HIP_TRY(ctx, hipEventRecord(ctx->evm, s));
+        launch_rc = rvcp_launch_legacy(&A, ctx->d_tri, ctx->d_shade, ctx->d_spheres, ctx->d_rawmats,
+                                       ctx->d_unorm, (uint32_t *)d_rgba8, lin, ctx->d_counters,
+                                       P.blocks, s, P.spec_legacy ? (void *)jk->legacy : nullptr);
+    } else if (P.variant >= 3) {
+        // (the launcher records evm itself, between the pre-pass and the path kernel)
+        launch_rc = (cosine ? rvcp_launch_games101_v3_cosine : rvcp_launch_games101_v3)(
+            FA.data(), n_frames, stride, ctx->d_tri, ctx->d_faces, ctx->d_verts, ctx->d_mats,
+            ctx->d_lights, ctx->d_gamma, (uint32_t *)d_rgba8, lin, ctx->d_counters, ctx->d_surf,
+            ctx->d_shade, ctx->d_bvh_nodes, ctx->d_bvh_tris, P.blocks, s, ctx->evm,
+            P.spec ? (void *)(P.variant == 6 ? jk->path6 : jk->path5)
+                   : P.spec_bvh ? (void *)jk->bvh_path : nullptr,
+            P.prepass_batched ? ctx->d_cams : nullptr,
+            P.spec && jit_spec_prepass() ? (void *)jk->primary
+                                         : P.spec_bvh ? (void *)jk->bvh_primary : nullptr);
     } else {
         HIP_TRY(ctx, hipEventRecord(ctx->evm, s));
+        launch_rc = (cosine ? rvcp_launch_games101_cosine : rvcp_launch_games101)(
+            &A, ctx->d_tri, ctx->d_faces, ctx->d_verts, ctx->d_mats, ctx->d_lights, ctx->d_gamma,
+            (uint32_t *)d_rgba8, (float *)d_linear_rgb, ctx->d_counters, P.blocks, s);
     }
+    if (launch_rc != 0) return fail(ctx, RVCP_E_HIP, std::string("kernel launch failed: ") +
+                                                         hipGetErrorString(hipGetLastError()));
     HIP_TRY(ctx, hipEventRecord(ctx->ev1, s));
     ctx->pending = true;
     ctx->render_stream = s;
-    ctx->last_trivial = trivial;
-    ctx->last_variant = (trivial || A.n_pixels == 0) ? 0 : legacy ? 8
-                      : A.accel ? 7 : A.variant;
-    if (ctx->last_spec && ctx->last_variant != 0) ctx->last_variant |= RVCP_VARIANT_SPECIALIZED;
+    ctx->last_trivial = P.trivial;
+    ctx->last_variant = P.stats_code;
     ctx->last_pixels = (uint64_t)frame_px * n_frames;       // stats cover the whole batch
     ctx->last_spp = A.spp;
     ctx->last_shard_index = shard_index;
@@ -1453,35 +1452,18 @@ static int render_multi(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint3
     const uint32_t N = (uint32_t)ctx->subs.size() + 1;
     int rc;
     // 1. launch every shard (shard 0 renders on ctx itself, into a packed buffer of its own)
-    for (uint32_t k = 0; k < N; k++) {
-        rvcp_ctx *c = k == 0 ? ctx : ctx->subs[k - 1];
-        const size_t rows = rvcp_shard_rows(H, k, N), px = rows * W;
-        if (k > 0 && (ctx->shard_cap[k - 1] < px || (want_lin && !ctx->shard_lin[k - 1]))) {
-            HIP_TRY(ctx, hipSetDevice(c->device));
-            (void)hipFree(ctx->shard_rgba[k - 1]);
-            (void)hipFree(ctx->shard_lin[k - 1]);
-            ctx->shard_rgba[k - 1] = nullptr;
-            ctx->shard_lin[k - 1] = nullptr;
-            ctx->shard_cap[k - 1] = 0;
-            HIP_TRY(ctx, hipMalloc((void **)&ctx->shard_rgba[k - 1], px * 4 + 4));
-            HIP_TRY(ctx, hipMalloc((void **)&ctx->shard_lin[k - 1], px * 12 + 12));
-            ctx->shard_cap[k - 1] = px;
-        }
+    for (uint32_t k = 1; k < N; k++) {
+        const size_t px = (size_t)rvcp_shard_rows(H, k, N) * W;
+        if ((rc = grow_packed(ctx, ctx->subs[k - 1]->device, &ctx->shard_rgba[k - 1],
+                              &ctx->shard_lin[k - 1], &ctx->shard_cap[k - 1], px, want_lin)) != RVCP_OK)
+            return rc;
     }
     // shard 0 needs its own packed buffer too: reuse the staging's tail is not possible, so
     // keep it in shard_rgba[-1] semantics via a dedicated allocation on ctx
     const size_t px0 = (size_t)rvcp_shard_rows(H, 0, N) * W;
-    if (ctx->cap_surf_pack < px0 || (want_lin && !ctx->d_pack_lin)) {
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        (void)hipFree(ctx->d_pack_rgba);
-        (void)hipFree(ctx->d_pack_lin);
-        ctx->d_pack_rgba = nullptr;
-        ctx->d_pack_lin = nullptr;
-        ctx->cap_surf_pack = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_pack_rgba, px0 * 4 + 4));
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_pack_lin, px0 * 12 + 12));
-        ctx->cap_surf_pack = px0;
-    }
+    if ((rc = grow_packed(ctx, ctx->device, &ctx->d_pack_rgba, &ctx->d_pack_lin, &ctx->cap_surf_pack,
+                          px0, want_lin)) != RVCP_OK)
+        return rc;
     for (uint32_t k = 0; k < N; k++) {
         rvcp_ctx *c = k == 0 ? ctx : ctx->subs[k - 1];
         uint32_t *d_rgba = k == 0 ? ctx->d_pack_rgba : ctx->shard_rgba[k - 1];
@@ -1552,21 +1534,10 @@ static int impl_render(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32
         return fail(ctx, RVCP_E_INVALID, "invalid frame size");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t npx = (size_t)width * height;
-    if (ctx->cap_rgba < npx) {
-        (void)hipFree(ctx->d_rgba);
-        ctx->d_rgba = nullptr;
-        ctx->cap_rgba = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_rgba, npx * 4));
-        ctx->cap_rgba = npx;
-    }
-    if (out_linear_rgb && ctx->cap_lin < npx) {
-        (void)hipFree(ctx->d_lin);
-        ctx->d_lin = nullptr;
-        ctx->cap_lin = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_lin, npx * 12));
-        ctx->cap_lin = npx;
-    }
     int rc;
+    if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, npx, 4)) != RVCP_OK) return rc;
+    if (out_linear_rgb && (rc = grow(ctx, (void **)&ctx->d_lin, &ctx->cap_lin, npx, 12)) != RVCP_OK)
+        return rc;
     if (ctx->subs.empty()) {
         rc = rvcp_render_shard_async(ctx, push, width, height, 0, 1, ctx->d_rgba,
                                      out_linear_rgb ? ctx->d_lin : nullptr, ctx->stream);
@@ -1590,21 +1561,11 @@ static int impl_mandelbrot(rvcp_ctx_t *ctx, const rvcp_mandelbrot_push_t *push, 
         return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t npx = (size_t)width * height;
-    if (ctx->cap_rgba < npx) {
-        (void)hipFree(ctx->d_rgba);
-        ctx->d_rgba = nullptr;
-        ctx->cap_rgba = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_rgba, npx * 4));
-        ctx->cap_rgba = npx;
-    }
+    int rc;
+    if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, npx, 4)) != RVCP_OK) return rc;
     // the float escape values reuse the linear-RGB staging buffer (npx floats <= 3 npx)
-    if (out_value && ctx->cap_lin < npx) {
-        (void)hipFree(ctx->d_lin);
-        ctx->d_lin = nullptr;
-        ctx->cap_lin = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_lin, npx * 12));
-        ctx->cap_lin = npx;
-    }
+    if (out_value && (rc = grow(ctx, (void **)&ctx->d_lin, &ctx->cap_lin, npx, 12)) != RVCP_OK)
+        return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     if (rvcp_launch_mandelbrot(push->position[0], push->position[1], push->scale, width, height,
                                ctx->d_unorm, ctx->d_rgba, out_value ? ctx->d_lin : nullptr,
@@ -1726,17 +1687,6 @@ static int tonemap_tail(rvcp_ctx_t *ctx, const char *step, const void *d_lin, si
     return RVCP_OK;
 }
 
-static int grow(rvcp_ctx_t *ctx, void **buf, size_t *cap, size_t n, size_t elem)
-{
-    if (*cap >= n) return RVCP_OK;
-    (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    HIP_TRY(ctx, hipMalloc(buf, n * elem));
-    *cap = n;
-    return RVCP_OK;
-}
-
 // ---- G-buffer and denoiser ---------------------------------------------
 
 static int impl_render_gbuffer_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push,
@@ -1757,21 +1707,12 @@ static int impl_render_gbuffer_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t
                     "shader's miss test t_max + 1, :287, :424)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    // the fields the primary ray and its scan read (render_frames fills the same ones)
     FrameArgs A;
     std::memset(&A, 0, sizeof(A));
-    camera_constants(*push, width, height, A);
-    A.width = width;
-    A.height = height;
+    primary_frame_args(ctx, *push, width, height, A);
     A.shard_index = 0;
     A.shard_count = 1;
     A.n_pixels = width * height;
-    A.n_faces = ctx->n_faces;
-    A.accel = (ctx->cfg.accel == RVCP_ACCEL_BVH && ctx->n_faces > 0) ? RVCP_ACCEL_BVH : RVCP_ACCEL_NONE;
-    A.bvh_root = ctx->bvh_root;
-    A.bvh_n4 = ctx->bvh_n4;
-    A.bvh_slots = ctx->bvh_slots;
-    A.bvh_prefix = A.accel == RVCP_ACCEL_BVH ? ctx->bvh_prefix : 0u;
     if (rvcp_launch_gbuffer(&A, ctx->d_tri, ctx->d_shade, ctx->d_bvh_nodes, ctx->d_bvh_tris,
                             d_gbuffer, s) != 0)
         return fail(ctx, RVCP_E_HIP, std::string("G-buffer launch failed: ") +
@@ -2743,14 +2684,9 @@ static int impl_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pus
     if ((rc = grow(ctx, (void **)&ctx->d_rgba, &ctx->cap_rgba, npx, 4)) != RVCP_OK) return rc;
     if ((rc = grow(ctx, &ctx->d_gbuf, &ctx->cap_gbuf, npx, sizeof(rvcp_gbuffer_texel_t))) != RVCP_OK)
         return rc;
-    if (ctx->cap_dn_io < npx) {
-        dev_free(ctx->d_dn_in);
-        dev_free(ctx->d_dn_out);
-        ctx->cap_dn_io = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_dn_in, npx * 12));
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_dn_out, npx * 12));
-        ctx->cap_dn_io = npx;
-    }
+    if ((rc = grow(ctx, (void **)&ctx->d_dn_in, &ctx->cap_dn_in, npx, 12)) != RVCP_OK ||
+        (rc = grow(ctx, (void **)&ctx->d_dn_out, &ctx->cap_dn_out, npx, 12)) != RVCP_OK)
+        return rc;
     ChainFrame F;               // (stateless: no history, no resolve)
     F.push = push;
     F.width = width;

@@ -13,6 +13,13 @@ using __hip_internal::uint32_t;
 using __hip_internal::uint64_t;
 #endif
 
+// functions the host and the kernels share: qualified under hipcc / hipRTC, plain elsewhere
+#if defined(__HIPCC__) || defined(__HIPCC_RTC__)
+#define RVCP_HOST_DEVICE __host__ __device__
+#else
+#define RVCP_HOST_DEVICE
+#endif
+
 namespace rvcp {
 
 // Wave width on CDNA4.
@@ -32,6 +39,23 @@ constexpr uint32_t kChunk = 64;
 // Small frames: the grid is sized so that a wave starts with at least kMinStatic pixels, and
 // the pixels are spread over all those waves (more waves per SIMD to hide latency).
 constexpr uint32_t kMinStatic = 8;
+// Static chunks: full 64-pixel waves (fewest wave-instructions for the work) unless that
+// leaves fewer than two waves per SIMD, in which case the pixels are spread over up to two
+// waves per SIMD, at least kMinStatic each (latency hiding matters more for tiny frames).
+// Returns the waves that get a static chunk and its size.  One definition for the host's frame
+// plan (rvcp_frame_plan.cpp, also built without HIP) and the kernels.
+RVCP_HOST_DEVICE inline void static_split(uint32_t n, uint32_t grid_waves, uint32_t n_simds,
+                                          uint32_t &waves, uint32_t &chunk) {
+    uint32_t w = (n + kChunk - 1) / kChunk;
+    const uint32_t spread = (n + kMinStatic - 1) / kMinStatic;
+    const uint32_t floor_w = spread < 2u * n_simds ? spread : 2u * n_simds;
+    if (w < floor_w) w = floor_w;
+    if (w > grid_waves) w = grid_waves;
+    if (w < 1u) w = 1u;
+    uint32_t c = (n + w - 1) / w;
+    chunk = c < 1u ? 1u : (c > kChunk ? kChunk : c);
+    waves = w;
+}
 // Frame-queue grabs after a wave's static chunk: what the wave consumes in kChunkWindow
 // s_memrealtime ticks (100 MHz), between kMinChunk and kDynChunk pixels (queue_take,
 // DESIGN.md §4.1).
@@ -443,7 +467,5 @@ int rvcp_launch_assemble(const uint32_t *gathered, uint32_t slot_rows, uint32_t 
 int rvcp_launch_fill(uint32_t *out_rgba, float *out_lin, uint32_t n_pixels, uint32_t rgba,
                      void *stream);
 int rvcp_games101_occupancy(int variant, int *blocks_per_cu);
-void rvcp_static_split(uint32_t n, uint32_t grid_waves, uint32_t n_simds, uint32_t *waves,
-                       uint32_t *chunk);
 }
 #endif  // __HIPCC_RTC__

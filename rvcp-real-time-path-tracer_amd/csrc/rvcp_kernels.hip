@@ -1144,22 +1144,6 @@ __device__ __forceinline__ bool att_stop(const FrameArgs &A, f3 att) {          
 }
 
 
-// Static chunks: full 64-pixel waves (fewest wave-instructions for the work) unless that
-// leaves fewer than two waves per SIMD, in which case the pixels are spread over up to two
-// waves per SIMD, at least kMinStatic each (latency hiding matters more for tiny frames).  Returns the waves that get a static chunk and its size.
-__host__ __device__ inline void static_split(uint32_t n, uint32_t grid_waves, uint32_t n_simds,
-                                             uint32_t &waves, uint32_t &chunk) {
-    uint32_t w = (n + kChunk - 1) / kChunk;
-    const uint32_t spread = (n + kMinStatic - 1) / kMinStatic;
-    const uint32_t floor_w = spread < 2u * n_simds ? spread : 2u * n_simds;
-    if (w < floor_w) w = floor_w;
-    if (w > grid_waves) w = grid_waves;
-    if (w < 1u) w = 1u;
-    uint32_t c = (n + w - 1) / w;
-    chunk = c < 1u ? 1u : (c > kChunk ? kChunk : c);
-    waves = w;
-}
-
 // Wave-uniform frame-queue state: [next, end) pixels owned by this wave; the pixels it has
 // handed to its lanes since t0 (s_memrealtime ticks) set the size of its next grab.
 struct Queue {
@@ -3618,12 +3602,6 @@ extern "C" int rvcp_launch_tonemap(const float *lin, uint32_t n, const float *ga
     hipLaunchKernelGGL(rvcp::tonemap_kernel, dim3(tb), dim3(rvcp::kToneBlock), 0, (hipStream_t)stream,
                        lin, n, gamma_t, out_rgba);
     return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-extern "C" void rvcp_static_split(uint32_t n, uint32_t grid_waves, uint32_t n_simds,
-                                  uint32_t *waves, uint32_t *chunk)
-{
-    rvcp::static_split(n, grid_waves, n_simds, *waves, *chunk);
 }
 
 extern "C" int rvcp_launch_assemble(const uint32_t *gathered, uint32_t slot_rows, uint32_t width,
