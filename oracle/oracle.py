@@ -58,6 +58,17 @@ def lib(o3: bool = False):
         L.rvcp_oracle_gamma_threshold_rule.argtypes = [ctypes.c_int, ctypes.c_int]
         L.rvcp_oracle_gamma_threshold_rule.restype = ctypes.c_float
         L.rvcp_oracle_render.restype = ctypes.c_int
+        # the array forms (tests/devmath_ref.py)
+        sz = ctypes.c_size_t
+        L.rvcp_oracle_sinf_array.argtypes = [P, P, sz]
+        L.rvcp_oracle_rand_of_array.argtypes = [P, P, sz]
+        L.rvcp_oracle_gamma_u8_array.argtypes = [P, P, sz, ctypes.c_int]
+        L.rvcp_oracle_rand_sequence_from.argtypes = [P, P, sz, ctypes.c_int, P]
+        L.rvcp_oracle_rand_sequence_array.argtypes = [P, sz, ctypes.c_int, P]
+        L.rvcp_oracle_intersect_array.argtypes = [P, P, P, sz, P, P]
+        for f in ("sinf_array", "rand_of_array", "gamma_u8_array", "rand_sequence_from",
+                  "rand_sequence_array", "intersect_array"):
+            getattr(L, "rvcp_oracle_" + f).restype = None
         L.rvcp_oracle_mandelbrot.argtypes = [P, u32, u32, ctypes.c_int, P, P]
         L.rvcp_oracle_mandelbrot.restype = ctypes.c_int
         _libs[path] = L
@@ -99,6 +110,67 @@ def intersect(ray, tri):
     out = np.zeros(3, dtype=np.float32)
     hit = lib().rvcp_oracle_intersect(_ptr(ray), _ptr(tri), _ptr(out))
     return bool(hit), out
+
+
+def _f32(a, shape=None):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    return a if shape is None else a.reshape(shape)
+
+
+def sinf_array(x) -> np.ndarray:
+    """sinf over a float32 array."""
+    x = _f32(x)
+    out = np.empty_like(x)
+    lib().rvcp_oracle_sinf_array(_ptr(x), _ptr(out), x.size)
+    return out
+
+
+def rand_of_array(x) -> np.ndarray:
+    """_rand(x) = fract(sin(x) * 43758.5453) over a float32 array."""
+    x = _f32(x)
+    out = np.empty_like(x)
+    lib().rvcp_oracle_rand_of_array(_ptr(x), _ptr(out), x.size)
+    return out
+
+
+def gamma_u8_array(c, unorm_rule: int = 0) -> np.ndarray:
+    """gamma_u8 over a float32 array (uint8 out)."""
+    c = _f32(c)
+    out = np.empty(c.shape, dtype=np.uint8)
+    lib().rvcp_oracle_gamma_u8_array(_ptr(c), _ptr(out), c.size, int(unorm_rule))
+    return out
+
+
+def rand_sequence_from(seed, index, n: int) -> np.ndarray:
+    """n rand() draws of each stream j from state (seed[j], index[j]): [m, n + 1] float32, the
+    last column the index after the draws."""
+    seed, index = _f32(seed).ravel(), _f32(index).ravel()
+    assert seed.size == index.size
+    out = np.zeros((seed.size, n + 1), dtype=np.float32)
+    lib().rvcp_oracle_rand_sequence_from(_ptr(seed), _ptr(index), seed.size, int(n), _ptr(out))
+    return out
+
+
+def rand_sequence_array(tuv, n: int) -> np.ndarray:
+    """rand_sequence for each (time, u, v) row: [m, n + 1] float32, column 0 the seed."""
+    tuv = _f32(tuv, (-1, 3))
+    out = np.zeros((len(tuv), n + 1), dtype=np.float32)
+    lib().rvcp_oracle_rand_sequence_array(_ptr(tuv), len(tuv), int(n), _ptr(out))
+    return out
+
+
+def intersect_array(rays, tris, normals=None):
+    """intersect over m pairs under the scan's keep rule (rays[:, 7] is the current nearest
+    hit's time): rays [m, 8], tris [m, 9], normals [m, 9] or None for (0, 1, 0).  Returns
+    (hit [m] bool, out [m, 12] float32 = t, b1, b2, pos, normal, den, n1, n2)."""
+    rays, tris = _f32(rays, (-1, 8)), _f32(tris, (-1, 9))
+    normals = None if normals is None else _f32(normals, (-1, 9))
+    assert len(rays) == len(tris) and (normals is None or len(normals) == len(rays))
+    hit = np.zeros(len(rays), dtype=np.int32)
+    out = np.zeros((len(rays), 12), dtype=np.float32)
+    lib().rvcp_oracle_intersect_array(_ptr(rays), _ptr(tris), _ptr(normals), len(rays),
+                                      _ptr(hit), _ptr(out))
+    return hit.astype(bool), out
 
 
 def sample_ray(push, W, H, x, y) -> np.ndarray:

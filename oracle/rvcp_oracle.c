@@ -768,3 +768,86 @@ void rvcp_oracle_sample_ray(const rvcp_push_constant_t *push, uint32_t W, uint32
     out[3] = r.d.x; out[4] = r.d.y; out[5] = r.d.z;
     out[6] = r.t_min; out[7] = r.t_max;
 }
+
+/* ------------------------------------------------------------------------------------- */
+/* Array forms of the helpers above (tests/devmath_ref.py): the same scalar code over n    */
+/* records, so a case of 2^24 inputs costs milliseconds, not a Python loop.                */
+/* ------------------------------------------------------------------------------------- */
+void rvcp_oracle_sinf_array(const float *x, float *out, size_t n)
+{
+    for (size_t i = 0; i < n; i++) out[i] = rvcp_oracle_sinf(x[i]);
+}
+
+/* out[i] = _rand(x[i]) = fract(sin(x[i]) * 43758.5453) */
+void rvcp_oracle_rand_of_array(const float *x, float *out, size_t n)
+{
+    for (size_t i = 0; i < n; i++) out[i] = rand_of(x[i]);
+}
+
+void rvcp_oracle_gamma_u8_array(const float *c, uint8_t *out, size_t n, int rule)
+{
+    for (size_t i = 0; i < n; i++) out[i] = rvcp_oracle_gamma_u8_rule(c[i], rule);
+}
+
+/* m streams of n rand() values each from a given state: stream j starts at (seed[j], index[j]);
+ * out[j * (n + 1) + k] = draw k, out[j * (n + 1) + n] = the index after the last draw. */
+void rvcp_oracle_rand_sequence_from(const float *seed, const float *index, size_t m, int n, float *out)
+{
+    for (size_t j = 0; j < m; j++) {
+        rng_t g = { seed[j], index[j] };
+        float *o = out + j * (size_t)(n + 1);
+        for (int k = 0; k < n; k++) o[k] = rand_next(&g);
+        o[n] = g.index;
+    }
+}
+
+/* rvcp_oracle_rand_sequence over m (time, u, v) triples: out[j * (n + 1) ...] as the scalar's. */
+void rvcp_oracle_rand_sequence_array(const float *tuv, size_t m, int n, float *out)
+{
+    for (size_t j = 0; j < m; j++)
+        rvcp_oracle_rand_sequence(tuv[3 * j], tuv[3 * j + 1], tuv[3 * j + 2], n,
+                                  out + j * (size_t)(n + 1));
+}
+
+/* is_intersect_with_face under the keep rule of get_intersection_with_scene, over m (ray,
+ * triangle) pairs.  rays: {o, d, t_min, bt} with bt the current nearest hit's time (the scan's
+ * ray.t_max); tris: 3 positions; normals: 3 vertex normals, or NULL for (0, 1, 0).  hit[j] = 1
+ * iff the shader would replace its nearest hit; out[12 j ...] = {t, b1, b2, pos, normal, den,
+ * n1, n2} (t, pos and normal only on a hit; den = s1.e1, n1 = s1.s and n2 = s2.d always). */
+void rvcp_oracle_intersect_array(const float *rays, const float *tris, const float *normals,
+                                 size_t m, int32_t *hit, float *out)
+{
+    for (size_t j = 0; j < m; j++) {
+        const float *ray = rays + 8 * j, *tri = tris + 9 * j;
+        rvcp_vertex_t v[3];
+        memset(v, 0, sizeof v);
+        for (int k = 0; k < 3; k++) {
+            for (int c = 0; c < 3; c++) {
+                v[k].position[c] = tri[3 * k + c];
+                v[k].normal[c] = normals ? normals[9 * j + 3 * k + c] : (c == 1 ? 1.0f : 0.0f);
+            }
+        }
+        rvcp_face_t f = { {0, 1, 2}, 0 };
+        scene_t sc = { NULL, 0, v, 3, &f, 1, NULL, 0, NULL, 0 };
+        ray_t r = { mk(ray[0], ray[1], ray[2]), mk(ray[3], ray[4], ray[5]), ray[6], ray[7] };
+        hit_t h;
+        float *o = out + 12 * j;
+        for (int c = 0; c < 12; c++) o[c] = 0.0f;
+        v3 e1 = sub(ld3(v[1].position), ld3(v[0].position));
+        v3 e2 = sub(ld3(v[2].position), ld3(v[0].position));
+        v3 s = sub(r.o, ld3(v[0].position));
+        v3 s1 = cross(r.d, e2), s2 = cross(s, e1);
+        float den = dot(s1, e1), f_ = 1.0f / den;
+        o[1] = f_ * dot(s1, s);
+        o[2] = f_ * dot(s2, r.d);
+        o[9] = den;
+        o[10] = dot(s1, s);
+        o[11] = dot(s2, r.d);
+        hit[j] = is_intersect_with_face(&sc, &r, &f, &h) && h.time <= r.t_max;
+        if (hit[j]) {
+            o[0] = h.time;
+            o[3] = h.pos.x; o[4] = h.pos.y; o[5] = h.pos.z;
+            o[6] = h.normal.x; o[7] = h.normal.y; o[8] = h.normal.z;
+        }
+    }
+}
