@@ -5,10 +5,13 @@
  * a binary PPM and prints one JSON line of stats per frame.
  *
  *   make -C examples            # gcc, links ../rvcp-real-time-path-tracer_amd/csrc/build/librvcp.so
- *   examples/build/rvcp_render scene.rvcpscn W H SPP TIME FRAMES out.ppm [--cosine]
+ *   examples/build/rvcp_render scene.rvcpscn W H SPP TIME FRAMES out.ppm [--cosine | --adaptive]
  *
  * --cosine: trace with the cosine-weighted bounce (rvcp_set_sampling) instead of
  * the shader's uniform one: less noise per sample, frames no longer the reference's bit for bit.
+ * --adaptive: every frame through SVGF (rvcp_render_svgf) with adaptive sampling
+ * (rvcp_set_adaptive) at a budget of SPP samples per pixel: the samples go where
+ * the previous frame's variance says the error is; `samples` is what the frame really traced.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -26,8 +29,10 @@ static int die(rvcp_ctx_t *ctx, const char *what, int rc)
 int main(int argc, char **argv)
 {
     const int cosine = argc == 9 && strcmp(argv[8], "--cosine") == 0;
-    if (argc != 8 && !cosine) {
-        fprintf(stderr, "usage: %s scene.rvcpscn W H SPP TIME FRAMES out.ppm [--cosine]\n", argv[0]);
+    const int adaptive = argc == 9 && strcmp(argv[8], "--adaptive") == 0;
+    if (argc != 8 && !cosine && !adaptive) {
+        fprintf(stderr, "usage: %s scene.rvcpscn W H SPP TIME FRAMES out.ppm [--cosine | --adaptive]\n",
+                argv[0]);
         return 2;
     }
     const uint32_t W = (uint32_t)strtoul(argv[2], NULL, 10);
@@ -53,6 +58,15 @@ int main(int argc, char **argv)
         rc = rvcp_set_sampling(ctx, RVCP_SAMPLING_COSINE);
         if (rc) return die(ctx, "rvcp_set_sampling", rc);
     }
+    if (adaptive) {                           /* no counterpart in the reference */
+        rvcp_adaptive_params_t ap;
+        rc = rvcp_adaptive_params_default(&ap);
+        if (rc) return die(ctx, "rvcp_adaptive_params_default", rc);
+        ap.mean_spp = (float)spp;             /* the budget: SPP samples per pixel on average */
+        if (ap.spp_max < spp) ap.spp_max = spp;
+        rc = rvcp_set_adaptive(ctx, &ap);
+        if (rc) return die(ctx, "rvcp_set_adaptive", rc);
+    }
 
     rvcp_push_constant_t push;
     memset(&push, 0, sizeof(push));
@@ -64,8 +78,10 @@ int main(int argc, char **argv)
     if (!rgba) return die(ctx, "malloc", -1);
     for (int f = 0; f < frames; f++) {
         rvcp_stats_t st;
-        rc = rvcp_render(ctx, &push, W, H, rgba, NULL, &st);  /* push constants + dispatch */
-        if (rc) { free(rgba); return die(ctx, "rvcp_render", rc); }
+        rc = adaptive ? rvcp_render_svgf(ctx, &push, W, H, NULL, NULL, 0, rgba, NULL, NULL, NULL, &st,
+                                         NULL, NULL)
+                      : rvcp_render(ctx, &push, W, H, rgba, NULL, &st);  /* push constants + dispatch */
+        if (rc) { free(rgba); return die(ctx, adaptive ? "rvcp_render_svgf" : "rvcp_render", rc); }
         printf("{\"frame\": %d, \"kernel_ms\": %.4f, \"traversals\": %llu, \"samples\": %llu}\n",
                f, st.kernel_ms, (unsigned long long)st.traversals,
                (unsigned long long)st.samples);

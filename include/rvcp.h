@@ -346,6 +346,23 @@ typedef struct rvcp_taau_params {
     uint32_t _pad;          /* must be 0 */
 } rvcp_taau_params_t;
 
+/* Adaptive sampling: per-pixel sample counts.  No counterpart in the
+ * reference: its shader gives every pixel the same SPP (ray_tracer_games101_branch.comp:8).
+ * RVCP_SPP_MAP_MAX: the largest count a pixel of a map can get; the pre-pass clamps every word of
+ * a map into 1..RVCP_SPP_MAP_MAX. */
+#define RVCP_SPP_MAP_MAX 256u
+
+/* Parameters of rvcp_spp_plan_async and rvcp_set_adaptive (the rule's definition: DESIGN.md
+ * §4.18). */
+typedef struct rvcp_adaptive_params {
+    uint32_t spp_min;       /* every pixel gets at least this; 1..RVCP_SPP_MAP_MAX */
+    uint32_t spp_max;       /* ... and at most this; spp_min..RVCP_SPP_MAP_MAX */
+    float mean_spp;         /* the frame's budget, samples per pixel; spp_min..spp_max */
+    float weight_cap;       /* priorities are cut off at this relative variance; finite, > 0 */
+    float epsilon;          /* added to the squared luminance; finite, > 0 */
+    uint32_t _pad;          /* must be 0 */
+} rvcp_adaptive_params_t;
+
 /* Layout checks: sizes/offsets the reference's Rust structs and std140/std430 blocks imply. */
 #ifdef __cplusplus
 #define RVCP_STATIC_ASSERT(c, m) static_assert(c, m)
@@ -397,6 +414,12 @@ RVCP_STATIC_ASSERT(sizeof(rvcp_taau_params_t) == 16, "TAA upsampling params are 
 RVCP_STATIC_ASSERT(offsetof(rvcp_taau_params_t, init_weight) == 4, "TaauParams.init_weight @4");
 RVCP_STATIC_ASSERT(offsetof(rvcp_taau_params_t, clamp) == 8, "TaauParams.clamp @8");
 RVCP_STATIC_ASSERT(offsetof(rvcp_taau_params_t, _pad) == 12, "TaauParams._pad @12");
+RVCP_STATIC_ASSERT(sizeof(rvcp_adaptive_params_t) == 24, "adaptive params are 24 B");
+RVCP_STATIC_ASSERT(offsetof(rvcp_adaptive_params_t, spp_max) == 4, "AdaptiveParams.spp_max @4");
+RVCP_STATIC_ASSERT(offsetof(rvcp_adaptive_params_t, mean_spp) == 8, "AdaptiveParams.mean_spp @8");
+RVCP_STATIC_ASSERT(offsetof(rvcp_adaptive_params_t, weight_cap) == 12, "AdaptiveParams.weight_cap @12");
+RVCP_STATIC_ASSERT(offsetof(rvcp_adaptive_params_t, epsilon) == 16, "AdaptiveParams.epsilon @16");
+RVCP_STATIC_ASSERT(offsetof(rvcp_adaptive_params_t, _pad) == 20, "AdaptiveParams._pad @20");
 
 typedef struct rvcp_ctx rvcp_ctx_t;
 
@@ -1068,6 +1091,78 @@ int rvcp_set_sampling(rvcp_ctx_t *ctx, int32_t sampling);
 
 /* *sampling = the context's bounce sampling. */
 int rvcp_get_sampling(rvcp_ctx_t *ctx, int32_t *sampling);
+
+/* ---------------------------------------------------------------------------------------
+ * Adaptive sampling (opt-in): frames traced with a per-pixel sample count, a
+ * plan step that makes the counts from a filtered frame's variance, and a switch that closes
+ * the loop inside rvcp_render_svgf.
+ * ------------------------------------------------------------------------------------- */
+
+/* rvcp_render_async with a per-pixel sample count: d_spp_map holds width x height uint32_t in
+ * device memory, row-major, and pixel p is traced with s_p = min(max(map[p], 1),
+ * RVCP_SPP_MAP_MAX) samples of its own RNG stream -- bit for bit the pixel of a frame rendered
+ * with cfg.spp = s_p (and of the oracle's, with RVCP_SAMPLING_UNIFORM); a uniform map of s is
+ * rvcp_render_async at cfg.spp = s.  cfg.spp is not read; spp_hint (1..RVCP_SPP_MAP_MAX) stands
+ * in for it where the schedule and the grid are chosen and changes no bit of the frame.  The
+ * map is read by the frame's first kernel: it must stay unchanged until rvcp_wait.  The frame
+ * is the context's pending frame (rvcp_wait / rvcp_sync_stats: samples = sum of s_p, traversals
+ * = traversals_executed + sum of (s_p - 1)) and is ordered like rvcp_render_async's; the
+ * context's bounce sampling holds (rvcp_set_sampling).  Scene-specialised kernels are compiled
+ * for map renders by the first one (cached per bounce sampling, in the process and on disk).
+ * RVCP_E_INVALID: a null or zero argument, a hint outside 1..RVCP_SPP_MAP_MAX, W*H >= 2^31, a
+ * frame pending.  RVCP_E_NO_SCENE before an upload.  RVCP_E_UNSUPPORTED: a
+ * RVCP_INTEGRATOR_LEGACY context, n_gpus > 1, a resolved schedule of 1 or 2 (the map is read by
+ * the pre-pass: schedules 3-6, 10 and the BVH path kernel). */
+int rvcp_render_spp_map_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push,
+                              uint32_t width, uint32_t height,
+                              const void *d_spp_map /* W*H uint32_t */, uint32_t spp_hint,
+                              void *d_rgba8, void *d_linear_rgb, void *stream);
+
+/* The defaults: the best row on average of tools/adaptive_sweep.py. */
+int rvcp_adaptive_params_default(rvcp_adaptive_params_t *params);
+
+/* The plan step (stateless, on the caller's buffers): the map of the next frame from a frame's
+ * variance d_variance (W*H float), the colour it belongs to d_linear (W*H*3 float, in the same
+ * domain), its history lengths d_len (W*H uint32_t, or NULL: 1 everywhere) and its G-buffer.
+ * Per pixel q = floor(2^20 min(w, weight_cap) / weight_cap) with w = v / (lum(c)^2 + epsilon) /
+ * n, every operation a float32 operation rounded once, and q = 0 for a pixel that is not
+ * filterable (a miss, emissive), reads a non-finite float, has v not > 0 or n = 0.  With S the
+ * integer sum of q, B = floor(mean_spp W H) and E = B - spp_min W H: s = spp_min + min(E q / S,
+ * spp_max - spp_min) in unsigned 64-bit integers, and with S = 0 every pixel gets
+ * min(spp_min + E / (W H), spp_max).  So spp_min <= s <= spp_max and sum(s) <= B always; what the
+ * spp_max clamp cuts off is not handed to other pixels.  params NULL: the defaults.  Ordered
+ * behind a render pending on this context and behind the context's previous plan step; the
+ * output may overlap no input.  RVCP_E_INVALID: a null or zero argument, W*H >= 2^31, parameters
+ * out of range (NaN included), _pad != 0, an overlap. */
+int rvcp_spp_plan_async(rvcp_ctx_t *ctx, const void *d_variance /* W*H float */,
+                        const void *d_linear /* W*H*3 float */, const void *d_len /* W*H u32, or NULL: 1 */,
+                        const void *d_gbuffer, uint32_t width, uint32_t height,
+                        const rvcp_adaptive_params_t *params, void *d_spp_map_out, void *stream);
+
+/* Wait for the plan step: its time and the sum of the map it wrote (either may be NULL). */
+int rvcp_spp_plan_wait(rvcp_ctx_t *ctx, float *plan_ms, uint64_t *planned_samples);
+
+/* The switch (off by default; params NULL: off).  While it is on, rvcp_render_svgf -- and only
+ * it -- traces its raw frame with rvcp_render_spp_map_async through a map the context keeps, and
+ * after the filter plans the next frame's map with rvcp_spp_plan_async from the frame's own
+ * filtered colour (irradiance when demodulating), variance, history lengths and G-buffer, at the
+ * traced size; `stats` are the map render's.  The map is in the previous frame's pixel grid and
+ * is not reprojected.  Wherever the SVGF history is dropped (the first call, a size change, an
+ * upload, rvcp_svgf_reset, a failed call, the switches that drop it) the map is dropped with it
+ * and the frame is traced through the uniform map of min(max(floor(mean_spp), spp_min),
+ * spp_max).  Turning the switch on or off or changing the parameters drops the map, not the SVGF
+ * history.  RVCP_E_UNSUPPORTED: a RVCP_INTEGRATOR_LEGACY or n_gpus > 1 context.  RVCP_E_INVALID:
+ * parameters out of range (NaN included), _pad != 0, a frame pending. */
+int rvcp_set_adaptive(rvcp_ctx_t *ctx, const rvcp_adaptive_params_t *params /* NULL: off */);
+
+/* *on = the switch, *out_params = its parameters (the defaults while it is off); either may be
+ * NULL. */
+int rvcp_get_adaptive(rvcp_ctx_t *ctx, int *on, rvcp_adaptive_params_t *out_params);
+
+/* The map the last frame of rvcp_render_svgf was traced with under the switch: out_map (host,
+ * *out_width x *out_height uint32_t; may be NULL to ask for the size alone).  RVCP_E_INVALID
+ * before any such frame. */
+int rvcp_adaptive_last_map(rvcp_ctx_t *ctx, uint32_t *out_map, uint32_t *out_width, uint32_t *out_height);
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,11 @@ TAA_JITTER_PERIOD = 16
 TAAU_PARAMS_DTYPE = np.dtype([("max_weight", "<f4"), ("init_weight", "<f4"), ("clamp", "<u4"),
                               ("_pad", "<u4")])
 assert TAAU_PARAMS_DTYPE.itemsize == 16
+# rvcp_adaptive_params_t (adaptive sampling: the plan step and the switch)
+ADAPTIVE_PARAMS_DTYPE = np.dtype([("spp_min", "<u4"), ("spp_max", "<u4"), ("mean_spp", "<f4"),
+                                  ("weight_cap", "<f4"), ("epsilon", "<f4"), ("_pad", "<u4")])
+assert ADAPTIVE_PARAMS_DTYPE.itemsize == 24
+SPP_MAP_MAX = 256               # RVCP_SPP_MAP_MAX
 # rvcp_stats_t.kernel_variant -> the dominant kernel's name as rocprofv3 reports it
 KERNEL_NAMES = {1: "games101_kernel", 2: "games101_dual_kernel", 3: "games101_path_kernel<5>",
                 4: "games101_tiled_kernel", 5: "games101_tiled_single_kernel",
@@ -105,7 +110,10 @@ EXPORTED = ["rvcp_version", "rvcp_config_default", "rvcp_config_default_for", "r
             "rvcp_taa_reset",
             "rvcp_taau_params_default", "rvcp_taa_upsample_async", "rvcp_taau_wait",
             "rvcp_set_taa_upsample", "rvcp_get_taa_upsample",
-            "rvcp_set_sampling", "rvcp_get_sampling"]
+            "rvcp_set_sampling", "rvcp_get_sampling",
+            "rvcp_render_spp_map_async", "rvcp_adaptive_params_default", "rvcp_spp_plan_async",
+            "rvcp_spp_plan_wait", "rvcp_set_adaptive", "rvcp_get_adaptive",
+            "rvcp_adaptive_last_map"]
 
 
 # Integrator mode 2 (ray_tracer.comp ray_trace): its own #defines (ray_tracer.comp:5-13).
@@ -187,6 +195,18 @@ def make_taau_params(**overrides) -> np.ndarray:
     rc = load().rvcp_taau_params_default(ptr(p))
     if rc != RVCP_OK:
         raise RvcpError(rc, "rvcp_taau_params_default failed")
+    for k, v in overrides.items():
+        p[k] = v
+    return p
+
+
+def make_adaptive_params(**overrides) -> np.ndarray:
+    """rvcp_adaptive_params_t with the library's defaults (rvcp_adaptive_params_default),
+    overridden by the keyword arguments."""
+    p = np.zeros((), dtype=ADAPTIVE_PARAMS_DTYPE)
+    rc = load().rvcp_adaptive_params_default(ptr(p))
+    if rc != RVCP_OK:
+        raise RvcpError(rc, "rvcp_adaptive_params_default failed")
     for k, v in overrides.items():
         p[k] = v
     return p
@@ -333,6 +353,13 @@ def load():
     L.rvcp_get_taa_upsample.argtypes = [P, P]
     L.rvcp_set_sampling.argtypes = [P, ctypes.c_int32]
     L.rvcp_get_sampling.argtypes = [P, P]
+    L.rvcp_render_spp_map_async.argtypes = [P, P, u32, u32, P, u32, P, P, P]
+    L.rvcp_adaptive_params_default.argtypes = [P]
+    L.rvcp_spp_plan_async.argtypes = [P, P, P, P, P, u32, u32, P, P, P]
+    L.rvcp_spp_plan_wait.argtypes = [P, P, P]
+    L.rvcp_set_adaptive.argtypes = [P, P]
+    L.rvcp_get_adaptive.argtypes = [P, P, P]
+    L.rvcp_adaptive_last_map.argtypes = [P, P, P, P]
     for name in ("rvcp_config_default", "rvcp_config_default_for", "rvcp_create", "rvcp_destroy", "rvcp_upload_scene",
                  "rvcp_render", "rvcp_render_shard_async", "rvcp_sync_stats",
                  "rvcp_assemble_frame_async", "rvcp_upload_scene_file", "rvcp_mandelbrot",
@@ -352,7 +379,9 @@ def load():
                  "rvcp_taa_resolve_async", "rvcp_taa_wait", "rvcp_set_taa", "rvcp_get_taa",
                  "rvcp_taa_reset", "rvcp_taau_params_default", "rvcp_taa_upsample_async",
                  "rvcp_taau_wait", "rvcp_set_taa_upsample", "rvcp_get_taa_upsample",
-                 "rvcp_set_sampling", "rvcp_get_sampling"):
+                 "rvcp_set_sampling", "rvcp_get_sampling", "rvcp_render_spp_map_async",
+                 "rvcp_adaptive_params_default", "rvcp_spp_plan_async", "rvcp_spp_plan_wait",
+                 "rvcp_set_adaptive", "rvcp_get_adaptive", "rvcp_adaptive_last_map"):
         getattr(L, name).restype = ctypes.c_int
     if L.rvcp_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI revision {L.rvcp_abi_version()}, this binding "

@@ -70,7 +70,8 @@ struct Stage {
 };
 
 enum StageId {
-    ST_DENOISE, ST_TEMPORAL, ST_SVGF_ACC, ST_SVGF_FLT, ST_DEMOD, ST_REMOD, ST_TAA, ST_TAAU, N_STAGES
+    ST_DENOISE, ST_TEMPORAL, ST_SVGF_ACC, ST_SVGF_FLT, ST_DEMOD, ST_REMOD, ST_TAA, ST_TAAU, ST_PLAN,
+    N_STAGES
 };
 
 constexpr uint32_t stage_bit(StageId id) { return 1u << id; }
@@ -78,11 +79,12 @@ constexpr uint32_t stage_bit(StageId id) { return 1u << id; }
 // The steps each step is ordered behind, besides a render pending on another stream: the denoiser,
 // the temporal step, the TAA resolve and the upsampling step reuse what their own previous call
 // wrote (intermediates, or the history); the SVGF and the albedo steps share buffers from call to
-// call, so each waits for the context's previous SVGF accumulation and filter.  (In StageId order.)
+// call, so each waits for the context's previous SVGF accumulation and filter; the plan step of
+// adaptive sampling reuses its own priority plane and sums.  (In StageId order.)
 constexpr uint32_t kSvgfSteps = stage_bit(ST_SVGF_ACC) | stage_bit(ST_SVGF_FLT);
 constexpr uint32_t kStageBehind[N_STAGES] = {
     stage_bit(ST_DENOISE), stage_bit(ST_TEMPORAL), kSvgfSteps, kSvgfSteps, kSvgfSteps, kSvgfSteps,
-    stage_bit(ST_TAA), stage_bit(ST_TAAU)};
+    stage_bit(ST_TAA), stage_bit(ST_TAAU), stage_bit(ST_PLAN)};
 
 // A history a stateful chain keeps from call to call, ping-ponging between slots `slot` (the
 // previous frame) and slot ^ 1
@@ -138,6 +140,10 @@ struct rvcp_ctx {
     // the same for the cosine builds of the games101 kernels (rvcp_kernels_cosine.hip)
     int grid_capacity_cos[kMaxVariant + 1] = {};
     int bvh_capacity_cos = 0;
+    // ... and for the map builds of the pre-pass family (rvcp_kernels_map.hip,
+    // rvcp_kernels_cosine_map.hip), by bounce sampling: schedules 3-6 and 10
+    int grid_capacity_map[2][kMaxVariant + 1] = {};
+    int bvh_capacity_map[2] = {};
     uint32_t n_simds = 1024;
 
     // scene (device)
@@ -175,6 +181,11 @@ struct rvcp_ctx {
     int32_t jit_sampling = RVCP_SAMPLING_UNIFORM;
     std::vector<TriRecord> jit_tri;
     bool jit_bvh = false;
+    // the scene's module for map renders (rvcp_render_spp_map_async, -DRVCP_SPP_MAP=1), compiled
+    // by the first one for the bounce sampling it runs with: jit_map_sampling is the mode jit_map
+    // was asked for, -1 before any (and after an upload)
+    std::shared_ptr<JitKernels> jit_map;
+    int32_t jit_map_sampling = -1;
     float light_total = 0.0f, light_pdf = 0.0f;
     bool has_scene = false;
 
@@ -234,6 +245,23 @@ struct rvcp_ctx {
     size_t cap_sv = 0;
     History sv_hist;
 
+    // adaptive sampling.  The plan step (rvcp_spp_plan_async) keeps its
+    // priority plane and its two 64-bit sums (sum of priorities, sum of the map) here.  The switch
+    // of rvcp_set_adaptive and its parameters; while it is set rvcp_render_svgf traces through
+    // d_ad_map[ad_slot] -- the plan of its previous frame while ad_valid (and the SVGF history
+    // continues), else a uniform map -- and plans the next frame into the other slot.  ad_last:
+    // the slot the last such frame was traced through (-1: none yet), ad_w x ad_h its size.
+    uint32_t *d_ad_q = nullptr;
+    size_t cap_ad_q = 0;
+    unsigned long long *d_ad_sums = nullptr;
+    bool adaptive = false;
+    rvcp_adaptive_params_t ad_params = {};
+    uint32_t *d_ad_map[2] = {nullptr, nullptr};
+    size_t cap_ad_map[2] = {0, 0};
+    uint32_t ad_slot = 0, ad_w = 0, ad_h = 0;
+    int ad_last = -1;
+    bool ad_valid = false;
+
     // albedo demodulation (rvcp_demodulate_async / rvcp_remodulate_async): the
     // scene's albedo table (one float4 per material, made by every upload) and the switch of
     // rvcp_set_demodulation: while it is set rvcp_render_denoised, rvcp_render_temporal and
@@ -289,6 +317,7 @@ struct rvcp_ctx {
     int32_t last_variant = 0;
     uint64_t last_pixels = 0;
     uint32_t last_spp = 0;
+    bool last_map = false;          // the last render was a map render: its counts are the pre-pass's sum
     uint32_t last_shard_index = 0, last_shard_count = 0;   // of the last rvcp_render_shard_async
     uint32_t last_width = 0, last_height = 0;
 
@@ -522,6 +551,8 @@ void free_scene(rvcp_ctx *ctx)
     (void)hipFree(ctx->d_bvh_nodes); ctx->d_bvh_nodes = nullptr;
     (void)hipFree(ctx->d_bvh_tris); ctx->d_bvh_tris = nullptr;
     ctx->jit.reset();
+    ctx->jit_map.reset();
+    ctx->jit_map_sampling = -1;
     ctx->has_scene = false;
 }
 
@@ -785,6 +816,12 @@ static int impl_create(const rvcp_config_t *cfg, rvcp_ctx_t **out_ctx)
     ctx->legacy_capacity = capacity(rvcp_legacy_occupancy);
     ctx->bvh_capacity = capacity([](int *n) { return rvcp_games101_occupancy(kOccupancyBvh, n); });
     ctx->bvh_capacity_cos = capacity([](int *n) { return rvcp_games101_occupancy_cosine(kOccupancyBvh, n); });
+    for (int v : {3, 4, 5, 6, 10}) {     // the map builds: the pre-pass schedules only
+        ctx->grid_capacity_map[0][v] = capacity([v](int *n) { return rvcp_games101_occupancy_map(v, n); });
+        ctx->grid_capacity_map[1][v] = capacity([v](int *n) { return rvcp_games101_occupancy_cosine_map(v, n); });
+    }
+    ctx->bvh_capacity_map[0] = capacity([](int *n) { return rvcp_games101_occupancy_map(kOccupancyBvh, n); });
+    ctx->bvh_capacity_map[1] = capacity([](int *n) { return rvcp_games101_occupancy_cosine_map(kOccupancyBvh, n); });
     if (cfg->n_gpus > 1) {   // one sub-context per further GPU (shards 1..N-1)
         for (int i = 1; i < cfg->n_gpus; i++) {
             rvcp_config_t sub_cfg = *cfg;
@@ -859,6 +896,7 @@ static int impl_destroy(rvcp_ctx_t *ctx)
         g_create_error = "rvcp_destroy: a gather (or its communicator's abort) is still stuck "
                          "after the deadline; the context's device memory and streams are leaked";
         new std::shared_ptr<JitKernels>(std::move(ctx->jit));   // never unloaded
+        new std::shared_ptr<JitKernels>(std::move(ctx->jit_map));
         delete ctx;
         return RVCP_E_TIMEOUT;
     }
@@ -895,6 +933,10 @@ static int impl_destroy(rvcp_ctx_t *ctx)
         (void)hipFree(ctx->d_sv_tmp[i]);
     }
     free_svgf_state(ctx);
+    (void)hipFree(ctx->d_ad_q);
+    (void)hipFree(ctx->d_ad_sums);
+    (void)hipFree(ctx->d_ad_map[0]);
+    (void)hipFree(ctx->d_ad_map[1]);
     for (ResolveState *st : {&ctx->taa_tp, &ctx->taa_sv, &ctx->taau_tp, &ctx->taau_sv})
         free_resolve_state(*st);
     for (const Stage &st : ctx->stage) {
@@ -1064,6 +1106,8 @@ static int upload_one(rvcp_ctx_t *ctx, const rvcp_material_t *materials, uint32_
     ctx->jit_tri.clear();
     ctx->jit_bvh = false;
     ctx->jit_sampling = ctx->sampling;
+    ctx->jit_map.reset();                     // (compiled by the first map render of this scene)
+    ctx->jit_map_sampling = -1;
     if (bvh_jit) {                            // the BVH hybrid's module (above)
         ctx->jit = bvh_jit;
         ctx->jit_tri.assign(tri.begin(), tri.begin() + ctx->bvh_prefix);
@@ -1139,17 +1183,37 @@ static void jit_for_sampling(rvcp_ctx_t *ctx)
     if (ctx->jit_bvh && ctx->jit && (!ctx->jit->bvh_path || !ctx->jit->bvh_primary)) ctx->jit.reset();
 }
 
+// The scene's specialised module for map renders (rvcp_render_spp_map_async) with the context's
+// bounce sampling, asked for as jit_for_sampling asks, with -DRVCP_SPP_MAP=1: by the first map
+// render of the scene in that mode.  Without one the generic map kernels run.
+static void jit_for_map(rvcp_ctx_t *ctx)
+{
+    ctx->jit_map_sampling = ctx->sampling;
+    ctx->jit_map.reset();
+    if (ctx->jit_tri.empty()) return;
+    std::string err;
+    ctx->jit_map = jit_path_kernels(ctx->device, ctx->jit_tri.data(), (uint32_t)ctx->jit_tri.size(),
+                                    err, false, false, false, ctx->jit_bvh, nullptr, 0, 64,
+                                    ctx->sampling, true);
+    (void)hipSetDevice(ctx->device);
+    if (ctx->jit_bvh && ctx->jit_map && (!ctx->jit_map->bvh_path || !ctx->jit_map->bvh_primary))
+        ctx->jit_map.reset();
+}
+
 // What plan_frame (rvcp_frame_plan.cpp) decides a render from: the config, the scene, the device's
-// capacities for the context's bounce sampling, the scene's specialised module and the frames
+// capacities for the context's bounce sampling, the scene's specialised module and the frames.
+// A map render (spp_hint > 0): the hint in place of cfg.spp, the map kernels' capacities and the
+// map module.
 static FramePlanIn frame_plan_input(const rvcp_ctx_t *ctx, uint32_t n_frames, uint32_t frame_px,
-                                    uint32_t stride)
+                                    uint32_t stride, uint32_t spp_hint = 0)
 {
     const bool cosine = ctx->sampling == RVCP_SAMPLING_COSINE;
+    const bool map = spp_hint > 0;
     FramePlanIn in;
     in.integrator = ctx->cfg.integrator;
     in.kernel_variant = ctx->cfg.kernel_variant;
     in.accel = ctx->cfg.accel;
-    in.spp = ctx->cfg.spp;
+    in.spp = map ? spp_hint : ctx->cfg.spp;
     in.max_bounces = ctx->cfg.max_bounces;
     in.attenuation_stop_eps = ctx->cfg.attenuation_stop_eps;
     in.ray_t_min = ctx->cfg.ray_t_min;
@@ -1157,11 +1221,14 @@ static FramePlanIn frame_plan_input(const rvcp_ctx_t *ctx, uint32_t n_frames, ui
     in.n_faces = ctx->n_faces;
     in.bvh_prefix = ctx->bvh_prefix;
     in.n_simds = ctx->n_simds;
-    std::memcpy(in.grid_capacity, cosine ? ctx->grid_capacity_cos : ctx->grid_capacity,
+    std::memcpy(in.grid_capacity,
+                map ? ctx->grid_capacity_map[cosine ? 1 : 0]
+                    : cosine ? ctx->grid_capacity_cos : ctx->grid_capacity,
                 sizeof(in.grid_capacity));
-    in.bvh_capacity = cosine ? ctx->bvh_capacity_cos : ctx->bvh_capacity;
+    in.bvh_capacity = map ? ctx->bvh_capacity_map[cosine ? 1 : 0]
+                          : cosine ? ctx->bvh_capacity_cos : ctx->bvh_capacity;
     in.legacy_capacity = ctx->legacy_capacity;
-    if (const JitKernels *jk = ctx->jit.get()) {
+    if (const JitKernels *jk = map ? ctx->jit_map.get() : ctx->jit.get()) {
         in.module = true;
         in.blocks_per_cu5 = jk->blocks_per_cu5;
         in.blocks_per_cu6 = jk->blocks_per_cu6;
@@ -1180,12 +1247,16 @@ static FramePlanIn frame_plan_input(const rvcp_ctx_t *ctx, uint32_t n_frames, ui
 
 // n_frames consecutive frames of one shard (pushes[k] for frame k) into outputs laid out frame
 // after frame, `slot` = the largest shard's rows apart (rvcp_render_frames_async); n_frames = 1
-// is rvcp_render_shard_async.
+// is rvcp_render_shard_async.  d_spp_map (rvcp_render_spp_map_async; one whole frame): the
+// frame's per-pixel sample counts, traced by the map builds of the pre-pass family, spp_hint in
+// place of cfg.spp in the plan.
 static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, uint32_t n_frames,
                          uint32_t width, uint32_t height, uint32_t shard_index,
-                         uint32_t shard_count, void *d_rgba8, void *d_linear_rgb, void *stream)
+                         uint32_t shard_count, void *d_rgba8, void *d_linear_rgb, void *stream,
+                         const uint32_t *d_spp_map = nullptr, uint32_t spp_hint = 0)
 {
     if (!ctx) return RVCP_E_INVALID;
+    const bool map = d_spp_map != nullptr;
     const rvcp_push_constant_t *push = pushes;
     if (!push || n_frames == 0 || !d_rgba8 || width == 0 || height == 0 || shard_count == 0 ||
         shard_index >= shard_count)
@@ -1212,14 +1283,21 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
     // the cosine-weighted bounce (rvcp_set_sampling): its kernels, and a
     // specialised module compiled for it
     const bool cosine = ctx->sampling == RVCP_SAMPLING_COSINE;
-    if (ctx->jit_sampling != ctx->sampling) jit_for_sampling(ctx);
+    if (map) {
+        if (ctx->jit_map_sampling != ctx->sampling) jit_for_map(ctx);
+    } else if (ctx->jit_sampling != ctx->sampling) {
+        jit_for_sampling(ctx);
+    }
 
     // the plan: schedule, specialised kernels and grid (rvcp_frame_plan.cpp)
     const uint32_t frame_px = rvcp_shard_rows(height, shard_index, shard_count) * width;
     const uint32_t split_px = frame_px * n_frames;          // the queue of the whole batch
-    const JitKernels *jk = ctx->jit.get();
-    const FramePlanIn in = frame_plan_input(ctx, n_frames, frame_px, stride);
+    const JitKernels *jk = map ? ctx->jit_map.get() : ctx->jit.get();
+    const FramePlanIn in = frame_plan_input(ctx, n_frames, frame_px, stride, map ? spp_hint : 0u);
     const FramePlan P = plan_frame(in);
+    if (map && P.status == RVCP_OK && !P.trivial && !P.legacy && P.variant < 3)
+        return fail(ctx, RVCP_E_UNSUPPORTED, "a per-pixel sample count needs a pre-pass schedule "
+                    "(schedules 3-6, 10, or the BVH path kernel)");
     if (P.status != RVCP_OK)
         return fail(ctx, P.status, "frame batches need a pre-pass schedule of the games101 "
                     "integrator (schedules 3-6, 10, or the BVH path kernel) or mode 2");
@@ -1232,7 +1310,7 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
     A.shard_index = shard_index;
     A.shard_count = shard_count;
     A.n_pixels = frame_px;
-    A.spp = ctx->cfg.spp;
+    A.spp = map ? spp_hint : ctx->cfg.spp;      // (a map build's kernels do not read it)
     A.max_bounces = ctx->cfg.max_bounces;
     A.att_stop = ctx->cfg.attenuation_stop_eps;
     A.t_min = ctx->cfg.ray_t_min;
@@ -1322,6 +1400,9 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
 
     // a gather of this context's previous frame may still read the caller's shard buffer
     if (ctx->gather_on_gstream) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evg1, 0));
+    // ... and a plan step of this context may still write the map
+    if (map && ctx->stage[ST_PLAN].recorded)
+        HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->stage[ST_PLAN].ev1, 0));
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, kCounterWords * sizeof(unsigned long long), s));
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
     int launch_rc = 0;
@@ -1336,6 +1417,18 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
         launch_rc = rvcp_launch_legacy(&A, ctx->d_tri, ctx->d_shade, ctx->d_spheres, ctx->d_rawmats,
                                        ctx->d_unorm, (uint32_t *)d_rgba8, lin, ctx->d_counters,
                                        P.blocks, s, P.spec_legacy ? (void *)jk->legacy : nullptr);
+    } else if (map) {
+        // the map builds of the pre-pass family (P.variant >= 3: checked above)
+        launch_rc = (cosine ? rvcp_launch_games101_v3_cosine_map : rvcp_launch_games101_v3_map)(
+            FA.data(), 1, stride, ctx->d_tri, ctx->d_faces, ctx->d_verts, ctx->d_mats,
+            ctx->d_lights, ctx->d_gamma, (uint32_t *)d_rgba8, lin, ctx->d_counters, ctx->d_surf,
+            ctx->d_shade, ctx->d_bvh_nodes, ctx->d_bvh_tris, P.blocks, s, ctx->evm,
+            P.spec ? (void *)(P.variant == 6 ? jk->path6 : jk->path5)
+                   : P.spec_bvh ? (void *)jk->bvh_path : nullptr,
+            nullptr,
+            P.spec && jit_spec_prepass() ? (void *)jk->primary
+                                         : P.spec_bvh ? (void *)jk->bvh_primary : nullptr,
+            d_spp_map);
     } else if (P.variant >= 3) {
         // (the launcher records evm itself, between the pre-pass and the path kernel)
         launch_rc = (cosine ? rvcp_launch_games101_v3_cosine : rvcp_launch_games101_v3)(
@@ -1362,6 +1455,7 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
     ctx->last_variant = P.stats_code;
     ctx->last_pixels = (uint64_t)frame_px * n_frames;       // stats cover the whole batch
     ctx->last_spp = A.spp;
+    ctx->last_map = map;
     ctx->last_shard_index = shard_index;
     ctx->last_shard_count = shard_count;
     ctx->last_width = width;
@@ -1395,6 +1489,29 @@ static int impl_render_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, 
     return rvcp_render_shard_async(ctx, push, width, height, 0, 1, d_rgba8, d_linear_rgb, stream);
 }
 
+// rvcp_render_async with a per-pixel sample count; every rejection comes before
+// any launch
+static int impl_render_spp_map_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push,
+                                     uint32_t width, uint32_t height, const void *d_spp_map,
+                                     uint32_t spp_hint, void *d_rgba8, void *d_linear_rgb,
+                                     void *stream)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!push || !d_spp_map || !d_rgba8 || width == 0 || height == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid map render arguments");
+    if (spp_hint < 1 || spp_hint > RVCP_SPP_MAP_MAX)
+        return fail(ctx, RVCP_E_INVALID, "spp_hint must be in 1..256");
+    if ((uint64_t)width * height >= (1ull << 31))
+        return fail(ctx, RVCP_E_INVALID, "frame too large (W*H must be < 2^31)");
+    if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
+        return fail(ctx, RVCP_E_UNSUPPORTED, "a per-pixel sample count is implemented for the "
+                    "games101 integrator");
+    if (!ctx->subs.empty())
+        return fail(ctx, RVCP_E_UNSUPPORTED, "rvcp_render_spp_map_async drives one GPU (n_gpus = 1)");
+    return render_frames(ctx, push, 1, width, height, 0, 1, d_rgba8, d_linear_rgb, stream,
+                         (const uint32_t *)d_spp_map, spp_hint);
+}
+
 static int impl_wait(rvcp_ctx_t *ctx, rvcp_stats_t *stats)
 {
     return rvcp_sync_stats(ctx, stats);
@@ -1424,6 +1541,13 @@ static int impl_sync_stats(rvcp_ctx_t *ctx, rvcp_stats_t *stats)
         // the reference re-traces the (RNG-independent) primary ray in every sample
         stats->traversals = ctx->last_trivial ? 0 : c[0] + ctx->last_pixels * (ctx->last_spp - 1);
         stats->samples = ctx->last_pixels * ctx->last_spp;
+        if (ctx->last_map) {
+            // a map render: the pre-pass's sum of the clamped counts (0 for a trivial frame, whose
+            // fill reads no map)
+            const uint64_t sum = c[kSppSumWord];
+            stats->samples = sum;
+            stats->traversals = ctx->last_trivial ? 0 : c[0] + (sum - ctx->last_pixels);
+        }
         stats->faces = ctx->n_faces;
         stats->kernel_variant = ctx->last_variant;
         stats->wave_iterations = c[2];
@@ -2431,6 +2555,138 @@ static int impl_get_demodulation(rvcp_ctx_t *ctx, int *on)
     return RVCP_OK;
 }
 
+// ---- adaptive sampling: the plan step and the switch -----------------------
+
+static int impl_adaptive_params_default(rvcp_adaptive_params_t *params)
+{
+    if (!params) return RVCP_E_INVALID;
+    // the best row on average of tools/adaptive_sweep.py
+    params->spp_min = 1;
+    params->spp_max = 32;
+    params->mean_spp = 4.0f;
+    params->weight_cap = 0.0625f;
+    params->epsilon = 1e-2f;
+    params->_pad = 0;
+    return RVCP_OK;
+}
+
+// *out = *params or the defaults, validated (negated compares: a NaN is rejected too)
+static int adaptive_params_checked(rvcp_ctx_t *ctx, const rvcp_adaptive_params_t *params,
+                                   rvcp_adaptive_params_t *out)
+{
+    if (params) *out = *params;
+    else (void)impl_adaptive_params_default(out);
+    if (out->spp_min < 1 || out->spp_min > RVCP_SPP_MAP_MAX)
+        return fail(ctx, RVCP_E_INVALID, "adaptive spp_min must be in 1..256");
+    if (out->spp_max < out->spp_min || out->spp_max > RVCP_SPP_MAP_MAX)
+        return fail(ctx, RVCP_E_INVALID, "adaptive spp_max must be in spp_min..256");
+    if (!(out->mean_spp >= (float)out->spp_min && out->mean_spp <= (float)out->spp_max))
+        return fail(ctx, RVCP_E_INVALID, "adaptive mean_spp must be in spp_min..spp_max");
+    if (!(out->weight_cap > 0.0f && out->weight_cap < INFINITY))
+        return fail(ctx, RVCP_E_INVALID, "adaptive weight_cap must be finite and > 0");
+    if (!(out->epsilon > 0.0f && out->epsilon < INFINITY))
+        return fail(ctx, RVCP_E_INVALID, "adaptive epsilon must be finite and > 0");
+    if (out->_pad != 0) return fail(ctx, RVCP_E_INVALID, "adaptive params._pad must be 0");
+    return RVCP_OK;
+}
+
+static int impl_spp_plan_async(rvcp_ctx_t *ctx, const void *d_variance, const void *d_linear,
+                               const void *d_len, const void *d_gbuffer, uint32_t width,
+                               uint32_t height, const rvcp_adaptive_params_t *params,
+                               void *d_map_out, void *stream)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!d_variance || !d_linear || !d_gbuffer || !d_map_out || width == 0 || height == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid plan arguments");
+    int rc;
+    if ((rc = frame_size_checked(ctx, width, height)) != RVCP_OK) return rc;
+    rvcp_adaptive_params_t P;
+    if ((rc = adaptive_params_checked(ctx, params, &P)) != RVCP_OK) return rc;
+    const size_t npx = (size_t)width * height;
+    if ((rc = overlap_checked(ctx, "plan",
+                              {{d_variance, npx * 4}, {d_linear, npx * 12}, {d_len, npx * 4},
+                               {d_gbuffer, npx * 32}},
+                              {{d_map_out, npx * 4}})) != RVCP_OK)
+        return rc;
+    // the budget B = floor(mean_spp npx) and what it leaves above spp_min for every pixel (mean_spp
+    // >= spp_min; the max is against the rounding of the product)
+    const uint64_t budget = (uint64_t)std::floor((double)P.mean_spp * (double)npx);
+    const uint64_t floor_px = (uint64_t)P.spp_min * npx;
+    const uint64_t extra = budget > floor_px ? budget - floor_px : 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if ((rc = grow(ctx, (void **)&ctx->d_ad_q, &ctx->cap_ad_q, npx, 4)) != RVCP_OK) return rc;
+    if (!ctx->d_ad_sums) HIP_TRY(ctx, hipMalloc((void **)&ctx->d_ad_sums, 2 * sizeof(unsigned long long)));
+    if ((rc = stage_begin(ctx, ST_PLAN, s)) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_ad_sums, 0, 2 * sizeof(unsigned long long), s));
+    if (rvcp_launch_spp_plan((const float *)d_variance, (const float *)d_linear,
+                             (const uint32_t *)d_len, d_gbuffer, (uint32_t)npx, P.weight_cap,
+                             P.epsilon, P.spp_min, P.spp_max, extra, ctx->d_ad_q, ctx->d_ad_sums,
+                             (uint32_t *)d_map_out, s) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string("plan launch failed: ") +
+                                         hipGetErrorString(hipGetLastError()));
+    return stage_end(ctx, ST_PLAN, s);
+}
+
+static int impl_spp_plan_wait(rvcp_ctx_t *ctx, float *plan_ms, uint64_t *planned_samples)
+{
+    int rc;
+    if ((rc = stage_wait(ctx, ST_PLAN, "no plan step in flight", plan_ms)) != RVCP_OK) return rc;
+    if (planned_samples) {
+        unsigned long long sums[2] = {};
+        HIP_TRY(ctx, hipMemcpy(sums, ctx->d_ad_sums, sizeof(sums), hipMemcpyDeviceToHost));
+        *planned_samples = sums[1];
+    }
+    return RVCP_OK;
+}
+
+static int impl_set_adaptive(rvcp_ctx_t *ctx, const rvcp_adaptive_params_t *params)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
+        return fail(ctx, RVCP_E_UNSUPPORTED, "adaptive sampling is implemented for the games101 "
+                    "integrator");
+    if (!ctx->subs.empty())
+        return fail(ctx, RVCP_E_UNSUPPORTED, "adaptive sampling drives one GPU (n_gpus = 1)");
+    if (ctx->pending)
+        return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    if (params) {
+        rvcp_adaptive_params_t P;
+        const int rc = adaptive_params_checked(ctx, params, &P);
+        if (rc != RVCP_OK) return rc;
+        ctx->ad_params = P;
+    }
+    ctx->adaptive = params != nullptr;
+    ctx->ad_valid = false;      // the map is dropped; the SVGF history is not
+    return RVCP_OK;
+}
+
+static int impl_get_adaptive(rvcp_ctx_t *ctx, int *on, rvcp_adaptive_params_t *out_params)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (on) *on = ctx->adaptive ? 1 : 0;
+    if (out_params) {
+        if (ctx->adaptive) *out_params = ctx->ad_params;
+        else (void)impl_adaptive_params_default(out_params);
+    }
+    return RVCP_OK;
+}
+
+static int impl_adaptive_last_map(rvcp_ctx_t *ctx, uint32_t *out_map, uint32_t *out_width,
+                                  uint32_t *out_height)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (ctx->ad_last < 0) return fail(ctx, RVCP_E_INVALID, "no frame was traced through a map yet");
+    if (out_width) *out_width = ctx->ad_w;
+    if (out_height) *out_height = ctx->ad_h;
+    if (out_map) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipMemcpy(out_map, ctx->d_ad_map[ctx->ad_last], (size_t)ctx->ad_w * ctx->ad_h * 4,
+                               hipMemcpyDeviceToHost));
+    }
+    return RVCP_OK;
+}
+
 // ---- the chains: rvcp_render_denoised, rvcp_render_temporal, rvcp_render_svgf ----------------
 
 // What a stateful chain does for its resolve state `st` before it renders (the TAA switch is set,
@@ -2638,6 +2894,7 @@ static int chain_tail(rvcp_ctx_t *ctx, ChainFrame &F, int rc, const float *d_out
     if (F.enqueued & stage_bit(ST_SVGF_ACC)) (void)impl_svgf_wait(ctx, nullptr, nullptr);
     if (ctx->stage[ST_DEMOD].pending || ctx->stage[ST_REMOD].pending)
         (void)impl_albedo_wait(ctx, nullptr, nullptr);
+    if (F.enqueued & stage_bit(ST_PLAN)) (void)impl_spp_plan_wait(ctx, nullptr, nullptr);
     ctx->err = why;
     return rc;
 }
@@ -2784,8 +3041,27 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
     const uint32_t prev = hist.slot, cur = prev ^ 1u;
     float *const d_cur = ctx->d_sv_cur;
     void *const d_gbuf = ctx->d_sv_gbuf[cur];
-    if ((rc = rvcp_render_async(ctx, F.push, F.width, F.height, ctx->d_rgba, d_cur, ctx->stream)) != RVCP_OK)
-        return rc;
+    // With the adaptive switch (§4.18): the raw frame through the map the previous frame planned,
+    // in that frame's pixel grid, while the SVGF history continues; else through a uniform map
+    const bool adaptive = ctx->adaptive;
+    const rvcp_adaptive_params_t &AP = ctx->ad_params;
+    if (adaptive) {
+        const bool planned = ctx->ad_valid && F.have && ctx->ad_w == F.width && ctx->ad_h == F.height;
+        ctx->ad_valid = false;              // until this frame is complete
+        for (int i = 0; i < 2; ++i)
+            if ((rc = grow(ctx, (void **)&ctx->d_ad_map[i], &ctx->cap_ad_map[i], F.npx, 4)) != RVCP_OK)
+                return rc;
+        const uint32_t fl = (uint32_t)AP.mean_spp;     // floor: mean_spp >= 1
+        const uint32_t uniform = fl < AP.spp_min ? AP.spp_min : fl > AP.spp_max ? AP.spp_max : fl;
+        if (!planned &&
+            rvcp_launch_fill_map(ctx->d_ad_map[ctx->ad_slot], (uint32_t)F.npx, uniform, ctx->stream) != 0)
+            return fail(ctx, RVCP_E_HIP, "render_svgf: the uniform map's launch failed");
+        rc = impl_render_spp_map_async(ctx, F.push, F.width, F.height, ctx->d_ad_map[ctx->ad_slot],
+                                       uniform, ctx->d_rgba, d_cur, ctx->stream);
+    } else {
+        rc = rvcp_render_async(ctx, F.push, F.width, F.height, ctx->d_rgba, d_cur, ctx->stream);
+    }
+    if (rc != RVCP_OK) return rc;
     // accumulation of colour and moments, then the filter
     rc = chain_gbuffer(ctx, F, d_cur, d_gbuf);
     if (rc == RVCP_OK) {
@@ -2802,10 +3078,17 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
                                     d_gbuf, F.width, F.height, sparams, ctx->d_sv_show,
                                     ctx->d_sv_showvar, feedback ? ctx->d_sv_fb : nullptr,
                                     F.demod ? nullptr : F.store, ctx->stream);
+    // ... and the next frame's map from this frame's filtered colour, variance, lengths and G-buffer
+    if (rc == RVCP_OK && adaptive) {
+        rc = impl_spp_plan_async(ctx, ctx->d_sv_showvar, ctx->d_sv_show, ctx->d_sv_len[cur], d_gbuf,
+                                 F.width, F.height, &AP, ctx->d_ad_map[ctx->ad_slot ^ 1u], ctx->stream);
+        if (rc == RVCP_OK) F.enqueued |= stage_bit(ST_PLAN);
+    }
     const float *d_final;
     if ((rc = chain_tail(ctx, F, rc, ctx->d_sv_show, d_gbuf, d_cur, &d_final)) != RVCP_OK) return rc;
     if ((rc = rvcp_wait(ctx, stats)) != RVCP_OK) return rc;
     if ((rc = impl_svgf_wait(ctx, accumulate_ms, filter_ms)) != RVCP_OK) return rc;
+    if (adaptive && (rc = impl_spp_plan_wait(ctx, nullptr, nullptr)) != RVCP_OK) return rc;
     if ((rc = chain_end(ctx, F, d_final, out_rgba8, out_linear_rgb)) != RVCP_OK) return rc;
     if (out_variance)
         HIP_TRY(ctx, hipMemcpy(out_variance, ctx->d_sv_showvar, F.npx * 4, hipMemcpyDeviceToHost));
@@ -2814,6 +3097,13 @@ static int impl_render_svgf(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, u
     // feedback: the next frame's colour history is pass 0's output (moments and lengths stay)
     if (feedback) std::swap(ctx->d_sv_lin[cur], ctx->d_sv_fb);
     chain_commit(F, hist);
+    if (adaptive) {         // the frame's map stays readable; the planned one is the next frame's
+        ctx->ad_last = (int)ctx->ad_slot;
+        ctx->ad_slot ^= 1u;
+        ctx->ad_w = F.width;
+        ctx->ad_h = F.height;
+        ctx->ad_valid = true;
+    }
     return RVCP_OK;
 }
 static int impl_assemble_frame_async(rvcp_ctx_t *ctx, const void *d_gathered, uint32_t slot_rows,
@@ -3597,6 +3887,48 @@ int rvcp_set_sampling(rvcp_ctx_t *ctx, int32_t sampling)
 int rvcp_get_sampling(rvcp_ctx_t *ctx, int32_t *sampling)
 {
     return barrier(ctx, [&] { return impl_get_sampling(ctx, sampling); });
+}
+
+int rvcp_render_spp_map_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                              uint32_t height, const void *d_spp_map, uint32_t spp_hint,
+                              void *d_rgba8, void *d_linear_rgb, void *stream)
+{
+    return barrier(ctx, [&] { return impl_render_spp_map_async(ctx, push, width, height, d_spp_map,
+        spp_hint, d_rgba8, d_linear_rgb, stream); });
+}
+
+int rvcp_adaptive_params_default(rvcp_adaptive_params_t *params)
+{
+    return barrier(nullptr, [&] { return impl_adaptive_params_default(params); });
+}
+
+int rvcp_spp_plan_async(rvcp_ctx_t *ctx, const void *d_variance, const void *d_linear,
+                        const void *d_len, const void *d_gbuffer, uint32_t width, uint32_t height,
+                        const rvcp_adaptive_params_t *params, void *d_spp_map_out, void *stream)
+{
+    return barrier(ctx, [&] { return impl_spp_plan_async(ctx, d_variance, d_linear, d_len, d_gbuffer,
+        width, height, params, d_spp_map_out, stream); });
+}
+
+int rvcp_spp_plan_wait(rvcp_ctx_t *ctx, float *plan_ms, uint64_t *planned_samples)
+{
+    return barrier(ctx, [&] { return impl_spp_plan_wait(ctx, plan_ms, planned_samples); });
+}
+
+int rvcp_set_adaptive(rvcp_ctx_t *ctx, const rvcp_adaptive_params_t *params)
+{
+    return barrier(ctx, [&] { return impl_set_adaptive(ctx, params); });
+}
+
+int rvcp_get_adaptive(rvcp_ctx_t *ctx, int *on, rvcp_adaptive_params_t *out_params)
+{
+    return barrier(ctx, [&] { return impl_get_adaptive(ctx, on, out_params); });
+}
+
+int rvcp_adaptive_last_map(rvcp_ctx_t *ctx, uint32_t *out_map, uint32_t *out_width,
+                           uint32_t *out_height)
+{
+    return barrier(ctx, [&] { return impl_adaptive_last_map(ctx, out_map, out_width, out_height); });
 }
 
 }  // extern "C"

@@ -85,6 +85,9 @@ constexpr int kMaxVariant = 10;
 // (shader-clock ticks, 100-MHz ticks; clock_stamp in rvcp_kernels.hip)
 constexpr int kCounterWords = 32;
 constexpr int kClockWord = 16;
+// ... and, from the pre-pass of a map render (RVCP_SPP_MAP), the sum of the
+// frame's clamped per-pixel sample counts
+constexpr int kSppSumWord = 4;
 constexpr int kTiledPoolVariant = 10;
 constexpr int variant_block(int v) { return v == kTiledPoolVariant ? kTiledPoolWaves * kWave : kBlock; }
 constexpr uint64_t kWideMinSamples = 8ull << 20;   // auto: variant 6 from 8 Msamples per frame
@@ -383,6 +386,34 @@ int rvcp_launch_games101_v3_cosine(const rvcp::FrameArgs *args, uint32_t n_frame
                                    uint32_t grid_blocks, void *stream, void *main_event,
                                    void *spec_path_fn, const float *cams, void *spec_pre_fn);
 int rvcp_games101_occupancy_cosine(int variant, int *blocks_per_cu);
+// The pre-pass family with a per-pixel sample count (rvcp_kernels_map.hip,
+// rvcp_kernels_cosine_map.hip: RVCP_SPP_MAP = 1), per bounce sampling: the
+// launcher takes the frame's map (n_pixels words of device memory, clamped by the pre-pass) and
+// a specialised module passed to it must have been compiled with the map too; the occupancy
+// query knows schedules 3, 4, 5, 6, 10 and kOccupancyBvh.
+int rvcp_launch_games101_v3_map(const rvcp::FrameArgs *args, uint32_t n_frames,
+                                uint32_t frame_stride, const rvcp::TriRecord *tri,
+                                const void *faces, const void *verts, const rvcp::MatRecord *mats,
+                                const rvcp::LightRecord *lights, const float *gamma_t,
+                                uint32_t *out_rgba, float *out_lin, unsigned long long *counters,
+                                rvcp::SurfRecord *surf, const rvcp::FaceShade *shade,
+                                const rvcp::Bvh4Node *bvh_nodes, const rvcp::TriRecord *bvh_tris,
+                                uint32_t grid_blocks, void *stream, void *main_event,
+                                void *spec_path_fn, const float *cams, void *spec_pre_fn,
+                                const uint32_t *spp_map);
+int rvcp_launch_games101_v3_cosine_map(const rvcp::FrameArgs *args, uint32_t n_frames,
+                                       uint32_t frame_stride, const rvcp::TriRecord *tri,
+                                       const void *faces, const void *verts,
+                                       const rvcp::MatRecord *mats, const rvcp::LightRecord *lights,
+                                       const float *gamma_t, uint32_t *out_rgba, float *out_lin,
+                                       unsigned long long *counters, rvcp::SurfRecord *surf,
+                                       const rvcp::FaceShade *shade, const rvcp::Bvh4Node *bvh_nodes,
+                                       const rvcp::TriRecord *bvh_tris, uint32_t grid_blocks,
+                                       void *stream, void *main_event, void *spec_path_fn,
+                                       const float *cams, void *spec_pre_fn,
+                                       const uint32_t *spp_map);
+int rvcp_games101_occupancy_map(int variant, int *blocks_per_cu);
+int rvcp_games101_occupancy_cosine_map(int variant, int *blocks_per_cu);
 // Integrator RVCP_INTEGRATOR_LEGACY (ray_tracer.comp): materials / spheres are the raw
 // rvcp_material_t / rvcp_sphere_t arrays, unorm_t the UNORM8 threshold table.
 int rvcp_launch_legacy(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
@@ -462,6 +493,16 @@ int rvcp_launch_taa_upsample(const float *cur_c, const void *g_hi, const float *
                              const struct rvcp_temporal_view *prev_view,
                              const struct rvcp_taau_params *params, uint32_t force_direct,
                              void *stream);
+// The plan step of adaptive sampling (rvcp_adaptive.hip) over n_pixels pixels:
+// priorities into q_plane and their sum into sums[0], then the map into map_out and its sum into
+// sums[1] (sums: two zeroed 64-bit words); len may be null (1 everywhere); extra = the budget
+// above spp_min for every pixel.  And a uniform map of `value`.
+int rvcp_launch_spp_plan(const float *var, const float *lin, const uint32_t *len,
+                         const void *gbuffer, uint32_t n_pixels, float weight_cap, float epsilon,
+                         uint32_t spp_min, uint32_t spp_max, unsigned long long extra,
+                         uint32_t *q_plane, unsigned long long *sums, uint32_t *map_out,
+                         void *stream);
+int rvcp_launch_fill_map(uint32_t *map, uint32_t n_pixels, uint32_t value, void *stream);
 int rvcp_launch_assemble(const uint32_t *gathered, uint32_t slot_rows, uint32_t width,
                          uint32_t height, uint32_t shard_count, uint32_t *frame, void *stream);
 int rvcp_launch_fill(uint32_t *out_rgba, float *out_lin, uint32_t n_pixels, uint32_t rgba,

@@ -780,7 +780,7 @@ unsigned jit_scan_opts()
 }
 
 std::vector<std::string> jit_options(bool legacy, int legacy_waves, bool lds_scene, bool bvh,
-                                     int sampling = 0);
+                                     int sampling = 0, bool spp_map = false);
 
 // The line a module's source ends with for a bounce sampling other than the default: the
 // process-wide module cache is keyed by the source text, so the two modes' modules differ in it.
@@ -788,6 +788,12 @@ std::string jit_sampling_tag(int sampling)
 {
     return sampling == RVCP_SAMPLING_UNIFORM ? std::string()
                                              : "// +sampling " + std::to_string(sampling) + "\n";
+}
+
+// ... and for a module whose pre-pass family takes a per-pixel sample count
+std::string jit_spp_map_tag(bool spp_map)
+{
+    return spp_map ? std::string("// +spp_map\n") : std::string();
 }
 
 namespace {
@@ -939,13 +945,13 @@ void disk_write(const std::string &dir, const std::string &key, const std::vecto
 // With g_mu held.
 int jit_cached_code(const std::string &scan, std::vector<char> &code, std::string &err,
                     bool legacy, int legacy_waves, bool lds_scene, bool bvh, bool *from_disk,
-                    bool force_compile, int sampling)
+                    bool force_compile, int sampling, bool spp_map)
 {
     *from_disk = false;
     const std::string dir = cache_dir();
     std::string key;
     if (!dir.empty()) {
-        key = code_key(scan, jit_options(legacy, legacy_waves, lds_scene, bvh, sampling));
+        key = code_key(scan, jit_options(legacy, legacy_waves, lds_scene, bvh, sampling, spp_map));
         if (force_compile) {
             g_disk_rejects++;
         } else {
@@ -958,7 +964,8 @@ int jit_cached_code(const std::string &scan, std::vector<char> &code, std::strin
             if (r < 0) g_disk_rejects++;
         }
     }
-    if (jit_compile_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, sampling) != 0) return -1;
+    if (jit_compile_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, sampling, spp_map) != 0)
+        return -1;
     g_disk_compiles++;
     if (!dir.empty()) disk_write(dir, key, code);
     return 0;
@@ -978,7 +985,7 @@ JitKernels::~JitKernels()
 // The hipRTC options of a module: the flags of the static build (Makefile), on which the
 // numeric contract depends, and the module's variant defines.
 std::vector<std::string> jit_options(bool legacy, int legacy_waves, bool lds_scene, bool bvh,
-                                     int sampling)
+                                     int sampling, bool spp_map)
 {
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17",
                                      "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
@@ -989,6 +996,8 @@ std::vector<std::string> jit_options(bool legacy, int legacy_waves, bool lds_sce
     // the games101 kernels' bounce (rvcp_set_sampling): the default modules get no define, so
     // their options and keys are the ones they always had
     if (sampling != RVCP_SAMPLING_UNIFORM) opts.push_back("-DRVCP_SAMPLING=" + std::to_string(sampling));
+    // the pre-pass family with a per-pixel sample count (rvcp_render_spp_map_async), likewise
+    if (spp_map) opts.push_back("-DRVCP_SPP_MAP=1");
 #ifdef RVCP_TIMELINE
     opts.push_back("-DRVCP_TIMELINE");      // the debug library's modules keep the per-wave timeline
 #endif
@@ -999,7 +1008,8 @@ std::vector<std::string> jit_options(bool legacy, int legacy_waves, bool lds_sce
 }
 
 int jit_compile_code(const std::string &scan, std::vector<char> &code, std::string &err,
-                     bool legacy, int legacy_waves, bool lds_scene, bool bvh, int sampling)
+                     bool legacy, int legacy_waves, bool lds_scene, bool bvh, int sampling,
+                     bool spp_map)
 {
     const RtcApi &api = rtc();
     if (!api.ok) {
@@ -1014,7 +1024,8 @@ int jit_compile_code(const std::string &scan, std::vector<char> &code, std::stri
         err = "hiprtcCreateProgram failed";
         return -1;
     }
-    const std::vector<std::string> opt_s = jit_options(legacy, legacy_waves, lds_scene, bvh, sampling);
+    const std::vector<std::string> opt_s =
+        jit_options(legacy, legacy_waves, lds_scene, bvh, sampling, spp_map);
     std::vector<const char *> opts;
     for (const std::string &x : opt_s) opts.push_back(x.c_str());
     const int rc = api.compile(prog, (int)opts.size(), opts.data());
@@ -1038,7 +1049,8 @@ int jit_compile_code(const std::string &scan, std::vector<char> &code, std::stri
 std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, uint32_t n,
                                              std::string &err, bool legacy, bool sphereless,
                                              bool lds_fits, bool bvh, const rvcp_sphere_t *spheres,
-                                             uint32_t n_spheres, uint32_t n_materials, int sampling)
+                                             uint32_t n_spheres, uint32_t n_materials, int sampling,
+                                             bool spp_map)
 {
     // Mode 2 on a scene without spheres (the Cornell frame): 6 waves per SIMD measured 2.5 %
     // faster than 5, with spheres 5 % slower (profiles/history/r02_legacy_waves_ab.log).  With the
@@ -1065,7 +1077,7 @@ std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, u
                 : std::string()) +
         (key_flags.empty() ? std::string() : "// +flags" + key_flags + "\n") +
         (bvh ? "// +bvh\n" : "") +
-        jit_sampling_tag(sampling);
+        jit_sampling_tag(sampling) + jit_spp_map_tag(spp_map);
     const uint64_t h = fnv1a(scan);
     std::lock_guard<std::mutex> lock(g_mu);
     for (auto it = g_cache.begin(); it != g_cache.end(); ++it) {
@@ -1098,9 +1110,11 @@ std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, u
     };
     std::vector<char> code;
     bool from_disk = false;
-    if (jit_cached_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, &from_disk, false, sampling) != 0)
+    if (jit_cached_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, &from_disk, false, sampling,
+                        spp_map) != 0)
         return nullptr;
-    const uint64_t key_hash = fnv1a(code_key(scan, jit_options(legacy, legacy_waves, lds_scene, bvh, sampling)));
+    const uint64_t key_hash =
+        fnv1a(code_key(scan, jit_options(legacy, legacy_waves, lds_scene, bvh, sampling, spp_map)));
     auto k = std::make_shared<JitKernels>();
     k->device = device;
     k->key_hash = key_hash;
@@ -1111,7 +1125,8 @@ std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, u
         k = std::make_shared<JitKernels>();
         k->device = device;
         k->key_hash = key_hash;
-        if (jit_cached_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, &from_disk, true, sampling) != 0)
+        if (jit_cached_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, &from_disk, true, sampling,
+                            spp_map) != 0)
             return nullptr;
         why = load(*k, code);
     }
@@ -1283,6 +1298,64 @@ extern "C" int rvcp_internal_jit_compile_check_sampling(const void *tri_records,
             rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n) +
             rvcp::jit_sampling_tag(sampling);
         const int rc = rvcp::jit_compile_code(scan, code, e, false, 0, false, false, sampling);
+        if (code_bytes) *code_bytes = code.size();
+        if (err && err_cap) {
+            std::strncpy(err, e.c_str(), err_cap - 1);
+            err[err_cap - 1] = '\0';
+        }
+        return rc;
+    } catch (...) {
+        return -1;
+    }
+}
+
+// The same three hooks for a module whose pre-pass family takes a per-pixel sample count
+// (rvcp_render_spp_map_async): `spp_map` != 0 adds jit_spp_map_tag and
+// -DRVCP_SPP_MAP=1.
+extern "C" size_t rvcp_internal_jit_module_source_map(const void *tri_records, uint32_t n,
+                                                      int sampling, int spp_map, char *out,
+                                                      size_t cap)
+{
+    try {
+        const std::string s =
+            rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n) +
+            rvcp::jit_sampling_tag(sampling) + rvcp::jit_spp_map_tag(spp_map != 0);
+        if (out && cap) {
+            std::strncpy(out, s.c_str(), cap - 1);
+            out[cap - 1] = '\0';
+        }
+        return s.size();
+    } catch (...) {
+        return 0;
+    }
+}
+
+extern "C" uint64_t rvcp_internal_jit_module_key_for_map(const void *tri_records, uint32_t n,
+                                                         int sampling, int spp_map)
+{
+    try {
+        const std::string scan =
+            rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n) +
+            rvcp::jit_sampling_tag(sampling) + rvcp::jit_spp_map_tag(spp_map != 0);
+        return rvcp::fnv1a(rvcp::code_key(
+            scan, rvcp::jit_options(false, 0, false, false, sampling, spp_map != 0)));
+    } catch (...) {
+        return 0;
+    }
+}
+
+extern "C" int rvcp_internal_jit_compile_check_map(const void *tri_records, uint32_t n,
+                                                    int sampling, int spp_map, int bvh,
+                                                    size_t *code_bytes, char *err, size_t err_cap)
+{
+    try {
+        std::string e;
+        std::vector<char> code;
+        const std::string scan =
+            rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n) +
+            rvcp::jit_sampling_tag(sampling) + rvcp::jit_spp_map_tag(spp_map != 0);
+        const int rc = rvcp::jit_compile_code(scan, code, e, false, 0, false, bvh != 0, sampling,
+                                              spp_map != 0);
         if (code_bytes) *code_bytes = code.size();
         if (err && err_cap) {
             std::strncpy(err, e.c_str(), err_cap - 1);

@@ -49,13 +49,13 @@ std::string jit_scan_source(const TriRecord *tri, uint32_t n, unsigned opts = 0)
 // `lds_scene`: the mode-2 kernel copies the scene into LDS (RVCP_LEGACY_LDS_SCENE).
 int jit_compile_code(const std::string &scan, std::vector<char> &code, std::string &err,
                      bool legacy = false, int legacy_waves = 0, bool lds_scene = false,
-                     bool bvh = false, int sampling = RVCP_SAMPLING_UNIFORM);
+                     bool bvh = false, int sampling = RVCP_SAMPLING_UNIFORM, bool spp_map = false);
 // jit_compile_code behind the on-disk code-object cache (rvcp_set_code_cache_dir): a verified
 // entry for exactly this compile is read (*from_disk = true), else the module is compiled and
 // stored; force_compile counts the entry rejected and recompiles it (the runtime refused it).
 int jit_cached_code(const std::string &scan, std::vector<char> &code, std::string &err,
                     bool legacy, int legacy_waves, bool lds_scene, bool bvh, bool *from_disk,
-                    bool force_compile, int sampling = RVCP_SAMPLING_UNIFORM);
+                    bool force_compile, int sampling = RVCP_SAMPLING_UNIFORM, bool spp_map = false);
 // Compiled + loaded kernels for the scene on `device` (process-wide cache keyed by the scan
 // source and `legacy`); nullptr with err set when hipRTC is unavailable or compilation fails.
 // `sphereless`: the mode-2 kernel is built for 6 waves per SIMD.
@@ -66,12 +66,16 @@ int jit_cached_code(const std::string &scan, std::vector<char> &code, std::strin
 // (jit_sphere_source) -- the module is then valid for these spheres only, like its scan.
 // `sampling` (RVCP_SAMPLING_*): the bounce the module's games101 kernels are compiled with
 // (-DRVCP_SAMPLING); part of the module's source tag and of its compile key.
+// `spp_map`: the module's pre-pass family takes a per-pixel sample count (-DRVCP_SPP_MAP=1,
+// rvcp_spec_primary_kernel and rvcp_spec_bvh_primary_kernel then have one more
+// parameter, the map); part of the source tag and of the compile key likewise.
 std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, uint32_t n,
                                              std::string &err, bool legacy = false,
                                              bool sphereless = false, bool lds_fits = false,
                                              bool bvh = false, const rvcp_sphere_t *spheres = nullptr,
                                              uint32_t n_spheres = 0, uint32_t n_materials = 64,
-                                             int sampling = RVCP_SAMPLING_UNIFORM);
+                                             int sampling = RVCP_SAMPLING_UNIFORM,
+                                             bool spp_map = false);
 // The sphere X-macro of a mode-2 module ("" for none or more than kJitMaxSpheres).
 constexpr uint32_t kJitMaxSpheres = 64;
 std::string jit_sphere_source(const rvcp_sphere_t *sph, uint32_t n);

@@ -51,10 +51,64 @@
 #define rvcp_games101_occupancy rvcp_games101_occupancy_cosine
 #endif
 
+// RVCP_SPP_MAP: 1 = the pre-pass family takes a per-pixel sample count (DESIGN.md §4.18,
+// rvcp_render_spp_map_async) -- the pre-pass reads pixel p's count from an extra argument
+// `spp_map`, clamps it to 1..RVCP_SPP_MAP_MAX, closes miss / light pixels with it and hands it to
+// the path kernel in SurfRecord::mat, where it stands in for FrameArgs::spp (path_body).  Chosen
+// when this file is compiled, by §4.17's mechanism: one translation unit per bounce sampling
+// (rvcp_kernels_map.hip, rvcp_kernels_cosine_map.hip) holding only the pre-pass family -- the
+// primary kernels, the path kernels of schedules 3, 4, 5, 6 and 10, the BVH path kernel -- under
+// names of their own (behind the headers below), and -DRVCP_SPP_MAP=1 for the scene-specialised
+// modules (rvcp_jit.cpp).  Read in primary_body and path_body only; the default text does not
+// mention a map.
+#ifndef RVCP_SPP_MAP
+#define RVCP_SPP_MAP 0
+#endif
+// the pre-pass's extra parameter and argument in a map build, nothing otherwise
+#if RVCP_SPP_MAP
+#define RVCP_SPP_MAP_PARAM , const uint32_t *__restrict__ spp_map
+#define RVCP_SPP_MAP_ARG , spp_map
+#else
+#define RVCP_SPP_MAP_PARAM
+#define RVCP_SPP_MAP_ARG
+#endif
+// a build other than the default one holds the games101 kernels only
+#define RVCP_GAMES101_ONLY (RVCP_SAMPLING || RVCP_SPP_MAP)
+
 #include "rvcp_internal.h"
 #include "../../include/rvcp.h"
 #include "rvcp_sqrt.h"
 #include "rvcp_tonemap.h"
+
+// a map build's names (after the headers: rvcp_internal.h declares every launcher by its own)
+#if RVCP_SPP_MAP && !defined(RVCP_JIT)
+#undef games101_path_kernel
+#undef games101_bvh_path_kernel
+#undef games101_tiled_kernel
+#undef games101_tiled_pool_kernel
+#undef games101_tiled_single_kernel
+#undef rvcp_launch_games101_v3
+#undef rvcp_games101_occupancy
+#if RVCP_SAMPLING
+#define games101_primary_kernel games101_cosine_map_primary_kernel
+#define games101_path_kernel games101_cosine_map_path_kernel
+#define games101_bvh_path_kernel games101_cosine_map_bvh_path_kernel
+#define games101_tiled_kernel games101_cosine_map_tiled_kernel
+#define games101_tiled_pool_kernel games101_cosine_map_tiled_pool_kernel
+#define games101_tiled_single_kernel games101_cosine_map_tiled_single_kernel
+#define rvcp_launch_games101_v3 rvcp_launch_games101_v3_cosine_map
+#define rvcp_games101_occupancy rvcp_games101_occupancy_cosine_map
+#else
+#define games101_primary_kernel games101_map_primary_kernel
+#define games101_path_kernel games101_map_path_kernel
+#define games101_bvh_path_kernel games101_map_bvh_path_kernel
+#define games101_tiled_kernel games101_map_tiled_kernel
+#define games101_tiled_pool_kernel games101_map_tiled_pool_kernel
+#define games101_tiled_single_kernel games101_map_tiled_single_kernel
+#define rvcp_launch_games101_v3 rvcp_launch_games101_v3_map
+#define rvcp_games101_occupancy rvcp_games101_occupancy_map
+#endif
+#endif
 
 namespace rvcp {
 namespace {
@@ -1336,7 +1390,8 @@ enum : int { K_NONE = -1, K_PRIMARY = 0, K_PATH = 1, K_SHADOW = 2 };
 
 }  // namespace
 
-#ifndef RVCP_JIT   // the scene-specialised module (rvcp_jit.cpp) holds only the path kernels
+#if !defined(RVCP_JIT) && !RVCP_SPP_MAP   // the scene-specialised module (rvcp_jit.cpp) holds only the path kernels,
+                                          // a map build (RVCP_SPP_MAP) only the pre-pass family
 // ======================================================================================
 // Variant 1: one ray per lane per iteration
 // ======================================================================================
@@ -1671,7 +1726,7 @@ __device__ __forceinline__ void primary_body(
     float *__restrict__ out_lin, unsigned long long *__restrict__ counters,
     SurfRecord *__restrict__ surf, const FaceShade *__restrict__ shade,
     const Bvh4Node *__restrict__ bvh_nodes, const TriRecord *__restrict__ bvh_tris,
-    const float *__restrict__ cams, uint32_t frame_stride)
+    const float *__restrict__ cams, uint32_t frame_stride RVCP_SPP_MAP_PARAM)
 {
     __shared__ uint32_t block_count, block_base;
     const uint32_t lane = lane_id();
@@ -1681,12 +1736,25 @@ __device__ __forceinline__ void primary_body(
     const Cam C = cams ? cam_load(cams + 16u * blockIdx.y) : cam_of(A);
     const uint32_t pix_base = A.pix_base + blockIdx.y * frame_stride;
     const bool live = pix < A.n_pixels;
+#if RVCP_SPP_MAP
+    __shared__ uint32_t block_spp;
+    if (threadIdx.x == 0) block_spp = 0;
+#endif
     if (threadIdx.x == 0) block_count = 0;
     __syncthreads();
     bool is_surf = false;
     f3 hpos = mk(0, 0, 0), hn = mk(0, 0, 0), halb = mk(0, 0, 0);
     uint32_t hmat = 0;
     float u_ = 0.0f, v_ = 0.0f;
+#if RVCP_SPP_MAP
+    // the pixel's sample count: the map's word, clamped here and nowhere else (the map is device
+    // memory the host cannot validate; 0 outside the frame, so that the block's sum skips it)
+    uint32_t s_p = 0;
+    if (live) {
+        s_p = spp_map[pix];
+        s_p = s_p < 1u ? 1u : (s_p > RVCP_SPP_MAP_MAX ? RVCP_SPP_MAP_MAX : s_p);
+    }
+#endif
     if (live) {
         float tmin, tmax;
         f3 o, d;
@@ -1734,9 +1802,14 @@ __device__ __forceinline__ void primary_body(
         const bool is_light = !miss && fs.ty == kLight;
         if (miss || is_light) {
             const f3 L = miss ? mk(0.1f, 0.1f, 0.1f) : ld3(mats[hmat].albedo);
-            const f3 Ls = divs(L, (float)A.spp);
+#if RVCP_SPP_MAP
+            const uint32_t n_spp = s_p;
+#else
+            const uint32_t n_spp = A.spp;
+#endif
+            const f3 Ls = divs(L, (float)n_spp);
             f3 acc = mk(0, 0, 0);
-            for (uint32_t i = 0; i < A.spp; ++i) acc = add(acc, Ls);
+            for (uint32_t i = 0; i < n_spp; ++i) acc = add(acc, Ls);
             store_acc(pix_base + pix, acc, out_lin);
         } else {
             is_surf = true;
@@ -1747,11 +1820,20 @@ __device__ __forceinline__ void primary_body(
     uint32_t wave_off = 0;
     if (lane == 0 && m) wave_off = atomicAdd(&block_count, (uint32_t)__builtin_popcountll(m));
     wave_off = __shfl(wave_off, 0);
+#if RVCP_SPP_MAP
+    // the block's sum of sample counts (rvcp_sync_stats: samples, traversals): wave sums into LDS
+    uint32_t wave_spp = s_p;
+    for (int o = kWave / 2; o > 0; o >>= 1) wave_spp += __shfl_xor(wave_spp, o);
+    if (lane == 0 && wave_spp) atomicAdd(&block_spp, wave_spp);
+#endif
     __syncthreads();
     if (threadIdx.x == 0) {
         block_base = block_count ? atomicAdd((unsigned int *)&counters[3], block_count) : 0u;
         const uint32_t lim = A.n_pixels - blockIdx.x * kPrimaryBlock;
         atomicAdd(&counters[0], (unsigned long long)(lim < kPrimaryBlock ? lim : kPrimaryBlock));
+#if RVCP_SPP_MAP
+        atomicAdd(&counters[kSppSumWord], (unsigned long long)block_spp);
+#endif
     }
     __syncthreads();
     if (is_surf) {
@@ -1759,6 +1841,9 @@ __device__ __forceinline__ void primary_body(
         r.pos[0] = hpos.x; r.pos[1] = hpos.y; r.pos[2] = hpos.z; r.pix = pix_base + pix;
         r.nrm[0] = hn.x; r.nrm[1] = hn.y; r.nrm[2] = hn.z; r.seed = pixel_seed(C, u_, v_);
         r.alb_pi[0] = halb.x; r.alb_pi[1] = halb.y; r.alb_pi[2] = halb.z; r.mat = hmat;
+#if RVCP_SPP_MAP
+        r.mat = s_p;        // (no path kernel reads the material: the word carries the count)
+#endif
         surf[block_base + wave_off + rank_in(m)] = r;
     }
 }
@@ -1772,10 +1857,10 @@ __global__ __launch_bounds__(kPrimaryBlock) void games101_primary_kernel(
     float *__restrict__ out_lin, unsigned long long *__restrict__ counters,
     SurfRecord *__restrict__ surf, const FaceShade *__restrict__ shade,
     const Bvh4Node *__restrict__ bvh_nodes, const TriRecord *__restrict__ bvh_tris,
-    const float *__restrict__ cams, uint32_t frame_stride)
+    const float *__restrict__ cams, uint32_t frame_stride RVCP_SPP_MAP_PARAM)
 {
     primary_body<BVH, false>(A, tri, faces, verts, mats, gamma_t, out_rgba, out_lin, counters,
-                             surf, shade, bvh_nodes, bvh_tris, cams, frame_stride);
+                             surf, shade, bvh_nodes, bvh_tris, cams, frame_stride RVCP_SPP_MAP_ARG);
 }
 
 // The G-buffer (rvcp_render_gbuffer_async): the pre-pass's primary hit of every
@@ -2006,8 +2091,10 @@ __device__ __forceinline__ void path_body(
         Q.static_chunks = c * waves;
     }
     Queue q = queue_init(Q);
+#if !RVCP_SPP_MAP
     const float sppf = (float)A.spp;
     const float inv_spp = rcp_ieee(sppf);     // divs_y's shared reciprocal
+#endif
 
     bool need_pixel = true, done = false, ended = false, surf_ev = false;
     // the pixel's surface record (cached primary hit, pixel index) is re-read from the list at
@@ -2038,10 +2125,23 @@ __device__ __forceinline__ void path_body(
             if (ended) {                                            // color += L / SPP (:495)
                 ended = false;
                 if (LDS_STATE) acc = st_get3(7);
+#if RVCP_SPP_MAP
+                // the pixel's own count (the pre-pass's clamped map word, in the record's `mat`),
+                // re-read where the record is re-read anyway instead of held across the scan:
+                // divs_y as in the default build, its reciprocal per lane instead of wave-uniform
+                const uint32_t px_spp = surf[pslot].mat;
+                const float px_sppf = (float)px_spp;
+                acc = add(acc, divs_y(col, px_sppf, rcp_ieee(px_sppf)));
+#else
                 acc = add(acc, divs_y(col, sppf, inv_spp));
+#endif
                 if (LDS_STATE) st_put3(7, acc);
                 k += 1;
+#if RVCP_SPP_MAP
+                if (k >= px_spp) {
+#else
                 if (k >= A.spp) {
+#endif
                     store_acc(surf[pslot].pix, acc, out_lin);
                     need_pixel = true;
                 } else {
@@ -2751,7 +2851,7 @@ __global__ __launch_bounds__(kBlock, kTiledMinWaves) void games101_tiled_single_
                            shade, tail_tab, tile);
 }
 
-#if !RVCP_SAMPLING  // (the cosine build holds the games101 kernels only)
+#if !RVCP_GAMES101_ONLY  // (the cosine and map builds hold the games101 kernels only)
 // Frame assembly after the RCCL gather: slot k holds shard k's stripes packed.
 __global__ void assemble_kernel(const uint32_t *__restrict__ gathered, uint32_t slot_rows,
                                 uint32_t width, uint32_t height, uint32_t shard_count,
@@ -2790,10 +2890,10 @@ __global__ void fill_kernel(uint32_t *__restrict__ out_rgba, float *__restrict__
         if (out_lin) { out_lin[3 * i] = 0.0f; out_lin[3 * i + 1] = 0.0f; out_lin[3 * i + 2] = 0.0f; }
     }
 }
-#endif  // !RVCP_SAMPLING
+#endif  // !RVCP_GAMES101_ONLY
 
 #endif  // RVCP_JIT
-#if (!defined(RVCP_JIT) && !RVCP_SAMPLING) || defined(RVCP_JIT_LEGACY)
+#if (!defined(RVCP_JIT) && !RVCP_GAMES101_ONLY) || defined(RVCP_JIT_LEGACY)
 // ======================================================================================
 // Integrator RVCP_INTEGRATOR_LEGACY: ray_trace of assets/shaders/ray_tracer.comp
 // (:618-694, main :802-822) -- spheres then triangles, Lambertian / metal / dielectric
@@ -3384,10 +3484,10 @@ extern "C" __global__ __launch_bounds__(kPrimaryBlock) void rvcp_spec_bvh_primar
     float *__restrict__ out_lin, unsigned long long *__restrict__ counters,
     SurfRecord *__restrict__ surf, const FaceShade *__restrict__ shade,
     const Bvh4Node *__restrict__ bvh_nodes, const TriRecord *__restrict__ bvh_tris,
-    const float *__restrict__ cams, uint32_t frame_stride)
+    const float *__restrict__ cams, uint32_t frame_stride RVCP_SPP_MAP_PARAM)
 {
     primary_body<true, true>(A, tri, faces, verts, mats, gamma_t, out_rgba, out_lin, counters,
-                             surf, shade, bvh_nodes, bvh_tris, cams, frame_stride);
+                             surf, shade, bvh_nodes, bvh_tris, cams, frame_stride RVCP_SPP_MAP_ARG);
 }
 #endif
 // the pre-pass with the specialised scan (rvcp_launch_games101_v3's spec_pre_fn)
@@ -3398,10 +3498,10 @@ extern "C" __global__ __launch_bounds__(kPrimaryBlock) void rvcp_spec_primary_ke
     float *__restrict__ out_lin, unsigned long long *__restrict__ counters,
     SurfRecord *__restrict__ surf, const FaceShade *__restrict__ shade,
     const Bvh4Node *__restrict__ bvh_nodes, const TriRecord *__restrict__ bvh_tris,
-    const float *__restrict__ cams, uint32_t frame_stride)
+    const float *__restrict__ cams, uint32_t frame_stride RVCP_SPP_MAP_PARAM)
 {
     primary_body<false, true>(A, tri, faces, verts, mats, gamma_t, out_rgba, out_lin, counters,
-                              surf, shade, bvh_nodes, bvh_tris, cams, frame_stride);
+                              surf, shade, bvh_nodes, bvh_tris, cams, frame_stride RVCP_SPP_MAP_ARG);
 }
 extern "C" __global__ __launch_bounds__(kBlock, kPathMinWaves) void rvcp_spec_path_kernel5(
     FrameArgs A, const TriRecord *__restrict__ tri, const MatRecord *__restrict__ mats,
@@ -3462,6 +3562,7 @@ extern "C" __global__ __launch_bounds__(kBlock, 6) void rvcp_spec_path_kernel6(
 
 #ifndef RVCP_JIT
 
+#if !RVCP_SPP_MAP   // (schedules 1 and 2 have no map build)
 extern "C" int rvcp_launch_games101(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
                                     const void *faces, const void *verts,
                                     const rvcp::MatRecord *mats, const rvcp::LightRecord *lights,
@@ -3475,6 +3576,7 @@ extern "C" int rvcp_launch_games101(const rvcp::FrameArgs *args, const rvcp::Tri
                        lights, gamma_t, out_rgba, out_lin, counters);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
+#endif
 
 extern "C" int rvcp_launch_games101_v3(const rvcp::FrameArgs *args, uint32_t n_frames,
                                        uint32_t frame_stride, const rvcp::TriRecord *tri,
@@ -3487,7 +3589,8 @@ extern "C" int rvcp_launch_games101_v3(const rvcp::FrameArgs *args, uint32_t n_f
                                        const rvcp::Bvh4Node *bvh_nodes,
                                        const rvcp::TriRecord *bvh_tris,
                                        uint32_t grid_blocks, void *stream, void *main_event,
-                                       void *spec_path_fn, const float *cams, void *spec_pre_fn)
+                                       void *spec_path_fn, const float *cams, void *spec_pre_fn
+                                       RVCP_SPP_MAP_PARAM)
 {
     const uint32_t pre_blocks = (args->n_pixels + rvcp::kPrimaryBlock - 1) / rvcp::kPrimaryBlock;
     auto pre = args->accel ? rvcp::games101_primary_kernel<true> : rvcp::games101_primary_kernel<false>;
@@ -3505,8 +3608,14 @@ extern "C" int rvcp_launch_games101_v3(const rvcp::FrameArgs *args, uint32_t n_f
             const rvcp::TriRecord *p_btris = bvh_tris;
             const float *p_cams = batch ? cams : nullptr;
             uint32_t p_stride = batch ? frame_stride : 0u;
+#if RVCP_SPP_MAP
+            void *params[] = {&a, &tri, &p_faces, &p_verts, &mats, &gamma_t, &out_rgba, &out_lin,
+                              &counters, &surf, &shade, &p_nodes, &p_btris, &p_cams, &p_stride,
+                              (void *)&spp_map};
+#else
             void *params[] = {&a, &tri, &p_faces, &p_verts, &mats, &gamma_t, &out_rgba, &out_lin,
                               &counters, &surf, &shade, &p_nodes, &p_btris, &p_cams, &p_stride};
+#endif
             if (hipModuleLaunchKernel((hipFunction_t)spec_pre_fn, pre_blocks, batch ? n_frames : 1u,
                                       1, rvcp::kPrimaryBlock, 1, 1, 0, (hipStream_t)stream, params,
                                       nullptr) != hipSuccess)
@@ -3516,14 +3625,14 @@ extern "C" int rvcp_launch_games101_v3(const rvcp::FrameArgs *args, uint32_t n_f
         hipLaunchKernelGGL(pre, dim3(pre_blocks, n_frames), dim3(rvcp::kPrimaryBlock), 0,
                            (hipStream_t)stream, args[0], tri, (const rvcp_face_t *)faces,
                            (const rvcp_vertex_t *)verts, mats, gamma_t, out_rgba, out_lin, counters,
-                           surf, shade, bvh_nodes, bvh_tris, cams, frame_stride);
+                           surf, shade, bvh_nodes, bvh_tris, cams, frame_stride RVCP_SPP_MAP_ARG);
     else
         for (uint32_t k = 0; k < n_frames; ++k)
             hipLaunchKernelGGL(pre, dim3(pre_blocks), dim3(rvcp::kPrimaryBlock), 0,
                                (hipStream_t)stream, args[k], tri, (const rvcp_face_t *)faces,
                                (const rvcp_vertex_t *)verts, mats, gamma_t, out_rgba, out_lin,
                                counters, surf, shade, bvh_nodes, bvh_tris, (const float *)nullptr,
-                               0u);
+                               0u RVCP_SPP_MAP_ARG);
     if (main_event && hipEventRecord((hipEvent_t)main_event, (hipStream_t)stream) != hipSuccess)
         return -2;
     if (spec_path_fn && args->accel) {
@@ -3569,7 +3678,7 @@ extern "C" int rvcp_launch_games101_v3(const rvcp::FrameArgs *args, uint32_t n_f
     // the frame's UNORM8 store from the linear colours (out_lin is never null here); a batch's
     // frames lie frame_stride pixels apart (the rows of a smaller shard's slot are padding)
     const uint32_t n_tone = n_frames > 1 ? n_frames * frame_stride : args->n_pixels;
-#if RVCP_SAMPLING
+#if RVCP_GAMES101_ONLY
     return rvcp_launch_tonemap(out_lin, n_tone, gamma_t, out_rgba, stream);   // the default object's
 #else
     uint32_t tb = (n_tone + rvcp::kToneBlock - 1) / rvcp::kToneBlock;
@@ -3580,7 +3689,7 @@ extern "C" int rvcp_launch_games101_v3(const rvcp::FrameArgs *args, uint32_t n_f
 #endif
 }
 
-#if !RVCP_SAMPLING
+#if !RVCP_GAMES101_ONLY
 extern "C" int rvcp_launch_gbuffer(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
                                    const rvcp::FaceShade *shade, const rvcp::Bvh4Node *bvh_nodes,
                                    const rvcp::TriRecord *bvh_tris, void *out, void *stream)
@@ -3622,7 +3731,7 @@ extern "C" int rvcp_launch_fill(uint32_t *out_rgba, float *out_lin, uint32_t n, 
                        out_rgba, out_lin, n, rgba);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
-#endif  // !RVCP_SAMPLING
+#endif  // !RVCP_GAMES101_ONLY
 
 extern "C" int rvcp_games101_occupancy(int variant, int *blocks_per_cu)
 {
@@ -3639,15 +3748,19 @@ extern "C" int rvcp_games101_occupancy(int variant, int *blocks_per_cu)
         ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::games101_path_kernel<6>, rvcp::kBlock, 0)
         : variant == 3
         ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::games101_path_kernel<rvcp::kPathMinWaves>, rvcp::kBlock, 0)
+#if RVCP_SPP_MAP
+        : hipErrorInvalidValue;             // schedules 1 and 2 have no map build
+#else
         : variant == 2
         ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::games101_dual_kernel, rvcp::kBlock, 0)
         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::games101_kernel, rvcp::kBlock, 0);
+#endif
     if (e != hipSuccess) return -2;
     *blocks_per_cu = b;
     return 0;
 }
 
-#if !RVCP_SAMPLING
+#if !RVCP_GAMES101_ONLY
 extern "C" int rvcp_launch_legacy(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
                                   const rvcp::FaceShade *shade, const void *spheres,
                                   const void *materials, const float *unorm_t, uint32_t *out_rgba,
@@ -3688,5 +3801,5 @@ extern "C" int rvcp_legacy_occupancy(int *blocks_per_cu)
     *blocks_per_cu = b;
     return 0;
 }
-#endif  // !RVCP_SAMPLING
+#endif  // !RVCP_GAMES101_ONLY
 #endif  // RVCP_JIT

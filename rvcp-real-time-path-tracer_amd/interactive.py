@@ -158,7 +158,8 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
                  dump_dir: Optional[str] = None, dump_format: str = "ppm",
                  on_fps: Optional[Callable[[int], None]] = None, denoise=None,
                  temporal=None, svgf=None, demodulate: Optional[bool] = None,
-                 taa: Optional[bool] = None, sampling: Optional[int] = None) -> dict:
+                 taa: Optional[bool] = None, sampling: Optional[int] = None,
+                 adaptive=None) -> dict:
     """``main_loop`` (ray_tracer.rs:22-100) without a window.
 
     Per frame: apply this frame's scripted events, count FPS (printed once a second as
@@ -183,6 +184,10 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
     ``sampling``: abi.SAMPLING_UNIFORM / abi.SAMPLING_COSINE sets ``tracer.sampling`` before the
     loop, so that every frame, through whichever chain, is traced with that bounce (DESIGN.md
     §4.17); None (default) leaves the tracer's mode as it is.
+    ``adaptive``: an ``abi.make_adaptive_params(...)`` record sets ``tracer.adaptive`` before the
+    loop (False switches it off), so that the ``svgf`` chain traces every frame through the
+    per-pixel sample counts planned from the previous frame's variance; None
+    (default) leaves the tracer's switch as it is.
     Returns per-frame render times and the final camera."""
     if demodulate is not None:
         tracer.demodulation = bool(demodulate)
@@ -190,6 +195,8 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
         tracer.taa = bool(taa)
     if sampling is not None:
         tracer.sampling = int(sampling)
+    if adaptive is not None:
+        tracer.adaptive = None if adaptive is False else adaptive
     info = RuntimeInfo(window_size=(width, height))
     by_frame: Dict[int, List[Event]] = {}
     for ev in events:

@@ -508,6 +508,74 @@ class RayTracer:
     def sampling(self, mode: int):
         self._check(self._lib.rvcp_set_sampling(self._ctx, int(mode)))
 
+    # adaptive sampling: per-pixel sample counts
+    def render_spp_map_async(self, push, width, height, d_spp_map: int, spp_hint: int, d_rgba: int,
+                             d_linear: int = 0, stream: int = 0):
+        """rvcp_render_spp_map_async: render_async with a per-pixel sample count -- d_spp_map holds
+        width * height uint32 in device memory, each clamped to 1..abi.SPP_MAP_MAX by the kernel;
+        cfg.spp is not read and spp_hint (1..abi.SPP_MAP_MAX) only steers the schedule and the
+        grid.  Every pixel is bit for bit the pixel of a frame rendered at spp = its count.  Wait
+        with wait() / sync_stats()."""
+        push = np.ascontiguousarray(push, dtype=PUSH_DTYPE)
+        self._push_keepalive = push
+        P = lambda a: ctypes.c_void_p(a) if a else None   # noqa: E731
+        self._check(self._lib.rvcp_render_spp_map_async(
+            self._ctx, abi.ptr(push), width, height, P(d_spp_map), int(spp_hint), P(d_rgba),
+            P(d_linear), P(stream)))
+
+    def spp_plan_async(self, d_variance: int, d_linear: int, d_len: int, d_gbuffer: int, width,
+                       height, d_spp_map_out: int, params=None, stream: int = 0):
+        """rvcp_spp_plan_async: enqueue the plan step -- the next frame's map (width * height
+        uint32 into d_spp_map_out) from a frame's variance, the colour it belongs to, its history
+        lengths (d_len 0: 1 everywhere) and its G-buffer, all in device memory (params:
+        abi.make_adaptive_params(...); None = the defaults).  Wait with spp_plan_wait()."""
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=abi.ADAPTIVE_PARAMS_DTYPE)
+        P = lambda a: ctypes.c_void_p(a) if a else None   # noqa: E731
+        self._check(self._lib.rvcp_spp_plan_async(
+            self._ctx, P(d_variance), P(d_linear), P(d_len), P(d_gbuffer), width, height,
+            abi.ptr(params), P(d_spp_map_out), P(stream)))
+
+    def spp_plan_wait(self):
+        """rvcp_spp_plan_wait: block until the last spp_plan_async is done; (its device time in
+        ms, the sum of the map it wrote)."""
+        ms, total = ctypes.c_float(0.0), ctypes.c_uint64(0)
+        self._check(self._lib.rvcp_spp_plan_wait(
+            self._ctx, ctypes.cast(ctypes.byref(ms), ctypes.c_void_p),
+            ctypes.cast(ctypes.byref(total), ctypes.c_void_p)))
+        return float(ms.value), int(total.value)
+
+    @property
+    def adaptive(self):
+        """The adaptive-sampling switch (rvcp_get_adaptive / rvcp_set_adaptive): None (off, the
+        default) or its abi.ADAPTIVE_PARAMS_DTYPE parameters.  While it is on, render_svgf traces
+        each frame through the per-pixel counts planned from the previous frame's variance (a
+        uniform map wherever its history restarts).  Setting it (params, or None for off) drops
+        the map, not the SVGF history."""
+        on = ctypes.c_int(0)
+        p = np.zeros((), dtype=abi.ADAPTIVE_PARAMS_DTYPE)
+        self._check(self._lib.rvcp_get_adaptive(
+            self._ctx, ctypes.cast(ctypes.byref(on), ctypes.c_void_p), abi.ptr(p)))
+        return p if on.value else None
+
+    @adaptive.setter
+    def adaptive(self, params):
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=abi.ADAPTIVE_PARAMS_DTYPE)
+            self._adaptive_keepalive = params
+        self._check(self._lib.rvcp_set_adaptive(self._ctx, abi.ptr(params)))
+
+    def adaptive_last_map(self) -> np.ndarray:
+        """rvcp_adaptive_last_map: the (rows, columns) uint32 map the last render_svgf frame was
+        traced with under the adaptive switch."""
+        w, h = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        pw = ctypes.cast(ctypes.byref(w), ctypes.c_void_p)
+        ph = ctypes.cast(ctypes.byref(h), ctypes.c_void_p)
+        self._check(self._lib.rvcp_adaptive_last_map(self._ctx, None, pw, ph))
+        out = np.empty((h.value, w.value), dtype=np.uint32)
+        self._check(self._lib.rvcp_adaptive_last_map(self._ctx, abi.ptr(out), pw, ph))
+        return out
+
     def _traced_size(self, width, height):
         """(rows, columns) of the frame render_temporal / render_svgf trace for a width x height
         call: the optional outputs other than the frame itself have this size."""
