@@ -37,6 +37,11 @@
 
 using namespace rvcp;
 
+// The static builds of the games101 kernels, [sampling][map] (rvcp_internal.h)
+const KernelBuild *const rvcp::kKernelBuilds[2][2] = {
+    {&rvcp_games101_build, &rvcp_games101_map_build},
+    {&rvcp_games101_cosine_build, &rvcp_games101_cosine_map_build}};
+
 // Experiment knobs (grid caps, fixed queue grabs, small-frame spreading, per-wave timelines,
 // generic-scan forcing) are read from the environment only in the debug build of the library
 // (make debug -> build/librvcp_debug.so, -DRVCP_DEBUG_KNOBS, used by tools/).  The product
@@ -134,16 +139,14 @@ struct rvcp_ctx {
     hipEvent_t evr = nullptr;
     bool gather_on_gstream = false;
     bool gather_pending = false;
-    int grid_capacity[kMaxVariant + 1] = {};   // resident workgroups per kernel variant
+    // resident workgroups per kernel variant and of the RVCP_ACCEL_BVH path kernel, for each
+    // build of the games101 kernels as kKernelBuilds indexes them: [sampling][map] (a map build
+    // has schedules 3-6 and 10 only; its other slots stay 0)
+    struct Capacity {
+        int grid[kMaxVariant + 1] = {};
+        int bvh = 0;
+    } capacity[2][2];
     int legacy_capacity = 0;                   // ... of the RVCP_INTEGRATOR_LEGACY kernel
-    int bvh_capacity = 0;                      // ... of the RVCP_ACCEL_BVH path kernel
-    // the same for the cosine builds of the games101 kernels (rvcp_kernels_cosine.hip)
-    int grid_capacity_cos[kMaxVariant + 1] = {};
-    int bvh_capacity_cos = 0;
-    // ... and for the map builds of the pre-pass family (rvcp_kernels_map.hip,
-    // rvcp_kernels_cosine_map.hip), by bounce sampling: schedules 3-6 and 10
-    int grid_capacity_map[2][kMaxVariant + 1] = {};
-    int bvh_capacity_map[2] = {};
     uint32_t n_simds = 1024;
 
     // scene (device)
@@ -170,22 +173,22 @@ struct rvcp_ctx {
     bool lights_same = false;      // every light record samples the same face
     bool rcp_fast = false;         // scan_rcp_fast_scene (FrameArgs::rcp_fast)
     bool has_metal = false;        // a material of type 1 (FrameArgs::has_metal)
-    // scene-specialised path kernels (rvcp_jit.cpp), or null: generic kernels
-    std::shared_ptr<JitKernels> jit;
+    // scene-specialised path kernels (rvcp_jit.cpp), or null: generic kernels.  By map: jit[0]
+    // serves the default renders, jit[1] the map renders (rvcp_render_spp_map_async,
+    // -DRVCP_SPP_MAP=1).
+    // The default slot is compiled at upload and records its error in jit_err.
+    std::shared_ptr<JitKernels> jit[2];
     std::string jit_err;
     // bounce sampling (rvcp_set_sampling).  A games101 module is compiled for
-    // one mode: jit_sampling is the mode ctx->jit was asked for, jit_tri / jit_bvh what upload
+    // one mode: jit_sampling[m] is the mode jit[m] was asked for, jit_tri / jit_bvh what upload
     // asked it with (empty: the scene gets no module), so that the first render after a switch
-    // can ask again for the other mode (jit_for_sampling)
+    // can ask again for the other mode (jit_for_render).
+    // The map slot is compiled by the first map render of a scene -- jit_sampling[1] is -1 before
+    // any (and after an upload) -- and its error is dropped.
     int32_t sampling = RVCP_SAMPLING_UNIFORM;
-    int32_t jit_sampling = RVCP_SAMPLING_UNIFORM;
+    int32_t jit_sampling[2] = {RVCP_SAMPLING_UNIFORM, -1};
     std::vector<TriRecord> jit_tri;
     bool jit_bvh = false;
-    // the scene's module for map renders (rvcp_render_spp_map_async, -DRVCP_SPP_MAP=1), compiled
-    // by the first one for the bounce sampling it runs with: jit_map_sampling is the mode jit_map
-    // was asked for, -1 before any (and after an upload)
-    std::shared_ptr<JitKernels> jit_map;
-    int32_t jit_map_sampling = -1;
     float light_total = 0.0f, light_pdf = 0.0f;
     bool has_scene = false;
 
@@ -550,9 +553,9 @@ void free_scene(rvcp_ctx *ctx)
     (void)hipFree(ctx->d_spheres); ctx->d_spheres = nullptr;
     (void)hipFree(ctx->d_bvh_nodes); ctx->d_bvh_nodes = nullptr;
     (void)hipFree(ctx->d_bvh_tris); ctx->d_bvh_tris = nullptr;
-    ctx->jit.reset();
-    ctx->jit_map.reset();
-    ctx->jit_map_sampling = -1;
+    ctx->jit[0].reset();
+    ctx->jit[1].reset();
+    ctx->jit_sampling[1] = -1;
     ctx->has_scene = false;
 }
 
@@ -679,7 +682,7 @@ const char *rvcp_internal_build_id(void)
 
 uint64_t rvcp_internal_module_key(const rvcp_ctx_t *ctx)
 {
-    return (ctx && ctx->jit) ? ctx->jit->key_hash : 0;
+    return (ctx && ctx->jit[0]) ? ctx->jit[0]->key_hash : 0;
 }
 
 static int impl_config_default_for(int32_t integrator, rvcp_config_t *cfg)
@@ -808,20 +811,17 @@ static int impl_create(const rvcp_config_t *cfg, rvcp_ctx_t **out_ctx)
         if (cap > 0 && cap < per_cu) per_cu = cap;
         return per_cu * cus;
     };
-    for (int v = 1; v <= kMaxVariant; v++) {
-        if (v == 7 || v == 8 || v == 9) continue;
-        ctx->grid_capacity[v] = capacity([v](int *n) { return rvcp_games101_occupancy(v, n); });
-        ctx->grid_capacity_cos[v] = capacity([v](int *n) { return rvcp_games101_occupancy_cosine(v, n); });
-    }
+    for (int sampling = 0; sampling < 2; sampling++)
+        for (int map = 0; map < 2; map++) {
+            const KernelBuild &build = *kKernelBuilds[sampling][map];
+            rvcp_ctx::Capacity &c = ctx->capacity[sampling][map];
+            for (int v = map ? 3 : 1; v <= kMaxVariant; v++) {   // (a map build: the pre-pass schedules only)
+                if (v == 7 || v == 8 || v == 9) continue;
+                c.grid[v] = capacity([&build, v](int *n) { return build.occupancy(v, n); });
+            }
+            c.bvh = capacity([&build](int *n) { return build.occupancy(kOccupancyBvh, n); });
+        }
     ctx->legacy_capacity = capacity(rvcp_legacy_occupancy);
-    ctx->bvh_capacity = capacity([](int *n) { return rvcp_games101_occupancy(kOccupancyBvh, n); });
-    ctx->bvh_capacity_cos = capacity([](int *n) { return rvcp_games101_occupancy_cosine(kOccupancyBvh, n); });
-    for (int v : {3, 4, 5, 6, 10}) {     // the map builds: the pre-pass schedules only
-        ctx->grid_capacity_map[0][v] = capacity([v](int *n) { return rvcp_games101_occupancy_map(v, n); });
-        ctx->grid_capacity_map[1][v] = capacity([v](int *n) { return rvcp_games101_occupancy_cosine_map(v, n); });
-    }
-    ctx->bvh_capacity_map[0] = capacity([](int *n) { return rvcp_games101_occupancy_map(kOccupancyBvh, n); });
-    ctx->bvh_capacity_map[1] = capacity([](int *n) { return rvcp_games101_occupancy_cosine_map(kOccupancyBvh, n); });
     if (cfg->n_gpus > 1) {   // one sub-context per further GPU (shards 1..N-1)
         for (int i = 1; i < cfg->n_gpus; i++) {
             rvcp_config_t sub_cfg = *cfg;
@@ -895,8 +895,8 @@ static int impl_destroy(rvcp_ctx_t *ctx)
         // still abort it); the host side is freed
         g_create_error = "rvcp_destroy: a gather (or its communicator's abort) is still stuck "
                          "after the deadline; the context's device memory and streams are leaked";
-        new std::shared_ptr<JitKernels>(std::move(ctx->jit));   // never unloaded
-        new std::shared_ptr<JitKernels>(std::move(ctx->jit_map));
+        new std::shared_ptr<JitKernels>(std::move(ctx->jit[0]));   // never unloaded
+        new std::shared_ptr<JitKernels>(std::move(ctx->jit[1]));
         delete ctx;
         return RVCP_E_TIMEOUT;
     }
@@ -1052,8 +1052,10 @@ static int upload_one(rvcp_ctx_t *ctx, const rvcp_material_t *materials, uint32_
             if (K < 8 || n_faces - K < 64 || !jit_scene_in_range(tri.data(), K)) K = 0;
             if (K) {
                 std::string jerr;
-                bvh_jit = jit_path_kernels(ctx->device, tri.data(), K, jerr, false, n_spheres == 0,
-                                           false, true, nullptr, 0, 64, ctx->sampling);
+                JitSpec spec;
+                spec.bvh = true;
+                spec.sampling = ctx->sampling;
+                bvh_jit = jit_path_kernels(ctx->device, tri.data(), K, spec, jerr);
                 HIP_TRY(ctx, hipSetDevice(ctx->device));
                 if (!bvh_jit || !bvh_jit->bvh_path || !bvh_jit->bvh_primary) {
                     K = 0;
@@ -1101,15 +1103,17 @@ static int upload_one(rvcp_ctx_t *ctx, const rvcp_material_t *materials, uint32_
         ctx->bvh_depth = depth;
     }
     // scene-specialised scan: compiled here, once per scene and process
-    ctx->jit.reset();
+    // Both slots are reset by an upload: the default one is filled here, the map one by the
+    // first map render of this scene (jit_sampling[1] = -1).
+    ctx->jit[0].reset();
+    ctx->jit[1].reset();
     ctx->jit_err.clear();
     ctx->jit_tri.clear();
     ctx->jit_bvh = false;
-    ctx->jit_sampling = ctx->sampling;
-    ctx->jit_map.reset();                     // (compiled by the first map render of this scene)
-    ctx->jit_map_sampling = -1;
+    ctx->jit_sampling[0] = ctx->sampling;
+    ctx->jit_sampling[1] = -1;
     if (bvh_jit) {                            // the BVH hybrid's module (above)
-        ctx->jit = bvh_jit;
+        ctx->jit[0] = bvh_jit;
         ctx->jit_tri.assign(tri.begin(), tri.begin() + ctx->bvh_prefix);
         ctx->jit_bvh = true;
     }
@@ -1117,9 +1121,15 @@ static int upload_one(rvcp_ctx_t *ctx, const rvcp_material_t *materials, uint32_
         n_faces >= 1 && n_faces <= kJitMaxFaces && jit_scene_in_range(tri.data(), n_faces) &&
         !RVCP_KNOB("RVCP_NO_SPECIALIZE")) {
         const bool legacy = ctx->cfg.integrator == RVCP_INTEGRATOR_LEGACY;
-        ctx->jit = jit_path_kernels(ctx->device, tri.data(), n_faces, ctx->jit_err, legacy,
-                                    n_spheres == 0, n_spheres <= 64 && n_materials <= 64, false,
-                                    spheres, n_spheres, n_materials, ctx->sampling);
+        JitSpec spec;
+        spec.legacy = legacy;
+        spec.sphereless = n_spheres == 0;
+        spec.lds_fits = n_spheres <= 64 && n_materials <= 64;
+        spec.sampling = ctx->sampling;
+        spec.spheres = spheres;
+        spec.n_spheres = n_spheres;
+        spec.n_materials = n_materials;
+        ctx->jit[0] = jit_path_kernels(ctx->device, tri.data(), n_faces, spec, ctx->jit_err);
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         if (!legacy) ctx->jit_tri = tri;      // (mode 2 has one sampling: nothing to ask again)
     }
@@ -1165,39 +1175,28 @@ uint32_t rvcp_shard_rows(uint32_t height, uint32_t shard_index, uint32_t shard_c
     return rows;
 }
 
-// The scene's specialised module for the context's bounce sampling, asked for again with what
-// upload asked (jit_tri, jit_bvh) by the first render after rvcp_set_sampling changed the mode:
+// The scene's specialised module for a default or a map render with the context's bounce
+// sampling, asked for again with what upload asked (jit_tri, jit_bvh) by the first such render
+// after rvcp_set_sampling changed the mode -- for a map render also by the first of the scene:
 // from the process's module cache, the disk cache, or hipRTC.  Without one (no module for this
-// scene, or the compilation failed) the generic kernels of the mode run; a module of the other
-// mode is never kept.
-static void jit_for_sampling(rvcp_ctx_t *ctx)
+// scene, or the compilation failed) the generic kernels of that build run; a module of the other
+// mode is never kept.  The default slot's error goes to jit_err; the map slot's is dropped.
+static void jit_for_render(rvcp_ctx_t *ctx, bool map)
 {
-    ctx->jit_sampling = ctx->sampling;
+    ctx->jit_sampling[map] = ctx->sampling;
     if (ctx->jit_tri.empty()) return;
-    ctx->jit.reset();
-    ctx->jit_err.clear();
-    ctx->jit = jit_path_kernels(ctx->device, ctx->jit_tri.data(), (uint32_t)ctx->jit_tri.size(),
-                                ctx->jit_err, false, false, false, ctx->jit_bvh, nullptr, 0, 64,
-                                ctx->sampling);
+    std::shared_ptr<JitKernels> &jit = ctx->jit[map];
+    jit.reset();
+    std::string map_err;
+    if (!map) ctx->jit_err.clear();
+    JitSpec spec;
+    spec.bvh = ctx->jit_bvh;
+    spec.sampling = ctx->sampling;
+    spec.spp_map = map;
+    jit = jit_path_kernels(ctx->device, ctx->jit_tri.data(), (uint32_t)ctx->jit_tri.size(), spec,
+                           map ? map_err : ctx->jit_err);
     (void)hipSetDevice(ctx->device);
-    if (ctx->jit_bvh && ctx->jit && (!ctx->jit->bvh_path || !ctx->jit->bvh_primary)) ctx->jit.reset();
-}
-
-// The scene's specialised module for map renders (rvcp_render_spp_map_async) with the context's
-// bounce sampling, asked for as jit_for_sampling asks, with -DRVCP_SPP_MAP=1: by the first map
-// render of the scene in that mode.  Without one the generic map kernels run.
-static void jit_for_map(rvcp_ctx_t *ctx)
-{
-    ctx->jit_map_sampling = ctx->sampling;
-    ctx->jit_map.reset();
-    if (ctx->jit_tri.empty()) return;
-    std::string err;
-    ctx->jit_map = jit_path_kernels(ctx->device, ctx->jit_tri.data(), (uint32_t)ctx->jit_tri.size(),
-                                    err, false, false, false, ctx->jit_bvh, nullptr, 0, 64,
-                                    ctx->sampling, true);
-    (void)hipSetDevice(ctx->device);
-    if (ctx->jit_bvh && ctx->jit_map && (!ctx->jit_map->bvh_path || !ctx->jit_map->bvh_primary))
-        ctx->jit_map.reset();
+    if (ctx->jit_bvh && jit && (!jit->bvh_path || !jit->bvh_primary)) jit.reset();
 }
 
 // What plan_frame (rvcp_frame_plan.cpp) decides a render from: the config, the scene, the device's
@@ -1221,14 +1220,11 @@ static FramePlanIn frame_plan_input(const rvcp_ctx_t *ctx, uint32_t n_frames, ui
     in.n_faces = ctx->n_faces;
     in.bvh_prefix = ctx->bvh_prefix;
     in.n_simds = ctx->n_simds;
-    std::memcpy(in.grid_capacity,
-                map ? ctx->grid_capacity_map[cosine ? 1 : 0]
-                    : cosine ? ctx->grid_capacity_cos : ctx->grid_capacity,
-                sizeof(in.grid_capacity));
-    in.bvh_capacity = map ? ctx->bvh_capacity_map[cosine ? 1 : 0]
-                          : cosine ? ctx->bvh_capacity_cos : ctx->bvh_capacity;
+    const rvcp_ctx::Capacity &cap = ctx->capacity[cosine][map];
+    std::memcpy(in.grid_capacity, cap.grid, sizeof(in.grid_capacity));
+    in.bvh_capacity = cap.bvh;
     in.legacy_capacity = ctx->legacy_capacity;
-    if (const JitKernels *jk = map ? ctx->jit_map.get() : ctx->jit.get()) {
+    if (const JitKernels *jk = ctx->jit[map].get()) {
         in.module = true;
         in.blocks_per_cu5 = jk->blocks_per_cu5;
         in.blocks_per_cu6 = jk->blocks_per_cu6;
@@ -1283,16 +1279,12 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
     // the cosine-weighted bounce (rvcp_set_sampling): its kernels, and a
     // specialised module compiled for it
     const bool cosine = ctx->sampling == RVCP_SAMPLING_COSINE;
-    if (map) {
-        if (ctx->jit_map_sampling != ctx->sampling) jit_for_map(ctx);
-    } else if (ctx->jit_sampling != ctx->sampling) {
-        jit_for_sampling(ctx);
-    }
+    if (ctx->jit_sampling[map] != ctx->sampling) jit_for_render(ctx, map);
 
     // the plan: schedule, specialised kernels and grid (rvcp_frame_plan.cpp)
     const uint32_t frame_px = rvcp_shard_rows(height, shard_index, shard_count) * width;
     const uint32_t split_px = frame_px * n_frames;          // the queue of the whole batch
-    const JitKernels *jk = map ? ctx->jit_map.get() : ctx->jit.get();
+    const JitKernels *jk = ctx->jit[map].get();
     const FramePlanIn in = frame_plan_input(ctx, n_frames, frame_px, stride, map ? spp_hint : 0u);
     const FramePlan P = plan_frame(in);
     if (map && P.status == RVCP_OK && !P.trivial && !P.legacy && P.variant < 3)
@@ -1417,34 +1409,43 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
         launch_rc = rvcp_launch_legacy(&A, ctx->d_tri, ctx->d_shade, ctx->d_spheres, ctx->d_rawmats,
                                        ctx->d_unorm, (uint32_t *)d_rgba8, lin, ctx->d_counters,
                                        P.blocks, s, P.spec_legacy ? (void *)jk->legacy : nullptr);
-    } else if (map) {
-        // the map builds of the pre-pass family (P.variant >= 3: checked above)
-        launch_rc = (cosine ? rvcp_launch_games101_v3_cosine_map : rvcp_launch_games101_v3_map)(
-            FA.data(), 1, stride, ctx->d_tri, ctx->d_faces, ctx->d_verts, ctx->d_mats,
-            ctx->d_lights, ctx->d_gamma, (uint32_t *)d_rgba8, lin, ctx->d_counters, ctx->d_surf,
-            ctx->d_shade, ctx->d_bvh_nodes, ctx->d_bvh_tris, P.blocks, s, ctx->evm,
-            P.spec ? (void *)(P.variant == 6 ? jk->path6 : jk->path5)
-                   : P.spec_bvh ? (void *)jk->bvh_path : nullptr,
-            nullptr,
-            P.spec && jit_spec_prepass() ? (void *)jk->primary
-                                         : P.spec_bvh ? (void *)jk->bvh_primary : nullptr,
-            d_spp_map);
-    } else if (P.variant >= 3) {
-        // (the launcher records evm itself, between the pre-pass and the path kernel)
-        launch_rc = (cosine ? rvcp_launch_games101_v3_cosine : rvcp_launch_games101_v3)(
-            FA.data(), n_frames, stride, ctx->d_tri, ctx->d_faces, ctx->d_verts, ctx->d_mats,
-            ctx->d_lights, ctx->d_gamma, (uint32_t *)d_rgba8, lin, ctx->d_counters, ctx->d_surf,
-            ctx->d_shade, ctx->d_bvh_nodes, ctx->d_bvh_tris, P.blocks, s, ctx->evm,
-            P.spec ? (void *)(P.variant == 6 ? jk->path6 : jk->path5)
-                   : P.spec_bvh ? (void *)jk->bvh_path : nullptr,
-            P.prepass_batched ? ctx->d_cams : nullptr,
-            P.spec && jit_spec_prepass() ? (void *)jk->primary
-                                         : P.spec_bvh ? (void *)jk->bvh_primary : nullptr);
     } else {
-        HIP_TRY(ctx, hipEventRecord(ctx->evm, s));
-        launch_rc = (cosine ? rvcp_launch_games101_cosine : rvcp_launch_games101)(
-            &A, ctx->d_tri, ctx->d_faces, ctx->d_verts, ctx->d_mats, ctx->d_lights, ctx->d_gamma,
-            (uint32_t *)d_rgba8, (float *)d_linear_rgb, ctx->d_counters, P.blocks, s);
+        // the games101 kernels of the context's build (kKernelBuilds; a map render has
+        // P.variant >= 3: checked above)
+        const KernelBuild &build = *kKernelBuilds[cosine][map];
+        PathLaunch L{};
+        L.args = FA.data();
+        L.n_frames = n_frames;
+        L.frame_stride = stride;
+        L.tri = ctx->d_tri;
+        L.faces = ctx->d_faces;
+        L.verts = ctx->d_verts;
+        L.mats = ctx->d_mats;
+        L.lights = ctx->d_lights;
+        L.gamma_t = ctx->d_gamma;
+        L.out_rgba = (uint32_t *)d_rgba8;
+        L.out_lin = lin;
+        L.counters = ctx->d_counters;
+        L.surf = ctx->d_surf;
+        L.shade = ctx->d_shade;
+        L.bvh_nodes = ctx->d_bvh_nodes;
+        L.bvh_tris = ctx->d_bvh_tris;
+        L.grid_blocks = P.blocks;
+        L.stream = s;
+        L.main_event = ctx->evm;
+        L.spec_path_fn = P.spec ? (void *)(P.variant == 6 ? jk->path6 : jk->path5)
+                                : P.spec_bvh ? (void *)jk->bvh_path : nullptr;
+        L.spec_pre_fn = P.spec && jit_spec_prepass() ? (void *)jk->primary
+                                                     : P.spec_bvh ? (void *)jk->bvh_primary : nullptr;
+        L.cams = P.prepass_batched ? ctx->d_cams : nullptr;
+        L.spp_map = d_spp_map;
+        if (P.variant >= 3) {
+            // (the launcher records evm itself, between the pre-pass and the path kernel)
+            launch_rc = build.launch_prepass(L);
+        } else {
+            HIP_TRY(ctx, hipEventRecord(ctx->evm, s));
+            launch_rc = build.launch(L);
+        }
     }
     if (launch_rc != 0) return fail(ctx, RVCP_E_HIP, std::string("kernel launch failed: ") +
                                                          hipGetErrorString(hipGetLastError()));

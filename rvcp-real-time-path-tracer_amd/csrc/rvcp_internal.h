@@ -100,7 +100,7 @@ constexpr uint64_t kWideMinSamples = 8ull << 20;   // auto: variant 6 from 8 Msa
 // profiles/history/r04pb_ab_prebatch.log).
 constexpr uint32_t kPrepassBatchMaxPixels = 512u * 1024u;
 constexpr uint64_t kSpecWideMinSamples = 256ull << 20;
-constexpr int kOccupancyBvh = 100;          // rvcp_games101_occupancy code of the BVH kernel
+constexpr int kOccupancyBvh = 100;          // KernelBuild::occupancy code of the BVH kernel
 #ifndef RVCP_TILE
 #define RVCP_TILE 256
 #endif
@@ -348,72 +348,56 @@ uint32_t bvh_big_prefix(const float (*pos)[3][3], uint32_t n, uint32_t cap);
 }  // namespace rvcp
 
 #ifndef __HIPCC_RTC__
-// Launchers (defined in rvcp_kernels.hip), called by rvcp_host.cpp.
+namespace rvcp {
+// One launch of the games101 kernels.  The pre-pass family (schedules 3-6, 10, the BVH path
+// kernel) reads all of it: args[0 .. n_frames) is one FrameArgs per frame of the batch (pix_base =
+// k x frame_stride); one pre-pass per frame into one surface list, main_event recorded, one path
+// kernel, one tone map over n_frames x frame_stride pixels (n_pixels when n_frames == 1).
+// Schedules 1 and 2 read args[0], the scene, the outputs, counters, grid_blocks and stream.
+struct PathLaunch {
+    const FrameArgs *args;
+    uint32_t n_frames, frame_stride;
+    const TriRecord *tri;
+    const void *faces, *verts;
+    const MatRecord *mats;
+    const LightRecord *lights;
+    const float *gamma_t;
+    uint32_t *out_rgba;
+    float *out_lin;
+    unsigned long long *counters;
+    SurfRecord *surf;
+    const FaceShade *shade;
+    const Bvh4Node *bvh_nodes;
+    const TriRecord *bvh_tris;
+    uint32_t grid_blocks;
+    void *stream, *main_event;
+    // the scene-specialised path kernel and pre-pass (rvcp_jit.cpp), or null for the built-in
+    // ones; their module must have been compiled for this build (JitSpec's sampling and spp_map)
+    void *spec_path_fn, *spec_pre_fn;
+    const float *cams;          // a batch's cameras in device memory: one pre-pass launch, or null
+    // a map build (RVCP_SPP_MAP = 1): the frame's per-pixel sample counts,
+    // n_pixels words of device memory, clamped by the pre-pass; null otherwise
+    const uint32_t *spp_map;
+};
+// One static build of the games101 kernels: rvcp_kernels.hip compiled per bounce sampling
+// (RVCP_SAMPLING) and with or without the per-pixel sample count (RVCP_SPP_MAP).
+struct KernelBuild {
+    int (*launch)(const PathLaunch &);           // schedules 1 and 2; null in a map build
+    int (*launch_prepass)(const PathLaunch &);   // the pre-pass family
+    // resident workgroups per CU of a schedule's kernel, or of the BVH path kernel
+    // (kOccupancyBvh); a map build knows schedules 3, 4, 5, 6, 10 and kOccupancyBvh
+    int (*occupancy)(int variant, int *blocks_per_cu);
+};
+// kKernelBuilds[sampling][map] (rvcp_host.cpp), over the one object each of rvcp_kernels.hip,
+// rvcp_kernels_map.hip, rvcp_kernels_cosine.hip and rvcp_kernels_cosine_map.hip exports
+extern const KernelBuild *const kKernelBuilds[2][2];
+}  // namespace rvcp
+
+// The launchers every build shares (defined in rvcp_kernels.hip and the post-process files),
+// called by rvcp_host.cpp.
 extern "C" {
-int rvcp_launch_games101(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
-                         const void *faces, const void *verts, const rvcp::MatRecord *mats,
-                         const rvcp::LightRecord *lights, const float *gamma_t,
-                         uint32_t *out_rgba, float *out_lin, unsigned long long *counters,
-                         uint32_t grid_blocks, void *stream);
-// args[0 .. n_frames): one FrameArgs per frame of the batch (pix_base = k x frame_stride);
-// one pre-pass per frame into one surface list, one path kernel, one tone map over
-// n_frames x frame_stride pixels (n_pixels when n_frames == 1).  spec_path_fn / spec_pre_fn:
-// the scene-specialised path kernel and pre-pass (rvcp_jit.cpp), or null for the built-in ones
-int rvcp_launch_games101_v3(const rvcp::FrameArgs *args, uint32_t n_frames, uint32_t frame_stride,
-                            const rvcp::TriRecord *tri,
-                            const void *faces, const void *verts, const rvcp::MatRecord *mats,
-                            const rvcp::LightRecord *lights, const float *gamma_t,
-                            uint32_t *out_rgba, float *out_lin, unsigned long long *counters,
-                            rvcp::SurfRecord *surf, const rvcp::FaceShade *shade,
-                            const rvcp::Bvh4Node *bvh_nodes, const rvcp::TriRecord *bvh_tris,
-                            uint32_t grid_blocks, void *stream, void *main_event,
-                            void *spec_path_fn, const float *cams, void *spec_pre_fn = nullptr);
-// The same three for RVCP_SAMPLING_COSINE (rvcp_kernels_cosine.hip: the games101 kernels built
-// with the cosine-weighted bounce); a specialised module passed to the second
-// must have been compiled for that mode too (jit_path_kernels' `sampling`).
-int rvcp_launch_games101_cosine(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
-                                const void *faces, const void *verts, const rvcp::MatRecord *mats,
-                                const rvcp::LightRecord *lights, const float *gamma_t,
-                                uint32_t *out_rgba, float *out_lin, unsigned long long *counters,
-                                uint32_t grid_blocks, void *stream);
-int rvcp_launch_games101_v3_cosine(const rvcp::FrameArgs *args, uint32_t n_frames,
-                                   uint32_t frame_stride, const rvcp::TriRecord *tri,
-                                   const void *faces, const void *verts, const rvcp::MatRecord *mats,
-                                   const rvcp::LightRecord *lights, const float *gamma_t,
-                                   uint32_t *out_rgba, float *out_lin, unsigned long long *counters,
-                                   rvcp::SurfRecord *surf, const rvcp::FaceShade *shade,
-                                   const rvcp::Bvh4Node *bvh_nodes, const rvcp::TriRecord *bvh_tris,
-                                   uint32_t grid_blocks, void *stream, void *main_event,
-                                   void *spec_path_fn, const float *cams, void *spec_pre_fn);
-int rvcp_games101_occupancy_cosine(int variant, int *blocks_per_cu);
-// The pre-pass family with a per-pixel sample count (rvcp_kernels_map.hip,
-// rvcp_kernels_cosine_map.hip: RVCP_SPP_MAP = 1), per bounce sampling: the
-// launcher takes the frame's map (n_pixels words of device memory, clamped by the pre-pass) and
-// a specialised module passed to it must have been compiled with the map too; the occupancy
-// query knows schedules 3, 4, 5, 6, 10 and kOccupancyBvh.
-int rvcp_launch_games101_v3_map(const rvcp::FrameArgs *args, uint32_t n_frames,
-                                uint32_t frame_stride, const rvcp::TriRecord *tri,
-                                const void *faces, const void *verts, const rvcp::MatRecord *mats,
-                                const rvcp::LightRecord *lights, const float *gamma_t,
-                                uint32_t *out_rgba, float *out_lin, unsigned long long *counters,
-                                rvcp::SurfRecord *surf, const rvcp::FaceShade *shade,
-                                const rvcp::Bvh4Node *bvh_nodes, const rvcp::TriRecord *bvh_tris,
-                                uint32_t grid_blocks, void *stream, void *main_event,
-                                void *spec_path_fn, const float *cams, void *spec_pre_fn,
-                                const uint32_t *spp_map);
-int rvcp_launch_games101_v3_cosine_map(const rvcp::FrameArgs *args, uint32_t n_frames,
-                                       uint32_t frame_stride, const rvcp::TriRecord *tri,
-                                       const void *faces, const void *verts,
-                                       const rvcp::MatRecord *mats, const rvcp::LightRecord *lights,
-                                       const float *gamma_t, uint32_t *out_rgba, float *out_lin,
-                                       unsigned long long *counters, rvcp::SurfRecord *surf,
-                                       const rvcp::FaceShade *shade, const rvcp::Bvh4Node *bvh_nodes,
-                                       const rvcp::TriRecord *bvh_tris, uint32_t grid_blocks,
-                                       void *stream, void *main_event, void *spec_path_fn,
-                                       const float *cams, void *spec_pre_fn,
-                                       const uint32_t *spp_map);
-int rvcp_games101_occupancy_map(int variant, int *blocks_per_cu);
-int rvcp_games101_occupancy_cosine_map(int variant, int *blocks_per_cu);
+extern const rvcp::KernelBuild rvcp_games101_build, rvcp_games101_map_build,
+    rvcp_games101_cosine_build, rvcp_games101_cosine_map_build;
 // Integrator RVCP_INTEGRATOR_LEGACY (ray_tracer.comp): materials / spheres are the raw
 // rvcp_material_t / rvcp_sphere_t arrays, unorm_t the UNORM8 threshold table.
 int rvcp_launch_legacy(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
@@ -507,6 +491,5 @@ int rvcp_launch_assemble(const uint32_t *gathered, uint32_t slot_rows, uint32_t 
                          uint32_t height, uint32_t shard_count, uint32_t *frame, void *stream);
 int rvcp_launch_fill(uint32_t *out_rgba, float *out_lin, uint32_t n_pixels, uint32_t rgba,
                      void *stream);
-int rvcp_games101_occupancy(int variant, int *blocks_per_cu);
 }
 #endif  // __HIPCC_RTC__

@@ -779,8 +779,7 @@ unsigned jit_scan_opts()
     return opts;
 }
 
-std::vector<std::string> jit_options(bool legacy, int legacy_waves, bool lds_scene, bool bvh,
-                                     int sampling = 0, bool spp_map = false);
+std::vector<std::string> jit_options(const JitCompile &cc);
 
 // The line a module's source ends with for a bounce sampling other than the default: the
 // process-wide module cache is keyed by the source text, so the two modes' modules differ in it.
@@ -944,14 +943,13 @@ void disk_write(const std::string &dir, const std::string &key, const std::vecto
 // found the disk entry unusable (the runtime refused it) -- count it rejected, compile, overwrite.
 // With g_mu held.
 int jit_cached_code(const std::string &scan, std::vector<char> &code, std::string &err,
-                    bool legacy, int legacy_waves, bool lds_scene, bool bvh, bool *from_disk,
-                    bool force_compile, int sampling, bool spp_map)
+                    const JitCompile &cc, bool *from_disk, bool force_compile)
 {
     *from_disk = false;
     const std::string dir = cache_dir();
     std::string key;
     if (!dir.empty()) {
-        key = code_key(scan, jit_options(legacy, legacy_waves, lds_scene, bvh, sampling, spp_map));
+        key = code_key(scan, jit_options(cc));
         if (force_compile) {
             g_disk_rejects++;
         } else {
@@ -964,8 +962,7 @@ int jit_cached_code(const std::string &scan, std::vector<char> &code, std::strin
             if (r < 0) g_disk_rejects++;
         }
     }
-    if (jit_compile_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, sampling, spp_map) != 0)
-        return -1;
+    if (jit_compile_code(scan, code, err, cc) != 0) return -1;
     g_disk_compiles++;
     if (!dir.empty()) disk_write(dir, key, code);
     return 0;
@@ -984,32 +981,32 @@ JitKernels::~JitKernels()
 
 // The hipRTC options of a module: the flags of the static build (Makefile), on which the
 // numeric contract depends, and the module's variant defines.
-std::vector<std::string> jit_options(bool legacy, int legacy_waves, bool lds_scene, bool bvh,
-                                     int sampling, bool spp_map)
+std::vector<std::string> jit_options(const JitCompile &cc)
 {
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17",
                                      "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
                                      "-fno-fast-math", "-fno-slp-vectorize", "-DRVCP_JIT",
                                      "-DRVCP_SPEC_SCAN=\"rvcp_spec_scan.inc\""};
-    if (legacy) opts.push_back("-DRVCP_JIT_LEGACY");
-    if (bvh) opts.push_back("-DRVCP_JIT_BVH");
+    if (cc.legacy) opts.push_back("-DRVCP_JIT_LEGACY");
+    if (cc.bvh) opts.push_back("-DRVCP_JIT_BVH");
     // the games101 kernels' bounce (rvcp_set_sampling): the default modules get no define, so
     // their options and keys are the ones they always had
-    if (sampling != RVCP_SAMPLING_UNIFORM) opts.push_back("-DRVCP_SAMPLING=" + std::to_string(sampling));
+    if (cc.sampling != RVCP_SAMPLING_UNIFORM)
+        opts.push_back("-DRVCP_SAMPLING=" + std::to_string(cc.sampling));
     // the pre-pass family with a per-pixel sample count (rvcp_render_spp_map_async), likewise
-    if (spp_map) opts.push_back("-DRVCP_SPP_MAP=1");
+    if (cc.spp_map) opts.push_back("-DRVCP_SPP_MAP=1");
 #ifdef RVCP_TIMELINE
     opts.push_back("-DRVCP_TIMELINE");      // the debug library's modules keep the per-wave timeline
 #endif
-    if (legacy && legacy_waves > 0) opts.push_back("-DRVCP_LEGACY_MIN_WAVES=" + std::to_string(legacy_waves));
-    if (legacy && lds_scene) opts.push_back("-DRVCP_LEGACY_LDS_SCENE");
+    if (cc.legacy && cc.legacy_waves > 0)
+        opts.push_back("-DRVCP_LEGACY_MIN_WAVES=" + std::to_string(cc.legacy_waves));
+    if (cc.legacy && cc.lds_scene) opts.push_back("-DRVCP_LEGACY_LDS_SCENE");
     for (const std::string &x : jit_extra_flags()) opts.push_back(x);
     return opts;
 }
 
 int jit_compile_code(const std::string &scan, std::vector<char> &code, std::string &err,
-                     bool legacy, int legacy_waves, bool lds_scene, bool bvh, int sampling,
-                     bool spp_map)
+                     const JitCompile &cc)
 {
     const RtcApi &api = rtc();
     if (!api.ok) {
@@ -1024,8 +1021,7 @@ int jit_compile_code(const std::string &scan, std::vector<char> &code, std::stri
         err = "hiprtcCreateProgram failed";
         return -1;
     }
-    const std::vector<std::string> opt_s =
-        jit_options(legacy, legacy_waves, lds_scene, bvh, sampling, spp_map);
+    const std::vector<std::string> opt_s = jit_options(cc);
     std::vector<const char *> opts;
     for (const std::string &x : opt_s) opts.push_back(x.c_str());
     const int rc = api.compile(prog, (int)opts.size(), opts.data());
@@ -1046,11 +1042,9 @@ int jit_compile_code(const std::string &scan, std::vector<char> &code, std::stri
     return cs ? 0 : -1;
 }
 
-std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, uint32_t n,
-                                             std::string &err, bool legacy, bool sphereless,
-                                             bool lds_fits, bool bvh, const rvcp_sphere_t *spheres,
-                                             uint32_t n_spheres, uint32_t n_materials, int sampling,
-                                             bool spp_map)
+// A module's source text -- its scan and one tag line per variant: the text the process-wide
+// module cache is keyed by -- and what it is compiled with.
+std::string jit_module_source(const TriRecord *tri, uint32_t n, const JitSpec &spec, JitCompile &cc)
 {
     // Mode 2 on a scene without spheres (the Cornell frame): 6 waves per SIMD measured 2.5 %
     // faster than 5, with spheres 5 % slower (profiles/history/r02_legacy_waves_ab.log).  With the
@@ -1058,26 +1052,39 @@ std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, u
     // 0.308; 5 waves without LDS 0.290), the Cornell frame 1.867 -> 1.831 ms at 6
     // (profiles/history/r04d_ab_m2.log, r04e_ab_m2b.log).
     // (debug build: RVCP_JIT_LEGACY_WAVES overrides; 0 = the compiler's choice)
-    const bool lds_scene = legacy && lds_fits;
+    cc = JitCompile{};
+    cc.legacy = spec.legacy;
+    cc.lds_scene = spec.legacy && spec.lds_fits;
 #ifndef RVCP_SPHERELESS_LEGACY_WAVES   // (A/B variants only, tools/build_variant.sh)
 #define RVCP_SPHERELESS_LEGACY_WAVES 6
 #endif
-    int legacy_waves = legacy && sphereless ? RVCP_SPHERELESS_LEGACY_WAVES : lds_scene ? 5 : 0;
+    cc.legacy_waves = spec.legacy && spec.sphereless ? RVCP_SPHERELESS_LEGACY_WAVES : cc.lds_scene ? 5 : 0;
 #ifdef RVCP_DEBUG_KNOBS
-    if (const char *e = std::getenv("RVCP_JIT_LEGACY_WAVES")) legacy_waves = std::atoi(e);
+    if (const char *e = std::getenv("RVCP_JIT_LEGACY_WAVES")) cc.legacy_waves = std::atoi(e);
 #endif
+    cc.bvh = spec.bvh;
+    cc.sampling = spec.sampling;
+    cc.spp_map = spec.spp_map;
     std::string key_flags;
     for (const std::string &x : jit_extra_flags()) key_flags += " " + x;
-    const std::string scan = jit_scan_source(tri, n, jit_scan_opts()) +
-        (legacy ? "// +legacy " + std::to_string(legacy_waves) + (lds_scene ? " lds" : "") + "\n"
+    return jit_scan_source(tri, n, jit_scan_opts()) +
+        (spec.legacy ? "// +legacy " + std::to_string(cc.legacy_waves) + (cc.lds_scene ? " lds" : "") + "\n"
 #ifndef RVCP_NO_SPHERE_LITERALS     // (A/B variant only, tools/build_variant.sh)
-                      + jit_sphere_source(spheres, n_spheres)
+                      + jit_sphere_source(spec.spheres, spec.n_spheres)
 #endif
-                      + (lds_scene ? jit_legacy_lds_source(n, n_spheres, n_materials) : std::string())
+                      + (cc.lds_scene ? jit_legacy_lds_source(n, spec.n_spheres, spec.n_materials) : std::string())
                 : std::string()) +
         (key_flags.empty() ? std::string() : "// +flags" + key_flags + "\n") +
-        (bvh ? "// +bvh\n" : "") +
-        jit_sampling_tag(sampling) + jit_spp_map_tag(spp_map);
+        (spec.bvh ? "// +bvh\n" : "") +
+        jit_sampling_tag(spec.sampling) + jit_spp_map_tag(spec.spp_map);
+}
+
+std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, uint32_t n,
+                                             const JitSpec &spec, std::string &err)
+{
+    JitCompile cc;
+    const std::string scan = jit_module_source(tri, n, spec, cc);
+    const bool legacy = spec.legacy, bvh = spec.bvh;
     const uint64_t h = fnv1a(scan);
     std::lock_guard<std::mutex> lock(g_mu);
     for (auto it = g_cache.begin(); it != g_cache.end(); ++it) {
@@ -1110,11 +1117,8 @@ std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, u
     };
     std::vector<char> code;
     bool from_disk = false;
-    if (jit_cached_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, &from_disk, false, sampling,
-                        spp_map) != 0)
-        return nullptr;
-    const uint64_t key_hash =
-        fnv1a(code_key(scan, jit_options(legacy, legacy_waves, lds_scene, bvh, sampling, spp_map)));
+    if (jit_cached_code(scan, code, err, cc, &from_disk, false) != 0) return nullptr;
+    const uint64_t key_hash = fnv1a(code_key(scan, jit_options(cc)));
     auto k = std::make_shared<JitKernels>();
     k->device = device;
     k->key_hash = key_hash;
@@ -1125,9 +1129,7 @@ std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, u
         k = std::make_shared<JitKernels>();
         k->device = device;
         k->key_hash = key_hash;
-        if (jit_cached_code(scan, code, err, legacy, legacy_waves, lds_scene, bvh, &from_disk, true, sampling,
-                            spp_map) != 0)
-            return nullptr;
+        if (jit_cached_code(scan, code, err, cc, &from_disk, true) != 0) return nullptr;
         why = load(*k, code);
     }
     if (!why.empty()) {
@@ -1168,72 +1170,145 @@ extern "C" int rvcp_internal_jit_scene_in_range(const void *tri_records, uint32_
     return rvcp::jit_scene_in_range(static_cast<const rvcp::TriRecord *>(tri_records), n) ? 1 : 0;
 }
 
-// Self-test hooks for the CPU test suite (not part of rvcp.h): generate and compile the
-// specialised module for n triangle records without a GPU (`legacy`: with the mode-2 kernel).
-// Returns 0 and the code-object size, or -1 with the message in err (err_cap bytes).
-// (with n_spheres sphere records: a mode-2 module with the spheres as literals, as upload
-// builds it for a scene with spheres -- rvcp_internal_jit_compile_check_spheres)
-static int jit_compile_check(const void *tri_records, uint32_t n, int legacy, const void *spheres,
-                             uint32_t n_spheres, size_t *code_bytes, char *err, size_t err_cap)
+// ---- self-test hooks for the CPU test suite (not part of rvcp.h), none needing a GPU ----
+// What they share: a string into the caller's buffer (at most cap bytes with the terminator;
+// returns the full length), ...
+static size_t copy_out(const std::string &s, char *out, size_t cap)
+{
+    if (out && cap) {
+        std::strncpy(out, s.c_str(), cap - 1);
+        out[cap - 1] = '\0';
+    }
+    return s.size();
+}
+
+// ... the spec of a games101 module by its variant flags, ...
+static rvcp::JitSpec hook_spec(int sampling, int spp_map = 0, int bvh = 0)
+{
+    rvcp::JitSpec spec;
+    spec.sampling = sampling;
+    spec.spp_map = spp_map != 0;
+    spec.bvh = bvh != 0;
+    return spec;
+}
+
+// ... the source text the module of n triangle records is cached under in the process (the scan
+// and the spec's tags), ...
+static size_t module_source(const void *tri_records, uint32_t n, const rvcp::JitSpec &spec,
+                            char *out, size_t cap)
+{
+    try {
+        rvcp::JitCompile cc;
+        return copy_out(rvcp::jit_module_source(static_cast<const rvcp::TriRecord *>(tri_records),
+                                                n, spec, cc), out, cap);
+    } catch (...) {
+        return 0;
+    }
+}
+
+// ... the hash of its whole compile input (JitKernels::key_hash, the disk-cache key), ...
+static uint64_t module_key(const void *tri_records, uint32_t n, const rvcp::JitSpec &spec)
+{
+    try {
+        rvcp::JitCompile cc;
+        const std::string src =
+            rvcp::jit_module_source(static_cast<const rvcp::TriRecord *>(tri_records), n, spec, cc);
+        return rvcp::fnv1a(rvcp::code_key(src, rvcp::jit_options(cc)));
+    } catch (...) {
+        return 0;
+    }
+}
+
+// ... and its generation and compilation (no module load): 0 and the code-object size, or -1 with
+// the message in err (err_cap bytes).  With from_disk: through the on-disk cache.
+static int compile_check(const void *tri_records, uint32_t n, const rvcp::JitSpec &spec,
+                         int *from_disk, size_t *code_bytes, char *err, size_t err_cap)
 {
     try {
         std::string e;
         std::vector<char> code;
-        std::string scan = rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n);
-        if (legacy) scan += rvcp::jit_sphere_source(static_cast<const rvcp_sphere_t *>(spheres), n_spheres);
-        const int rc = rvcp::jit_compile_code(scan, code, e, legacy != 0);
-        if (code_bytes) *code_bytes = code.size();
-        if (err && err_cap) {
-            std::strncpy(err, e.c_str(), err_cap - 1);
-            err[err_cap - 1] = '\0';
+        rvcp::JitCompile cc;
+        const std::string src =
+            rvcp::jit_module_source(static_cast<const rvcp::TriRecord *>(tri_records), n, spec, cc);
+        int rc;
+        if (from_disk) {
+            bool disk = false;
+            std::lock_guard<std::mutex> lock(rvcp::g_mu);
+            rc = rvcp::jit_cached_code(src, code, e, cc, &disk, false);
+            *from_disk = disk ? 1 : 0;
+        } else {
+            rc = rvcp::jit_compile_code(src, code, e, cc);
         }
+        if (code_bytes) *code_bytes = code.size();
+        copy_out(e, err, err_cap);
         return rc;
     } catch (...) {
         return -1;
     }
 }
 
+// (`legacy`: with the mode-2 kernel)
 extern "C" int rvcp_internal_jit_compile_check_mode(const void *tri_records, uint32_t n,
                                                      int legacy, size_t *code_bytes, char *err,
                                                      size_t err_cap)
 {
-    return jit_compile_check(tri_records, n, legacy, nullptr, 0, code_bytes, err, err_cap);
+    rvcp::JitSpec spec;
+    spec.legacy = legacy != 0;
+    return compile_check(tri_records, n, spec, nullptr, code_bytes, err, err_cap);
 }
 
+// (a mode-2 module with the n_spheres sphere records as literals, as upload builds it for a scene
+// with spheres)
 extern "C" int rvcp_internal_jit_compile_check_spheres(const void *tri_records, uint32_t n,
                                                         const void *spheres, uint32_t n_spheres,
                                                         size_t *code_bytes, char *err,
                                                         size_t err_cap)
 {
-    return jit_compile_check(tri_records, n, 1, spheres, n_spheres, code_bytes, err, err_cap);
+    rvcp::JitSpec spec;
+    spec.legacy = true;
+    spec.spheres = static_cast<const rvcp_sphere_t *>(spheres);
+    spec.n_spheres = n_spheres;
+    return compile_check(tri_records, n, spec, nullptr, code_bytes, err, err_cap);
 }
 
 extern "C" int rvcp_internal_jit_compile_check(const void *tri_records, uint32_t n,
                                                 size_t *code_bytes, char *err, size_t err_cap)
 {
-    return rvcp_internal_jit_compile_check_mode(tri_records, n, 0, code_bytes, err, err_cap);
+    return compile_check(tri_records, n, rvcp::JitSpec{}, nullptr, code_bytes, err, err_cap);
 }
 
-// The generated scan source for n triangle records (for inspection): writes at most cap bytes
-// including the terminator and returns the full length.
+extern "C" int rvcp_internal_jit_cached_code(const void *tri_records, uint32_t n, int legacy,
+                                             int *from_disk, size_t *code_bytes, char *err,
+                                             size_t err_cap)
+{
+    rvcp::JitSpec spec;
+    spec.legacy = legacy != 0;
+    int disk = 0;
+    const int rc = compile_check(tri_records, n, spec, &disk, code_bytes, err, err_cap);
+    if (from_disk) *from_disk = disk;
+    return rc;
+}
+
+// The generated scan source for n triangle records (for inspection).
 extern "C" size_t rvcp_internal_jit_scan_source_opt(const void *tri_records, uint32_t n,
                                                     int opts, char *out, size_t cap)
 {
     try {
-        const std::string s = rvcp::jit_scan_source(
-            static_cast<const rvcp::TriRecord *>(tri_records), n, (unsigned)opts);
-        if (out && cap) {
-            std::strncpy(out, s.c_str(), cap - 1);
-            out[cap - 1] = '\0';
-        }
-        return s.size();
+        return copy_out(rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n,
+                                              (unsigned)opts), out, cap);
     } catch (...) {
         return 0;
     }
 }
 
-// Self-test hook: the sphere X-macro of a mode-2 module for n sphere records (rvcp_sphere_t);
-// the length without the terminator, written into out when it fits cap bytes.
+extern "C" size_t rvcp_internal_jit_scan_source(const void *tri_records, uint32_t n, char *out,
+                                                size_t cap)
+{
+    return rvcp_internal_jit_scan_source_opt(tri_records, n, 0, out, cap);
+}
+
+// The sphere X-macro of a mode-2 module for n sphere records (rvcp_sphere_t); the length without
+// the terminator, written into out when it fits cap bytes.
 extern "C" size_t rvcp_internal_jit_sphere_source(const void *spheres, uint32_t n, char *out,
                                                    size_t cap)
 {
@@ -1246,125 +1321,47 @@ extern "C" size_t rvcp_internal_jit_sphere_source(const void *spheres, uint32_t 
     }
 }
 
-extern "C" size_t rvcp_internal_jit_scan_source(const void *tri_records, uint32_t n, char *out,
-                                                size_t cap)
-{
-    return rvcp_internal_jit_scan_source_opt(tri_records, n, 0, out, cap);
-}
-
-// Self-test hooks for the bounce sampling (rvcp_set_sampling), none needing a
-// GPU: the source text a games101 module of n triangle records is cached under in the process
-// (the scan plus jit_sampling_tag), ...
+// A games101 module by its bounce sampling (rvcp_set_sampling) ...
 extern "C" size_t rvcp_internal_jit_module_source(const void *tri_records, uint32_t n,
                                                   int sampling, char *out, size_t cap)
 {
-    try {
-        const std::string s =
-            rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n) +
-            rvcp::jit_sampling_tag(sampling);
-        if (out && cap) {
-            std::strncpy(out, s.c_str(), cap - 1);
-            out[cap - 1] = '\0';
-        }
-        return s.size();
-    } catch (...) {
-        return 0;
-    }
+    return module_source(tri_records, n, hook_spec(sampling), out, cap);
 }
 
-// ... the hash of its whole compile input (JitKernels::key_hash, the disk-cache key), ...
 extern "C" uint64_t rvcp_internal_jit_module_key_for(const void *tri_records, uint32_t n,
                                                      int sampling)
 {
-    try {
-        const std::string scan =
-            rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n) +
-            rvcp::jit_sampling_tag(sampling);
-        return rvcp::fnv1a(rvcp::code_key(scan, rvcp::jit_options(false, 0, false, false, sampling)));
-    } catch (...) {
-        return 0;
-    }
+    return module_key(tri_records, n, hook_spec(sampling));
 }
 
-// ... and its compilation (as rvcp_internal_jit_compile_check).
 extern "C" int rvcp_internal_jit_compile_check_sampling(const void *tri_records, uint32_t n,
                                                          int sampling, size_t *code_bytes,
                                                          char *err, size_t err_cap)
 {
-    try {
-        std::string e;
-        std::vector<char> code;
-        const std::string scan =
-            rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n) +
-            rvcp::jit_sampling_tag(sampling);
-        const int rc = rvcp::jit_compile_code(scan, code, e, false, 0, false, false, sampling);
-        if (code_bytes) *code_bytes = code.size();
-        if (err && err_cap) {
-            std::strncpy(err, e.c_str(), err_cap - 1);
-            err[err_cap - 1] = '\0';
-        }
-        return rc;
-    } catch (...) {
-        return -1;
-    }
+    return compile_check(tri_records, n, hook_spec(sampling), nullptr, code_bytes, err, err_cap);
 }
 
-// The same three hooks for a module whose pre-pass family takes a per-pixel sample count
-// (rvcp_render_spp_map_async): `spp_map` != 0 adds jit_spp_map_tag and
-// -DRVCP_SPP_MAP=1.
+// ... and by whether its pre-pass family takes a per-pixel sample count
+// (rvcp_render_spp_map_async), the compilation also with the BVH hybrid's kernels.
 extern "C" size_t rvcp_internal_jit_module_source_map(const void *tri_records, uint32_t n,
                                                       int sampling, int spp_map, char *out,
                                                       size_t cap)
 {
-    try {
-        const std::string s =
-            rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n) +
-            rvcp::jit_sampling_tag(sampling) + rvcp::jit_spp_map_tag(spp_map != 0);
-        if (out && cap) {
-            std::strncpy(out, s.c_str(), cap - 1);
-            out[cap - 1] = '\0';
-        }
-        return s.size();
-    } catch (...) {
-        return 0;
-    }
+    return module_source(tri_records, n, hook_spec(sampling, spp_map), out, cap);
 }
 
 extern "C" uint64_t rvcp_internal_jit_module_key_for_map(const void *tri_records, uint32_t n,
                                                          int sampling, int spp_map)
 {
-    try {
-        const std::string scan =
-            rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n) +
-            rvcp::jit_sampling_tag(sampling) + rvcp::jit_spp_map_tag(spp_map != 0);
-        return rvcp::fnv1a(rvcp::code_key(
-            scan, rvcp::jit_options(false, 0, false, false, sampling, spp_map != 0)));
-    } catch (...) {
-        return 0;
-    }
+    return module_key(tri_records, n, hook_spec(sampling, spp_map));
 }
 
 extern "C" int rvcp_internal_jit_compile_check_map(const void *tri_records, uint32_t n,
                                                     int sampling, int spp_map, int bvh,
                                                     size_t *code_bytes, char *err, size_t err_cap)
 {
-    try {
-        std::string e;
-        std::vector<char> code;
-        const std::string scan =
-            rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n) +
-            rvcp::jit_sampling_tag(sampling) + rvcp::jit_spp_map_tag(spp_map != 0);
-        const int rc = rvcp::jit_compile_code(scan, code, e, false, 0, false, bvh != 0, sampling,
-                                              spp_map != 0);
-        if (code_bytes) *code_bytes = code.size();
-        if (err && err_cap) {
-            std::strncpy(err, e.c_str(), err_cap - 1);
-            err[err_cap - 1] = '\0';
-        }
-        return rc;
-    } catch (...) {
-        return -1;
-    }
+    return compile_check(tri_records, n, hook_spec(sampling, spp_map, bvh), nullptr, code_bytes,
+                         err, err_cap);
 }
 
 // ---- the on-disk code-object cache's C-ABI (rvcp.h) ----
@@ -1388,34 +1385,4 @@ extern "C" int rvcp_code_cache_counts(uint64_t out[3])
     out[1] = rvcp::g_disk_compiles.load();
     out[2] = rvcp::g_disk_rejects.load();
     return 0;
-}
-
-// Self-test hook for the CPU suite (not part of rvcp.h): the specialised module's code object
-// for n triangle records through the on-disk cache, without a GPU (no module load).  Returns 0
-// with *from_disk and *code_bytes, or -1 with the message in err.
-extern "C" int rvcp_internal_jit_cached_code(const void *tri_records, uint32_t n, int legacy,
-                                             int *from_disk, size_t *code_bytes, char *err,
-                                             size_t err_cap)
-{
-    try {
-        std::string e;
-        std::vector<char> code;
-        const std::string scan =
-            rvcp::jit_scan_source(static_cast<const rvcp::TriRecord *>(tri_records), n);
-        bool disk = false;
-        int rc;
-        {
-            std::lock_guard<std::mutex> lock(rvcp::g_mu);
-            rc = rvcp::jit_cached_code(scan, code, e, legacy != 0, 0, false, false, &disk, false);
-        }
-        if (from_disk) *from_disk = disk ? 1 : 0;
-        if (code_bytes) *code_bytes = code.size();
-        if (err && err_cap) {
-            std::strncpy(err, e.c_str(), err_cap - 1);
-            err[err_cap - 1] = '\0';
-        }
-        return rc;
-    } catch (...) {
-        return -1;
-    }
 }

@@ -44,38 +44,50 @@ std::vector<std::string> jit_extra_flags();
 // opts: kScanSkipB | kScanEagerSplit (experiment knobs, jit_scan_opts)
 constexpr unsigned kScanSkipB = 1u, kScanEagerSplit = 2u;
 std::string jit_scan_source(const TriRecord *tri, uint32_t n, unsigned opts = 0);
+// What a module is compiled with besides its scan: the options' variant defines (jit_options)
+// and so, with the scan, the module's compile key.
+struct JitCompile {
+    bool legacy = false;        // also the mode-2 kernel (RVCP_JIT_LEGACY) ...
+    int legacy_waves = 0;       // ... for this many waves per SIMD (0: the compiler's choice)
+    bool lds_scene = false;     // ... which copies the scene into LDS (RVCP_LEGACY_LDS_SCENE)
+    bool bvh = false;           // also the BVH hybrid's kernels (RVCP_JIT_BVH)
+    int sampling = RVCP_SAMPLING_UNIFORM;   // -DRVCP_SAMPLING (none for the default)
+    bool spp_map = false;       // -DRVCP_SPP_MAP=1
+};
 // Compile rvcp_kernels.hip with the given scan for gfx950 (hipRTC); 0 or -1 with err set.
-// `legacy` also builds the mode-2 kernel (RVCP_JIT_LEGACY).
-// `lds_scene`: the mode-2 kernel copies the scene into LDS (RVCP_LEGACY_LDS_SCENE).
 int jit_compile_code(const std::string &scan, std::vector<char> &code, std::string &err,
-                     bool legacy = false, int legacy_waves = 0, bool lds_scene = false,
-                     bool bvh = false, int sampling = RVCP_SAMPLING_UNIFORM, bool spp_map = false);
+                     const JitCompile &cc);
 // jit_compile_code behind the on-disk code-object cache (rvcp_set_code_cache_dir): a verified
 // entry for exactly this compile is read (*from_disk = true), else the module is compiled and
 // stored; force_compile counts the entry rejected and recompiles it (the runtime refused it).
 int jit_cached_code(const std::string &scan, std::vector<char> &code, std::string &err,
-                    bool legacy, int legacy_waves, bool lds_scene, bool bvh, bool *from_disk,
-                    bool force_compile, int sampling = RVCP_SAMPLING_UNIFORM, bool spp_map = false);
-// Compiled + loaded kernels for the scene on `device` (process-wide cache keyed by the scan
-// source and `legacy`); nullptr with err set when hipRTC is unavailable or compilation fails.
-// `sphereless`: the mode-2 kernel is built for 6 waves per SIMD.
-// `lds_fits`: at most 64 spheres and 64 materials (and, as always here, 64 faces): the mode-2
-// kernel reads its hit records, spheres and materials from LDS copies.
-// `bvh`: also the BVH hybrid's kernels (RVCP_JIT_BVH; tri / n are then the prefix faces).
-// `spheres` (legacy modules): the scene's sphere records, written into the module as literals
-// (jit_sphere_source) -- the module is then valid for these spheres only, like its scan.
-// `sampling` (RVCP_SAMPLING_*): the bounce the module's games101 kernels are compiled with
-// (-DRVCP_SAMPLING); part of the module's source tag and of its compile key.
-// `spp_map`: the module's pre-pass family takes a per-pixel sample count (-DRVCP_SPP_MAP=1,
-// rvcp_spec_primary_kernel and rvcp_spec_bvh_primary_kernel then have one more
-// parameter, the map); part of the source tag and of the compile key likewise.
+                    const JitCompile &cc, bool *from_disk, bool force_compile);
+// Which module a scene gets.
+struct JitSpec {
+    bool legacy = false;        // the module also holds the mode-2 kernel
+    // (legacy) no spheres: the mode-2 kernel is built for 6 waves per SIMD
+    bool sphereless = false;
+    // (legacy) at most 64 spheres and 64 materials (and, as always here, 64 faces): the mode-2
+    // kernel reads its hit records, spheres and materials from LDS copies
+    bool lds_fits = false;
+    bool bvh = false;           // also the BVH hybrid's kernels; tri / n are then the prefix faces
+    // the bounce the module's games101 kernels are compiled with (RVCP_SAMPLING_*, DESIGN.md
+    // §4.17); part of the module's source tag and of its compile key
+    int sampling = RVCP_SAMPLING_UNIFORM;
+    // the module's pre-pass family takes a per-pixel sample count (DESIGN.md §4.18:
+    // rvcp_spec_primary_kernel and rvcp_spec_bvh_primary_kernel then have one more parameter, the
+    // map); part of the source tag and of the compile key likewise
+    bool spp_map = false;
+    // (legacy) the scene's sphere records, written into the module as literals
+    // (jit_sphere_source) -- the module is then valid for these spheres only, like its scan
+    const rvcp_sphere_t *spheres = nullptr;
+    uint32_t n_spheres = 0, n_materials = 64;
+};
+// Compiled + loaded kernels for the scene on `device` (process-wide cache keyed by the module's
+// source text: the scan and the spec's tags); nullptr with err set when hipRTC is unavailable or
+// compilation fails.
 std::shared_ptr<JitKernels> jit_path_kernels(int device, const TriRecord *tri, uint32_t n,
-                                             std::string &err, bool legacy = false,
-                                             bool sphereless = false, bool lds_fits = false,
-                                             bool bvh = false, const rvcp_sphere_t *spheres = nullptr,
-                                             uint32_t n_spheres = 0, uint32_t n_materials = 64,
-                                             int sampling = RVCP_SAMPLING_UNIFORM,
-                                             bool spp_map = false);
+                                             const JitSpec &spec, std::string &err);
 // The sphere X-macro of a mode-2 module ("" for none or more than kJitMaxSpheres).
 constexpr uint32_t kJitMaxSpheres = 64;
 std::string jit_sphere_source(const rvcp_sphere_t *sph, uint32_t n);

@@ -32,25 +32,12 @@
 // draws, chosen when this file is compiled -- 0, the default: the shader's
 // uniform hemisphere; 1: the cosine-weighted bounce (brdf_continue, brdf_finish).  The cosine
 // build is a translation unit of its own (rvcp_kernels_cosine.hip: this file with
-// RVCP_SAMPLING = 1) holding only the games101 kernels and their launchers under the names
-// below, so the default object is compiled from the text it always was; the scene-specialised
-// modules get the define from rvcp_jit.cpp.
+// RVCP_SAMPLING = 1) holding only the games101 kernels and their launchers under names of its
+// own (RVCP_BUILD_TAG below), so the default object is compiled from the text it always was; the
+// scene-specialised modules get the define from rvcp_jit.cpp.
 #ifndef RVCP_SAMPLING
 #define RVCP_SAMPLING 0
 #endif
-#if RVCP_SAMPLING && !defined(RVCP_JIT)
-#define games101_kernel games101_cosine_kernel
-#define games101_dual_kernel games101_cosine_dual_kernel
-#define games101_path_kernel games101_cosine_path_kernel
-#define games101_bvh_path_kernel games101_cosine_bvh_path_kernel
-#define games101_tiled_kernel games101_cosine_tiled_kernel
-#define games101_tiled_pool_kernel games101_cosine_tiled_pool_kernel
-#define games101_tiled_single_kernel games101_cosine_tiled_single_kernel
-#define rvcp_launch_games101 rvcp_launch_games101_cosine
-#define rvcp_launch_games101_v3 rvcp_launch_games101_v3_cosine
-#define rvcp_games101_occupancy rvcp_games101_occupancy_cosine
-#endif
-
 // RVCP_SPP_MAP: 1 = the pre-pass family takes a per-pixel sample count (DESIGN.md §4.18,
 // rvcp_render_spp_map_async) -- the pre-pass reads pixel p's count from an extra argument
 // `spp_map`, clamps it to 1..RVCP_SPP_MAP_MAX, closes miss / light pixels with it and hands it to
@@ -58,7 +45,7 @@
 // when this file is compiled, by §4.17's mechanism: one translation unit per bounce sampling
 // (rvcp_kernels_map.hip, rvcp_kernels_cosine_map.hip) holding only the pre-pass family -- the
 // primary kernels, the path kernels of schedules 3, 4, 5, 6 and 10, the BVH path kernel -- under
-// names of their own (behind the headers below), and -DRVCP_SPP_MAP=1 for the scene-specialised
+// names of their own (RVCP_BUILD_TAG below), and -DRVCP_SPP_MAP=1 for the scene-specialised
 // modules (rvcp_jit.cpp).  Read in primary_body and path_body only; the default text does not
 // mention a map.
 #ifndef RVCP_SPP_MAP
@@ -80,34 +67,28 @@
 #include "rvcp_sqrt.h"
 #include "rvcp_tonemap.h"
 
-// a map build's names (after the headers: rvcp_internal.h declares every launcher by its own)
-#if RVCP_SPP_MAP && !defined(RVCP_JIT)
-#undef games101_path_kernel
-#undef games101_bvh_path_kernel
-#undef games101_tiled_kernel
-#undef games101_tiled_pool_kernel
-#undef games101_tiled_single_kernel
-#undef rvcp_launch_games101_v3
-#undef rvcp_games101_occupancy
-#if RVCP_SAMPLING
-#define games101_primary_kernel games101_cosine_map_primary_kernel
-#define games101_path_kernel games101_cosine_map_path_kernel
-#define games101_bvh_path_kernel games101_cosine_map_bvh_path_kernel
-#define games101_tiled_kernel games101_cosine_map_tiled_kernel
-#define games101_tiled_pool_kernel games101_cosine_map_tiled_pool_kernel
-#define games101_tiled_single_kernel games101_cosine_map_tiled_single_kernel
-#define rvcp_launch_games101_v3 rvcp_launch_games101_v3_cosine_map
-#define rvcp_games101_occupancy rvcp_games101_occupancy_cosine_map
+// The build tag: a build other than the default one names its games101 kernels (the pre-pass too
+// in a map build) and its KernelBuild object (rvcp_internal.h) after its macros, so that the four
+// translation units link into one library: games101_cosine_path_kernel,
+// games101_map_primary_kernel<..>, rvcp_games101_cosine_map_build, ...  A scene-specialised module
+// (RVCP_JIT) is alone in its code object and keeps the plain names.
+#if defined(RVCP_JIT) || !RVCP_GAMES101_ONLY
+#define RVCP_BUILD_TAG
+#elif RVCP_SAMPLING && RVCP_SPP_MAP
+#define RVCP_BUILD_TAG cosine_map_
+#elif RVCP_SPP_MAP
+#define RVCP_BUILD_TAG map_
 #else
-#define games101_primary_kernel games101_map_primary_kernel
-#define games101_path_kernel games101_map_path_kernel
-#define games101_bvh_path_kernel games101_map_bvh_path_kernel
-#define games101_tiled_kernel games101_map_tiled_kernel
-#define games101_tiled_pool_kernel games101_map_tiled_pool_kernel
-#define games101_tiled_single_kernel games101_map_tiled_single_kernel
-#define rvcp_launch_games101_v3 rvcp_launch_games101_v3_map
-#define rvcp_games101_occupancy rvcp_games101_occupancy_map
+#define RVCP_BUILD_TAG cosine_
 #endif
+#define RVCP_PASTE3_(a, b, c) a##b##c
+#define RVCP_PASTE3(a, b, c) RVCP_PASTE3_(a, b, c)
+#define RVCP_G101(name) RVCP_PASTE3(games101_, RVCP_BUILD_TAG, name)
+#define RVCP_KERNEL_BUILD RVCP_PASTE3(rvcp_games101_, RVCP_BUILD_TAG, build)
+#if RVCP_SPP_MAP
+#define RVCP_G101_PRIMARY RVCP_G101(primary_kernel)
+#else
+#define RVCP_G101_PRIMARY games101_primary_kernel     // (the bounce does not reach the pre-pass)
 #endif
 
 namespace rvcp {
@@ -1395,7 +1376,7 @@ enum : int { K_NONE = -1, K_PRIMARY = 0, K_PATH = 1, K_SHADOW = 2 };
 // ======================================================================================
 // Variant 1: one ray per lane per iteration
 // ======================================================================================
-__global__ __launch_bounds__(kBlock) void games101_kernel(
+__global__ __launch_bounds__(kBlock) void RVCP_G101(kernel)(
     FrameArgs A, const TriRecord *__restrict__ tri, const rvcp_face_t *__restrict__ faces,
     const rvcp_vertex_t *__restrict__ verts, const MatRecord *__restrict__ mats,
     const LightRecord *__restrict__ lights, const float *__restrict__ gamma_t,
@@ -1552,7 +1533,7 @@ __global__ __launch_bounds__(kBlock) void games101_kernel(
 // the NEE term of bounce d is added before the miss/emission term of bounce d+1, as in the
 // shader.
 // ======================================================================================
-__global__ __launch_bounds__(kBlock) void games101_dual_kernel(
+__global__ __launch_bounds__(kBlock) void RVCP_G101(dual_kernel)(
     FrameArgs A, const TriRecord *__restrict__ tri, const rvcp_face_t *__restrict__ faces,
     const rvcp_vertex_t *__restrict__ verts, const MatRecord *__restrict__ mats,
     const LightRecord *__restrict__ lights, const float *__restrict__ gamma_t,
@@ -1850,7 +1831,7 @@ __device__ __forceinline__ void primary_body(
 
 #ifndef RVCP_JIT
 template <bool BVH>
-__global__ __launch_bounds__(kPrimaryBlock) void games101_primary_kernel(
+__global__ __launch_bounds__(kPrimaryBlock) void RVCP_G101_PRIMARY(
     FrameArgs A, const TriRecord *__restrict__ tri, const rvcp_face_t *__restrict__ faces,
     const rvcp_vertex_t *__restrict__ verts, const MatRecord *__restrict__ mats,
     const float *__restrict__ gamma_t, uint32_t *__restrict__ out_rgba,
@@ -2771,7 +2752,7 @@ __device__ __forceinline__ void path_body(
 
 #ifndef RVCP_JIT
 template <int MIN_WAVES>
-__global__ __launch_bounds__(kBlock, MIN_WAVES) void games101_path_kernel(
+__global__ __launch_bounds__(kBlock, MIN_WAVES) void RVCP_G101(path_kernel)(
     FrameArgs A, const TriRecord *__restrict__ tri, const MatRecord *__restrict__ mats,
     const LightRecord *__restrict__ lights, const float *__restrict__ gamma_t,
     uint32_t *__restrict__ out_rgba, float *__restrict__ out_lin,
@@ -2790,7 +2771,7 @@ __global__ __launch_bounds__(kBlock, MIN_WAVES) void games101_path_kernel(
 // the brute-force scan.
 // (Measured and not kept: private scratch stacks, the path state in LDS columns, 5 waves per SIMD
 // (96 VGPRs with two-triangle leaf chunks): all slower)
-__global__ __launch_bounds__(kBlock, 4) void games101_bvh_path_kernel(
+__global__ __launch_bounds__(kBlock, 4) void RVCP_G101(bvh_path_kernel)(
     FrameArgs A, const TriRecord *__restrict__ tri, const MatRecord *__restrict__ mats,
     const LightRecord *__restrict__ lights, const float *__restrict__ gamma_t,
     uint32_t *__restrict__ out_rgba, float *__restrict__ out_lin,
@@ -2806,7 +2787,7 @@ __global__ __launch_bounds__(kBlock, 4) void games101_bvh_path_kernel(
                            bvh_stack + threadIdx.x, nullptr, nullptr, bvh_pool_lds);
 }
 
-__global__ __launch_bounds__(kBlock, kTiledMinWaves) void games101_tiled_kernel(
+__global__ __launch_bounds__(kBlock, kTiledMinWaves) void RVCP_G101(tiled_kernel)(
     FrameArgs A, const TriRecord *__restrict__ tri, const MatRecord *__restrict__ mats,
     const LightRecord *__restrict__ lights, const float *__restrict__ gamma_t,
     uint32_t *__restrict__ out_rgba, float *__restrict__ out_lin,
@@ -2821,7 +2802,7 @@ __global__ __launch_bounds__(kBlock, kTiledMinWaves) void games101_tiled_kernel(
 
 // Schedule 10: schedule 4 with the workgroup ray pool (path_body POOL_W): the workgroup's rays
 // are scanned against each LDS tile in full 64-ray passes shared out over its 4 waves.
-__global__ __launch_bounds__(kTiledPoolWaves * kWave, kTiledMinWaves) void games101_tiled_pool_kernel(
+__global__ __launch_bounds__(kTiledPoolWaves * kWave, kTiledMinWaves) void RVCP_G101(tiled_pool_kernel)(
     FrameArgs A, const TriRecord *__restrict__ tri, const MatRecord *__restrict__ mats,
     const LightRecord *__restrict__ lights, const float *__restrict__ gamma_t,
     uint32_t *__restrict__ out_rgba, float *__restrict__ out_lin,
@@ -2838,7 +2819,7 @@ __global__ __launch_bounds__(kTiledPoolWaves * kWave, kTiledMinWaves) void games
 }
 
 // Variant 5: the LDS-tiled scan with one ray per lane per iteration (no empty ray slots).
-__global__ __launch_bounds__(kBlock, kTiledMinWaves) void games101_tiled_single_kernel(
+__global__ __launch_bounds__(kBlock, kTiledMinWaves) void RVCP_G101(tiled_single_kernel)(
     FrameArgs A, const TriRecord *__restrict__ tri, const MatRecord *__restrict__ mats,
     const LightRecord *__restrict__ lights, const float *__restrict__ gamma_t,
     uint32_t *__restrict__ out_rgba, float *__restrict__ out_lin,
@@ -3490,7 +3471,7 @@ extern "C" __global__ __launch_bounds__(kPrimaryBlock) void rvcp_spec_bvh_primar
                              surf, shade, bvh_nodes, bvh_tris, cams, frame_stride RVCP_SPP_MAP_ARG);
 }
 #endif
-// the pre-pass with the specialised scan (rvcp_launch_games101_v3's spec_pre_fn)
+// the pre-pass with the specialised scan (PathLaunch::spec_pre_fn)
 extern "C" __global__ __launch_bounds__(kPrimaryBlock) void rvcp_spec_primary_kernel(
     FrameArgs A, const TriRecord *__restrict__ tri, const rvcp_face_t *__restrict__ faces,
     const rvcp_vertex_t *__restrict__ verts, const MatRecord *__restrict__ mats,
@@ -3562,131 +3543,99 @@ extern "C" __global__ __launch_bounds__(kBlock, 6) void rvcp_spec_path_kernel6(
 
 #ifndef RVCP_JIT
 
+// This build's launchers and occupancy query, reached through its KernelBuild (below).
 #if !RVCP_SPP_MAP   // (schedules 1 and 2 have no map build)
-extern "C" int rvcp_launch_games101(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
-                                    const void *faces, const void *verts,
-                                    const rvcp::MatRecord *mats, const rvcp::LightRecord *lights,
-                                    const float *gamma_t, uint32_t *out_rgba, float *out_lin,
-                                    unsigned long long *counters, uint32_t grid_blocks,
-                                    void *stream)
+static int launch_games101(const rvcp::PathLaunch &L)
 {
-    auto kern = args->variant == 2 ? rvcp::games101_dual_kernel : rvcp::games101_kernel;
-    hipLaunchKernelGGL(kern, dim3(grid_blocks), dim3(rvcp::kBlock), 0, (hipStream_t)stream,
-                       *args, tri, (const rvcp_face_t *)faces, (const rvcp_vertex_t *)verts, mats,
-                       lights, gamma_t, out_rgba, out_lin, counters);
+    auto kern = L.args->variant == 2 ? rvcp::RVCP_G101(dual_kernel) : rvcp::RVCP_G101(kernel);
+    hipLaunchKernelGGL(kern, dim3(L.grid_blocks), dim3(rvcp::kBlock), 0, (hipStream_t)L.stream,
+                       *L.args, L.tri, (const rvcp_face_t *)L.faces, (const rvcp_vertex_t *)L.verts,
+                       L.mats, L.lights, L.gamma_t, L.out_rgba, L.out_lin, L.counters);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
+#else
+static constexpr int (*launch_games101)(const rvcp::PathLaunch &) = nullptr;
 #endif
 
-extern "C" int rvcp_launch_games101_v3(const rvcp::FrameArgs *args, uint32_t n_frames,
-                                       uint32_t frame_stride, const rvcp::TriRecord *tri,
-                                       const void *faces, const void *verts,
-                                       const rvcp::MatRecord *mats,
-                                       const rvcp::LightRecord *lights, const float *gamma_t,
-                                       uint32_t *out_rgba, float *out_lin,
-                                       unsigned long long *counters, rvcp::SurfRecord *surf,
-                                       const rvcp::FaceShade *shade,
-                                       const rvcp::Bvh4Node *bvh_nodes,
-                                       const rvcp::TriRecord *bvh_tris,
-                                       uint32_t grid_blocks, void *stream, void *main_event,
-                                       void *spec_path_fn, const float *cams, void *spec_pre_fn
-                                       RVCP_SPP_MAP_PARAM)
+static int launch_games101_prepass(const rvcp::PathLaunch &launch)
 {
-    const uint32_t pre_blocks = (args->n_pixels + rvcp::kPrimaryBlock - 1) / rvcp::kPrimaryBlock;
-    auto pre = args->accel ? rvcp::games101_primary_kernel<true> : rvcp::games101_primary_kernel<false>;
+    rvcp::PathLaunch L = launch;    // (hipModuleLaunchKernel takes its arguments' addresses)
+    const hipStream_t stream = (hipStream_t)L.stream;
+#if RVCP_SPP_MAP
+    const uint32_t *const spp_map = L.spp_map;      // (RVCP_SPP_MAP_ARG)
+#endif
+    const uint32_t pre_blocks = (L.args->n_pixels + rvcp::kPrimaryBlock - 1) / rvcp::kPrimaryBlock;
+    auto pre = L.args->accel ? rvcp::RVCP_G101_PRIMARY<true> : rvcp::RVCP_G101_PRIMARY<false>;
     // the frames' pre-passes append to one surface list (the path kernel reads each record's
     // pixel and seed, so the list's order is free): a batch with its cameras in device memory
     // in one launch, one frame per grid row, else one launch per frame
-    if (spec_pre_fn) {
+    const bool batch = L.cams && L.n_frames > 1;
+    if (L.spec_pre_fn) {
         // the specialised pre-pass (same parameters as games101_primary_kernel; with the BVH:
-        // the hybrid's, rvcp_spec_bvh_primary_kernel)
-        const bool batch = cams && n_frames > 1;
-        for (uint32_t k = 0; k < (batch ? 1u : n_frames); ++k) {
-            rvcp::FrameArgs a = args[k];
-            const void *p_faces = faces, *p_verts = verts;
-            const rvcp::Bvh4Node *p_nodes = bvh_nodes;
-            const rvcp::TriRecord *p_btris = bvh_tris;
-            const float *p_cams = batch ? cams : nullptr;
-            uint32_t p_stride = batch ? frame_stride : 0u;
-#if RVCP_SPP_MAP
-            void *params[] = {&a, &tri, &p_faces, &p_verts, &mats, &gamma_t, &out_rgba, &out_lin,
-                              &counters, &surf, &shade, &p_nodes, &p_btris, &p_cams, &p_stride,
-                              (void *)&spp_map};
-#else
-            void *params[] = {&a, &tri, &p_faces, &p_verts, &mats, &gamma_t, &out_rgba, &out_lin,
-                              &counters, &surf, &shade, &p_nodes, &p_btris, &p_cams, &p_stride};
-#endif
-            if (hipModuleLaunchKernel((hipFunction_t)spec_pre_fn, pre_blocks, batch ? n_frames : 1u,
-                                      1, rvcp::kPrimaryBlock, 1, 1, 0, (hipStream_t)stream, params,
-                                      nullptr) != hipSuccess)
+        // the hybrid's, rvcp_spec_bvh_primary_kernel); only a map build's reads the last one
+        for (uint32_t k = 0; k < (batch ? 1u : L.n_frames); ++k) {
+            rvcp::FrameArgs a = L.args[k];
+            const float *p_cams = batch ? L.cams : nullptr;
+            uint32_t p_stride = batch ? L.frame_stride : 0u;
+            void *params[] = {&a, &L.tri, &L.faces, &L.verts, &L.mats, &L.gamma_t, &L.out_rgba,
+                              &L.out_lin, &L.counters, &L.surf, &L.shade, &L.bvh_nodes, &L.bvh_tris,
+                              &p_cams, &p_stride, &L.spp_map};
+            if (hipModuleLaunchKernel((hipFunction_t)L.spec_pre_fn, pre_blocks,
+                                      batch ? L.n_frames : 1u, 1, rvcp::kPrimaryBlock, 1, 1, 0,
+                                      stream, params, nullptr) != hipSuccess)
                 return -2;
         }
-    } else if (cams && n_frames > 1)
-        hipLaunchKernelGGL(pre, dim3(pre_blocks, n_frames), dim3(rvcp::kPrimaryBlock), 0,
-                           (hipStream_t)stream, args[0], tri, (const rvcp_face_t *)faces,
-                           (const rvcp_vertex_t *)verts, mats, gamma_t, out_rgba, out_lin, counters,
-                           surf, shade, bvh_nodes, bvh_tris, cams, frame_stride RVCP_SPP_MAP_ARG);
+    } else if (batch)
+        hipLaunchKernelGGL(pre, dim3(pre_blocks, L.n_frames), dim3(rvcp::kPrimaryBlock), 0, stream,
+                           L.args[0], L.tri, (const rvcp_face_t *)L.faces,
+                           (const rvcp_vertex_t *)L.verts, L.mats, L.gamma_t, L.out_rgba, L.out_lin,
+                           L.counters, L.surf, L.shade, L.bvh_nodes, L.bvh_tris, L.cams,
+                           L.frame_stride RVCP_SPP_MAP_ARG);
     else
-        for (uint32_t k = 0; k < n_frames; ++k)
-            hipLaunchKernelGGL(pre, dim3(pre_blocks), dim3(rvcp::kPrimaryBlock), 0,
-                               (hipStream_t)stream, args[k], tri, (const rvcp_face_t *)faces,
-                               (const rvcp_vertex_t *)verts, mats, gamma_t, out_rgba, out_lin,
-                               counters, surf, shade, bvh_nodes, bvh_tris, (const float *)nullptr,
-                               0u RVCP_SPP_MAP_ARG);
-    if (main_event && hipEventRecord((hipEvent_t)main_event, (hipStream_t)stream) != hipSuccess)
-        return -2;
-    if (spec_path_fn && args->accel) {
-        // the BVH hybrid's path kernel (rvcp_spec_bvh_path_kernel, games101_bvh_path_kernel's
-        // signature)
-        rvcp::FrameArgs a = *args;
-        void *params[] = {&a, &tri, &mats, &lights, &gamma_t, &out_rgba, &out_lin, &counters,
-                          &surf, &shade, &bvh_nodes, &bvh_tris};
-        if (hipModuleLaunchKernel((hipFunction_t)spec_path_fn, grid_blocks, 1, 1, rvcp::kBlock,
-                                  1, 1, 0, (hipStream_t)stream, params, nullptr) != hipSuccess)
+        for (uint32_t k = 0; k < L.n_frames; ++k)
+            hipLaunchKernelGGL(pre, dim3(pre_blocks), dim3(rvcp::kPrimaryBlock), 0, stream,
+                               L.args[k], L.tri, (const rvcp_face_t *)L.faces,
+                               (const rvcp_vertex_t *)L.verts, L.mats, L.gamma_t, L.out_rgba,
+                               L.out_lin, L.counters, L.surf, L.shade, L.bvh_nodes, L.bvh_tris,
+                               (const float *)nullptr, 0u RVCP_SPP_MAP_ARG);
+    if (L.main_event && hipEventRecord((hipEvent_t)L.main_event, stream) != hipSuccess) return -2;
+    const rvcp::FrameArgs &A = *L.args;
+    if (L.spec_path_fn) {
+        // the scene-specialised schedule 3 / 6 kernel of rvcp_jit.cpp (games101_path_kernel's
+        // signature) or, with the BVH, the hybrid's path kernel (rvcp_spec_bvh_path_kernel,
+        // games101_bvh_path_kernel's signature: the same and the last two)
+        rvcp::FrameArgs a = A;
+        void *params[] = {&a, &L.tri, &L.mats, &L.lights, &L.gamma_t, &L.out_rgba, &L.out_lin,
+                          &L.counters, &L.surf, &L.shade, &L.bvh_nodes, &L.bvh_tris};
+        if (hipModuleLaunchKernel((hipFunction_t)L.spec_path_fn, L.grid_blocks, 1, 1, rvcp::kBlock,
+                                  1, 1, 0, stream, params, nullptr) != hipSuccess)
             return -2;
-    } else if (spec_path_fn) {
-        // the scene-specialised schedule 3 / 6 kernel of rvcp_jit.cpp (same signature)
-        rvcp::FrameArgs a = *args;
-        void *params[] = {&a, &tri, &mats, &lights, &gamma_t, &out_rgba, &out_lin, &counters,
-                          &surf, &shade};
-        if (hipModuleLaunchKernel((hipFunction_t)spec_path_fn, grid_blocks, 1, 1, rvcp::kBlock,
-                                  1, 1, 0, (hipStream_t)stream, params, nullptr) != hipSuccess)
-            return -2;
-    } else if (args->accel)
-        hipLaunchKernelGGL(rvcp::games101_bvh_path_kernel, dim3(grid_blocks), dim3(rvcp::kBlock), 0,
-                           (hipStream_t)stream, *args, tri, mats, lights, gamma_t, out_rgba,
-                           out_lin, counters, surf, shade, bvh_nodes, bvh_tris);
-    else if (args->variant == 10)
-        hipLaunchKernelGGL(rvcp::games101_tiled_pool_kernel, dim3(grid_blocks), dim3(rvcp::kTiledPoolWaves * rvcp::kWave), 0,
-                           (hipStream_t)stream, *args, tri, mats, lights, gamma_t, out_rgba,
-                           out_lin, counters, surf, shade);
-    else if (args->variant == 5)
-        hipLaunchKernelGGL(rvcp::games101_tiled_single_kernel, dim3(grid_blocks), dim3(rvcp::kBlock), 0,
-                           (hipStream_t)stream, *args, tri, mats, lights, gamma_t, out_rgba,
-                           out_lin, counters, surf, shade);
-    else if (args->variant == 4)
-        hipLaunchKernelGGL(rvcp::games101_tiled_kernel, dim3(grid_blocks), dim3(rvcp::kBlock), 0,
-                           (hipStream_t)stream, *args, tri, mats, lights, gamma_t, out_rgba,
-                           out_lin, counters, surf, shade);
+    } else if (A.accel)
+        hipLaunchKernelGGL(rvcp::RVCP_G101(bvh_path_kernel), dim3(L.grid_blocks), dim3(rvcp::kBlock),
+                           0, stream, A, L.tri, L.mats, L.lights, L.gamma_t, L.out_rgba, L.out_lin,
+                           L.counters, L.surf, L.shade, L.bvh_nodes, L.bvh_tris);
+    else if (A.variant == 10)
+        hipLaunchKernelGGL(rvcp::RVCP_G101(tiled_pool_kernel), dim3(L.grid_blocks),
+                           dim3(rvcp::kTiledPoolWaves * rvcp::kWave), 0, stream, A, L.tri, L.mats,
+                           L.lights, L.gamma_t, L.out_rgba, L.out_lin, L.counters, L.surf, L.shade);
+    else if (A.variant == 5)
+        hipLaunchKernelGGL(rvcp::RVCP_G101(tiled_single_kernel), dim3(L.grid_blocks),
+                           dim3(rvcp::kBlock), 0, stream, A, L.tri, L.mats, L.lights, L.gamma_t,
+                           L.out_rgba, L.out_lin, L.counters, L.surf, L.shade);
+    else if (A.variant == 4)
+        hipLaunchKernelGGL(rvcp::RVCP_G101(tiled_kernel), dim3(L.grid_blocks), dim3(rvcp::kBlock), 0,
+                           stream, A, L.tri, L.mats, L.lights, L.gamma_t, L.out_rgba, L.out_lin,
+                           L.counters, L.surf, L.shade);
     else
-        hipLaunchKernelGGL(args->variant == 6 ? rvcp::games101_path_kernel<6>
-                                              : rvcp::games101_path_kernel<rvcp::kPathMinWaves>,
-                           dim3(grid_blocks), dim3(rvcp::kBlock), 0,
-                           (hipStream_t)stream, *args, tri, mats, lights, gamma_t, out_rgba,
-                           out_lin, counters, surf, shade);
+        hipLaunchKernelGGL(A.variant == 6 ? rvcp::RVCP_G101(path_kernel)<6>
+                                          : rvcp::RVCP_G101(path_kernel)<rvcp::kPathMinWaves>,
+                           dim3(L.grid_blocks), dim3(rvcp::kBlock), 0, stream, A, L.tri, L.mats,
+                           L.lights, L.gamma_t, L.out_rgba, L.out_lin, L.counters, L.surf, L.shade);
     if (hipGetLastError() != hipSuccess) return -2;
     // the frame's UNORM8 store from the linear colours (out_lin is never null here); a batch's
     // frames lie frame_stride pixels apart (the rows of a smaller shard's slot are padding)
-    const uint32_t n_tone = n_frames > 1 ? n_frames * frame_stride : args->n_pixels;
-#if RVCP_GAMES101_ONLY
-    return rvcp_launch_tonemap(out_lin, n_tone, gamma_t, out_rgba, stream);   // the default object's
-#else
-    uint32_t tb = (n_tone + rvcp::kToneBlock - 1) / rvcp::kToneBlock;
-    if (tb > 8192u) tb = 8192u;
-    hipLaunchKernelGGL(rvcp::tonemap_kernel, dim3(tb), dim3(rvcp::kToneBlock), 0, (hipStream_t)stream,
-                       out_lin, n_tone, gamma_t, out_rgba);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-#endif
+    const uint32_t n_tone = L.n_frames > 1 ? L.n_frames * L.frame_stride : A.n_pixels;
+    return rvcp_launch_tonemap(L.out_lin, n_tone, L.gamma_t, L.out_rgba, L.stream);
 }
 
 #if !RVCP_GAMES101_ONLY
@@ -3733,32 +3682,39 @@ extern "C" int rvcp_launch_fill(uint32_t *out_rgba, float *out_lin, uint32_t n, 
 }
 #endif  // !RVCP_GAMES101_ONLY
 
-extern "C" int rvcp_games101_occupancy(int variant, int *blocks_per_cu)
+static int games101_occupancy(int variant, int *blocks_per_cu)
 {
     int b = 0;
     const hipError_t e = variant == rvcp::kOccupancyBvh
-        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::games101_bvh_path_kernel, rvcp::kBlock, 0)
+        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::RVCP_G101(bvh_path_kernel), rvcp::kBlock, 0)
         : variant == 5
-        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::games101_tiled_single_kernel, rvcp::kBlock, 0)
+        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::RVCP_G101(tiled_single_kernel), rvcp::kBlock, 0)
         : variant == 4
-        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::games101_tiled_kernel, rvcp::kBlock, 0)
+        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::RVCP_G101(tiled_kernel), rvcp::kBlock, 0)
         : variant == 10
-        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::games101_tiled_pool_kernel, rvcp::kTiledPoolWaves * rvcp::kWave, 0)
+        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::RVCP_G101(tiled_pool_kernel), rvcp::kTiledPoolWaves * rvcp::kWave, 0)
         : variant == 6
-        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::games101_path_kernel<6>, rvcp::kBlock, 0)
+        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::RVCP_G101(path_kernel)<6>, rvcp::kBlock, 0)
         : variant == 3
-        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::games101_path_kernel<rvcp::kPathMinWaves>, rvcp::kBlock, 0)
+        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::RVCP_G101(path_kernel)<rvcp::kPathMinWaves>, rvcp::kBlock, 0)
 #if RVCP_SPP_MAP
         : hipErrorInvalidValue;             // schedules 1 and 2 have no map build
 #else
         : variant == 2
-        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::games101_dual_kernel, rvcp::kBlock, 0)
-        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::games101_kernel, rvcp::kBlock, 0);
+        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::RVCP_G101(dual_kernel), rvcp::kBlock, 0)
+        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, rvcp::RVCP_G101(kernel), rvcp::kBlock, 0);
 #endif
     if (e != hipSuccess) return -2;
     *blocks_per_cu = b;
     return 0;
 }
+
+// this translation unit's entry of the host's [sampling][map] table (rvcp_internal.h); host
+// data, which the device pass would otherwise emit for its external linkage
+#if !defined(__HIP_DEVICE_COMPILE__)
+extern "C" const rvcp::KernelBuild RVCP_KERNEL_BUILD = {launch_games101, launch_games101_prepass,
+                                                        games101_occupancy};
+#endif
 
 #if !RVCP_GAMES101_ONLY
 extern "C" int rvcp_launch_legacy(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,

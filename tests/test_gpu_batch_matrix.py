@@ -40,8 +40,8 @@ mutation misreads a camera or misplaces a pixel inside the caller's buffers; 76 
  4. start_batch_pixel passes `pix`, not `pix - f * A.frame_pixels`, to pixel_uv: the 11
     mode-2 cases fail (A, B, C, E, and the batches that follow the refused and the empty
     one), every games101 case passes.
- 5. rvcp_launch_games101_v3 passes 0 for frame_stride to the batched specialised pre-pass
-    (all frames land in slot 0): 27 fail -- r3s, r6s, hybrid and auto in A (sky-only batches
+ 5. the pre-pass launcher (KernelBuild::launch_prepass) passes 0 for frame_stride to the batched
+    specialised pre-pass (all frames land in slot 0): 27 fail -- r3s, r6s, hybrid and auto in A (sky-only batches
     included), B, C, E, F, G, H and the one-launch half of D; the generic routes, mode 2 and
     the per-frame half of D pass.
  6. (added, since the sky-only batches of the generic routes r3g, r10 and bvh fail under none

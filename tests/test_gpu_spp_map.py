@@ -350,3 +350,49 @@ def test_default_render_after_a_map_render_is_the_oracles(cornell, cornell_array
             assert np.array_equal(rgba, o_rgba)
             assert int(rt.last_stats["traversals"]) == o_trav
             assert int(rt.last_stats["samples"]) == 3 * W * H
+
+
+@pytest.mark.parametrize("name,ckw", [("cornell", dict()), ("specks-2", dict(accel=abi.ACCEL_BVH))],
+                         ids=["specialised", "hybrid"])
+def test_sampling_switches_between_default_and_map_renders(name, ckw):
+    """One context keeps a module per render kind (default, map), each compiled for one bounce
+    sampling: switching the sampling between renders of both kinds must hand every frame the module
+    of its kind and mode.  Each frame of the sequence equals, in linear bits, RGBA8 bytes, traversal
+    count and the kernel that ran, the same call on a fresh context in that mode -- which for the
+    uniform bounce is the oracle's frame (of cfg.spp for a default render, of each pixel's level for
+    a map render)."""
+    W, H, SPP = 48, 40, 3
+    sc, kw, t, _ = _scene(name)
+    push, m = sc.push_constant(t), random_map(W, H)
+
+    def frame(rt, is_map):
+        if is_map:
+            rgba, lin, st = map_frame(rt, push, W, H, m)
+        else:
+            rgba, lin = rt.render(W, H, t, want_linear=True)
+            st = rt.last_stats
+        return rgba, lin.view(np.uint32), int(st["traversals"]), int(st["kernel_variant"])
+
+    def same(got, want):
+        return all(np.array_equal(g, w) for g, w in zip(got, want))
+
+    want = {}
+    for mode in (UNI, COS):
+        for is_map in (False, True):
+            with rvcp_amd.RayTracer(spp=SPP, **ckw, **kw) as rt:
+                rt.sampling = mode
+                rt.upload_scene(sc)
+                want[mode, is_map] = frame(rt, is_map)
+            assert want[mode, is_map][3] & SPEC, "no specialised module ran"
+    o_lin, o_rgba, o_trav = O.render(scene_arrays(sc), push, abi.make_config(spp=SPP, **kw), W, H)
+    assert same(want[UNI, False][:3], (o_rgba, o_lin.view(np.uint32), o_trav))
+    e_rgba, e_lin = expected(name, W, H, m)
+    assert same(want[UNI, True][:2], (e_rgba, e_lin.view(np.uint32)))
+    for is_map in (False, True):           # (the switch shows: the two modes' frames differ)
+        assert not np.array_equal(want[UNI, is_map][1], want[COS, is_map][1])
+    with rvcp_amd.RayTracer(spp=SPP, **ckw, **kw) as rt:
+        rt.upload_scene(sc)
+        steps = [(UNI, False), (UNI, True), (COS, True), (COS, False), (UNI, False), (UNI, True)]
+        for i, (mode, is_map) in enumerate(steps):
+            rt.sampling = mode
+            assert same(frame(rt, is_map), want[mode, is_map]), (i, mode, is_map)
