@@ -263,6 +263,39 @@ typedef struct rvcp_gbuffer_texel {
     uint32_t material;      /* face.material_id | RVCP_GBUFFER_EMISSIVE when its ty is 3 */
 } rvcp_gbuffer_texel_t;
 
+/* ---------------------------------------------------------------------------------------
+ * Ray queries (rvcp_trace_rays_async; additions to 0.3.0, RVCP_ABI_VERSION
+ * stays 2).  No counterpart in the reference, whose only rays are its own.
+ * ------------------------------------------------------------------------------------- */
+/* One ray of a query: points origin + t direction with t_min <= t <= t_max.  The direction
+ * need not be normalised (t is in its units).  Every word must be finite: a ray with a NaN or an
+ * infinity anywhere is reported as a miss and is not traced -- the one place where a query
+ * decides before the scan does; it keeps such rays out of the tree.  A zero direction and
+ * t_min > t_max go through the arithmetic like any other ray (and hit nothing). */
+typedef struct rvcp_ray {
+    float origin[3];
+    float direction[3];
+    float t_min;
+    float t_max;
+} rvcp_ray_t;
+
+/* The nearest hit of one ray: what get_intersection_with_scene
+ * (ray_tracer_games101_branch.comp:283-296) keeps for it -- every face tested with
+ * is_intersect_with_face (:238-260), a hit accepted iff b1 >= 0, b2 >= 0, b1 + b2 <= 1 and
+ * t_min <= t <= bt, with bt starting at the ray's own t_max and shrinking to each accepted t, so
+ * that the later face wins at equal t.  face is numbered as rvcp_gbuffer_texel_t.face; t, b1, b2
+ * are the winning test's own values (the hit point is v0 + b1 e1 + b2 e2 = origin + t direction
+ * up to rounding).  A miss is face = -1 and zeros: the shader's t_max + 1 convention plays no
+ * part, so t_max needs no 2^24 cap. */
+typedef struct rvcp_ray_hit {
+    int32_t face;           /* face index, or -1 */
+    float t;
+    float b1, b2;           /* barycentric weights of the face's second and third vertex */
+} rvcp_ray_hit_t;
+
+#define RVCP_RAYS_NEAREST 0   /* d_out: n rvcp_ray_hit_t */
+#define RVCP_RAYS_ANY     1   /* d_out: n uint32_t, 1 = something lies in [t_min, t_max] */
+
 #define RVCP_DENOISE_MAX_ITERATIONS 8
 
 /* Parameters of rvcp_denoise_async (the filter's definition: DESIGN.md §4.9). */
@@ -388,6 +421,14 @@ RVCP_STATIC_ASSERT(sizeof(rvcp_gbuffer_texel_t) == 32, "G-buffer texel is 32 B")
 RVCP_STATIC_ASSERT(offsetof(rvcp_gbuffer_texel_t, face) == 12, "GBuffer.face @12");
 RVCP_STATIC_ASSERT(offsetof(rvcp_gbuffer_texel_t, normal) == 16, "GBuffer.normal @16");
 RVCP_STATIC_ASSERT(offsetof(rvcp_gbuffer_texel_t, material) == 28, "GBuffer.material @28");
+RVCP_STATIC_ASSERT(sizeof(rvcp_ray_t) == 32, "a ray is 32 B");
+RVCP_STATIC_ASSERT(offsetof(rvcp_ray_t, direction) == 12, "Ray.direction @12");
+RVCP_STATIC_ASSERT(offsetof(rvcp_ray_t, t_min) == 24, "Ray.t_min @24");
+RVCP_STATIC_ASSERT(offsetof(rvcp_ray_t, t_max) == 28, "Ray.t_max @28");
+RVCP_STATIC_ASSERT(sizeof(rvcp_ray_hit_t) == 16, "a ray hit is 16 B");
+RVCP_STATIC_ASSERT(offsetof(rvcp_ray_hit_t, t) == 4, "RayHit.t @4");
+RVCP_STATIC_ASSERT(offsetof(rvcp_ray_hit_t, b1) == 8, "RayHit.b1 @8");
+RVCP_STATIC_ASSERT(offsetof(rvcp_ray_hit_t, b2) == 12, "RayHit.b2 @12");
 RVCP_STATIC_ASSERT(sizeof(rvcp_denoise_params_t) == 16, "denoise params are 16 B");
 RVCP_STATIC_ASSERT(sizeof(rvcp_temporal_params_t) == 16, "temporal params are 16 B");
 RVCP_STATIC_ASSERT(offsetof(rvcp_temporal_params_t, max_history) == 4, "TemporalParams.max_history @4");
@@ -720,6 +761,53 @@ int rvcp_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push,
                          uint32_t width, uint32_t height, const rvcp_denoise_params_t *params,
                          uint8_t *out_rgba8, float *out_linear_rgb, rvcp_stats_t *stats,
                          float *denoise_ms);
+
+/* ---------------------------------------------------------------------------------------
+ * Ray queries: nearest hit and occlusion for rays the caller supplies (opt-in; no other entry
+ * point changes).  Triangles only, as the G-buffer: spheres are not tested.
+ * ------------------------------------------------------------------------------------- */
+
+/* Enqueue a query on `stream`: n_rays rvcp_ray_t in device memory (16-byte aligned) traced
+ * against the uploaded scene, one lane per ray, with the render's own tests -- the generic scan
+ * over every face, or with accel = RVCP_ACCEL_BVH the hybrid's prefix faces and then the tree,
+ * as rvcp_render_gbuffer_async -- so a result is the brute-force scan's, bit for bit (the
+ * struct comments above define it; the tree's exactness is argued in DESIGN.md §4.6 and tested
+ * on these very rays, §4.19).  mode RVCP_RAYS_NEAREST writes n_rays rvcp_ray_hit_t (16-byte
+ * aligned) to d_out; RVCP_RAYS_ANY writes n_rays uint32_t (4-byte aligned), 1 exactly where
+ * NEAREST would report a hit -- it may stop at the first accepted face, which only skips work
+ * NEAREST does after it already holds a hit.  Ordered on `stream` (NULL: the context's) like the
+ * other async calls, behind a render pending on the context (not an error) and behind the
+ * context's previous query; it is not the context's pending frame and touches no statistics.
+ * RVCP_E_INVALID: a NULL or zero argument, n_rays >= 2^31, another mode, a misaligned buffer.
+ * RVCP_E_NO_SCENE before an upload.  RVCP_E_UNSUPPORTED: a RVCP_INTEGRATOR_LEGACY or n_gpus > 1 context. */
+int rvcp_trace_rays_async(rvcp_ctx_t *ctx, const void *d_rays, uint32_t n_rays, uint32_t mode,
+                          void *d_out, void *stream);
+
+/* Wait for the context's last rvcp_trace_rays_async; *rays_ms (optional) gets its device time
+ * (HIP events on its stream).  RVCP_E_INVALID when no query was enqueued since the last call. */
+int rvcp_rays_wait(rvcp_ctx_t *ctx, float *rays_ms);
+
+/* The same query from and into host memory, synchronously, on the context's stream and through
+ * staging the context owns: out is n_rays rvcp_ray_hit_t or uint32_t by mode; *rays_ms
+ * (optional) gets its device time.  It is ordered behind a pending rvcp_trace_rays_async and
+ * leaves it pending: that query's rvcp_rays_wait still returns its own time. */
+int rvcp_trace_rays(rvcp_ctx_t *ctx, const rvcp_ray_t *rays, uint32_t n_rays, uint32_t mode,
+                    void *out, float *rays_ms);
+
+/* Enqueue on `stream` the W*H rays the pre-pass and the G-buffer trace, in pixel order
+ * (row-major), as rvcp_ray_t into device memory (16-byte aligned): origin the camera, direction
+ * normalised, [t_min, t_max] = [t_near, t_far] x t_coef (sample_ray, :217-235).  Tracing them
+ * with RVCP_RAYS_NEAREST gives the G-buffer's face at every pixel.  Restrictions and checks of
+ * rvcp_render_gbuffer_async (W*H < 2^31, t_far x t_coef < 2^24). */
+int rvcp_primary_rays_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                            uint32_t height, void *d_rays, void *stream);
+
+/* The nearest hit under pixel (x, y) of the W x H frame: that pixel's primary ray and a one-ray
+ * RVCP_RAYS_NEAREST query, synchronously, in buffers the context owns (and, as
+ * rvcp_trace_rays, without disturbing a pending rvcp_trace_rays_async).  RVCP_E_INVALID also for
+ * x >= width or y >= height. */
+int rvcp_pick(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width, uint32_t height,
+              uint32_t x, uint32_t y, rvcp_ray_hit_t *out_hit);
 
 /* ---------------------------------------------------------------------------------------
  * Temporal reprojection and accumulation of frames across calls (opt-in; no other entry point

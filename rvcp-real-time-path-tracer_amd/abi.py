@@ -66,6 +66,11 @@ ADAPTIVE_PARAMS_DTYPE = np.dtype([("spp_min", "<u4"), ("spp_max", "<u4"), ("mean
                                   ("weight_cap", "<f4"), ("epsilon", "<f4"), ("_pad", "<u4")])
 assert ADAPTIVE_PARAMS_DTYPE.itemsize == 24
 SPP_MAP_MAX = 256               # RVCP_SPP_MAP_MAX
+# rvcp_ray_t / rvcp_ray_hit_t (ray queries)
+RAY_DTYPE = np.dtype([("o", "<f4", (3,)), ("d", "<f4", (3,)), ("t_min", "<f4"), ("t_max", "<f4")])
+RAY_HIT_DTYPE = np.dtype([("face", "<i4"), ("t", "<f4"), ("b1", "<f4"), ("b2", "<f4")])
+assert RAY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 16
+RAYS_NEAREST, RAYS_ANY = 0, 1
 # rvcp_stats_t.kernel_variant -> the dominant kernel's name as rocprofv3 reports it
 KERNEL_NAMES = {1: "games101_kernel", 2: "games101_dual_kernel", 3: "games101_path_kernel<5>",
                 4: "games101_tiled_kernel", 5: "games101_tiled_single_kernel",
@@ -113,7 +118,9 @@ EXPORTED = ["rvcp_version", "rvcp_config_default", "rvcp_config_default_for", "r
             "rvcp_set_sampling", "rvcp_get_sampling",
             "rvcp_render_spp_map_async", "rvcp_adaptive_params_default", "rvcp_spp_plan_async",
             "rvcp_spp_plan_wait", "rvcp_set_adaptive", "rvcp_get_adaptive",
-            "rvcp_adaptive_last_map"]
+            "rvcp_adaptive_last_map",
+            "rvcp_trace_rays_async", "rvcp_rays_wait", "rvcp_trace_rays", "rvcp_primary_rays_async",
+            "rvcp_pick"]
 
 
 # Integrator mode 2 (ray_tracer.comp ray_trace): its own #defines (ray_tracer.comp:5-13).
@@ -360,6 +367,11 @@ def load():
     L.rvcp_set_adaptive.argtypes = [P, P]
     L.rvcp_get_adaptive.argtypes = [P, P, P]
     L.rvcp_adaptive_last_map.argtypes = [P, P, P, P]
+    L.rvcp_trace_rays_async.argtypes = [P, P, u32, u32, P, P]
+    L.rvcp_rays_wait.argtypes = [P, P]
+    L.rvcp_trace_rays.argtypes = [P, P, u32, u32, P, P]
+    L.rvcp_primary_rays_async.argtypes = [P, P, u32, u32, P, P]
+    L.rvcp_pick.argtypes = [P, P, u32, u32, u32, u32, P]
     for name in ("rvcp_config_default", "rvcp_config_default_for", "rvcp_create", "rvcp_destroy", "rvcp_upload_scene",
                  "rvcp_render", "rvcp_render_shard_async", "rvcp_sync_stats",
                  "rvcp_assemble_frame_async", "rvcp_upload_scene_file", "rvcp_mandelbrot",
@@ -381,7 +393,9 @@ def load():
                  "rvcp_taau_wait", "rvcp_set_taa_upsample", "rvcp_get_taa_upsample",
                  "rvcp_set_sampling", "rvcp_get_sampling", "rvcp_render_spp_map_async",
                  "rvcp_adaptive_params_default", "rvcp_spp_plan_async", "rvcp_spp_plan_wait",
-                 "rvcp_set_adaptive", "rvcp_get_adaptive", "rvcp_adaptive_last_map"):
+                 "rvcp_set_adaptive", "rvcp_get_adaptive", "rvcp_adaptive_last_map",
+                 "rvcp_trace_rays_async", "rvcp_rays_wait", "rvcp_trace_rays",
+                 "rvcp_primary_rays_async", "rvcp_pick"):
         getattr(L, name).restype = ctypes.c_int
     if L.rvcp_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI revision {L.rvcp_abi_version()}, this binding "

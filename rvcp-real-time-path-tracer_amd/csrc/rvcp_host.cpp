@@ -76,7 +76,7 @@ struct Stage {
 
 enum StageId {
     ST_DENOISE, ST_TEMPORAL, ST_SVGF_ACC, ST_SVGF_FLT, ST_DEMOD, ST_REMOD, ST_TAA, ST_TAAU, ST_PLAN,
-    N_STAGES
+    ST_RAYS, ST_RAYS_SYNC, N_STAGES
 };
 
 constexpr uint32_t stage_bit(StageId id) { return 1u << id; }
@@ -85,11 +85,15 @@ constexpr uint32_t stage_bit(StageId id) { return 1u << id; }
 // the temporal step, the TAA resolve and the upsampling step reuse what their own previous call
 // wrote (intermediates, or the history); the SVGF and the albedo steps share buffers from call to
 // call, so each waits for the context's previous SVGF accumulation and filter; the plan step of
-// adaptive sampling reuses its own priority plane and sums.  (In StageId order.)
+// adaptive sampling reuses its own priority plane and sums; a ray query is ordered behind the
+// context's previous one, asynchronous (ST_RAYS) or synchronous (ST_RAYS_SYNC: rvcp_trace_rays and
+// rvcp_pick, which bracket their query with events of their own so that they leave a pending
+// rvcp_trace_rays_async to its rvcp_rays_wait).  (In StageId order.)
 constexpr uint32_t kSvgfSteps = stage_bit(ST_SVGF_ACC) | stage_bit(ST_SVGF_FLT);
+constexpr uint32_t kRaySteps = stage_bit(ST_RAYS) | stage_bit(ST_RAYS_SYNC);
 constexpr uint32_t kStageBehind[N_STAGES] = {
     stage_bit(ST_DENOISE), stage_bit(ST_TEMPORAL), kSvgfSteps, kSvgfSteps, kSvgfSteps, kSvgfSteps,
-    stage_bit(ST_TAA), stage_bit(ST_TAAU), stage_bit(ST_PLAN)};
+    stage_bit(ST_TAA), stage_bit(ST_TAAU), stage_bit(ST_PLAN), kRaySteps, kRaySteps};
 
 // A history a stateful chain keeps from call to call, ping-ponging between slots `slot` (the
 // previous frame) and slot ^ 1
@@ -264,6 +268,10 @@ struct rvcp_ctx {
     uint32_t ad_slot = 0, ad_w = 0, ad_h = 0;
     int ad_last = -1;
     bool ad_valid = false;
+
+    // ray queries: the staging of the synchronous rvcp_trace_rays and rvcp_pick
+    void *d_q_rays = nullptr, *d_q_out = nullptr;
+    size_t cap_q_rays = 0, cap_q_out = 0;
 
     // albedo demodulation (rvcp_demodulate_async / rvcp_remodulate_async): the
     // scene's albedo table (one float4 per material, made by every upload) and the switch of
@@ -933,6 +941,8 @@ static int impl_destroy(rvcp_ctx_t *ctx)
         (void)hipFree(ctx->d_sv_tmp[i]);
     }
     free_svgf_state(ctx);
+    (void)hipFree(ctx->d_q_rays);
+    (void)hipFree(ctx->d_q_out);
     (void)hipFree(ctx->d_ad_q);
     (void)hipFree(ctx->d_ad_sums);
     (void)hipFree(ctx->d_ad_map[0]);
@@ -1915,6 +1925,158 @@ static int impl_denoise_async(rvcp_ctx_t *ctx, const void *d_in, const void *d_g
 static int impl_denoise_wait(rvcp_ctx_t *ctx, float *denoise_ms)
 {
     return stage_wait(ctx, ST_DENOISE, "no denoise in flight", denoise_ms);
+}
+
+// ---- ray queries ---------------------------------------------------------
+
+// the stack of the tree's traversal: kRayQueryLdsStack; the debug build's RVCP_DEBUG_RAYS_LDS=0/1
+// chooses per call (the A/B of tools/rays_time.py; the release library holds the kept form only)
+static int ray_query_lds_stack()
+{
+    const char *e = RVCP_KNOB("RVCP_DEBUG_RAYS_LDS");
+    return e && (*e == '0' || *e == '1') ? *e - '0' : (kRayQueryLdsStack ? 1 : 0);
+}
+
+// what the ray entry points share with rvcp_render_gbuffer_async: a games101 context that drives
+// one GPU and holds a scene
+static int rays_ctx_checked(rvcp_ctx_t *ctx, const char *what)
+{
+    if (ctx->cfg.integrator != RVCP_INTEGRATOR_GAMES101)
+        return fail(ctx, RVCP_E_UNSUPPORTED, std::string(what) + " is implemented for the games101 integrator");
+    if (!ctx->subs.empty())
+        return fail(ctx, RVCP_E_UNSUPPORTED, std::string(what) + " drives one GPU (n_gpus = 1)");
+    if (!ctx->has_scene) return fail(ctx, RVCP_E_NO_SCENE, std::string(what) + " before rvcp_upload_scene");
+    return RVCP_OK;
+}
+
+// one query enqueued under stage `id` (ST_RAYS: the caller's, ST_RAYS_SYNC: a synchronous call's)
+static int trace_rays_enqueue(rvcp_ctx_t *ctx, const void *d_rays, uint32_t n_rays, uint32_t mode,
+                              void *d_out, void *stream, StageId id)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!d_rays || !d_out || n_rays == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid ray query arguments");
+    if (n_rays >= (1u << 31))
+        return fail(ctx, RVCP_E_INVALID, "too many rays (n_rays must be < 2^31)");
+    if (mode != RVCP_RAYS_NEAREST && mode != RVCP_RAYS_ANY)
+        return fail(ctx, RVCP_E_INVALID, "ray query mode must be RVCP_RAYS_NEAREST or RVCP_RAYS_ANY");
+    if ((uintptr_t)d_rays % 16 || (uintptr_t)d_out % (mode == RVCP_RAYS_ANY ? 4 : 16))
+        return fail(ctx, RVCP_E_INVALID, "ray query buffers must be 16-byte aligned (4-byte: the "
+                    "RVCP_RAYS_ANY output)");
+    int rc;
+    if ((rc = rays_ctx_checked(ctx, "a ray query")) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    FrameArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.n_pixels = n_rays;
+    A.n_faces = ctx->n_faces;
+    A.accel = resolved_accel(ctx->cfg.accel, ctx->n_faces);
+    A.bvh_root = ctx->bvh_root;
+    A.bvh_n4 = ctx->bvh_n4;
+    A.bvh_slots = ctx->bvh_slots;
+    A.bvh_prefix = A.accel == RVCP_ACCEL_BVH ? ctx->bvh_prefix : 0u;
+    if ((rc = stage_begin(ctx, id, s)) != RVCP_OK) return rc;
+    if (rvcp_launch_ray_query(&A, ctx->d_tri, ctx->d_bvh_nodes, ctx->d_bvh_tris, d_rays,
+                              mode == RVCP_RAYS_ANY, ray_query_lds_stack(), d_out, s) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string("ray query launch failed: ") +
+                                         hipGetErrorString(hipGetLastError()));
+    return stage_end(ctx, id, s);
+}
+
+static int impl_trace_rays_async(rvcp_ctx_t *ctx, const void *d_rays, uint32_t n_rays,
+                                 uint32_t mode, void *d_out, void *stream)
+{
+    return trace_rays_enqueue(ctx, d_rays, n_rays, mode, d_out, stream, ST_RAYS);
+}
+
+static int impl_rays_wait(rvcp_ctx_t *ctx, float *rays_ms)
+{
+    return stage_wait(ctx, ST_RAYS, "no ray query in flight", rays_ms);
+}
+
+// the primary rays of pixels [first, first + count) of the W x H frame (the public call: all)
+static int primary_rays_launch(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                               uint32_t height, uint32_t first, uint32_t count, void *d_rays,
+                               hipStream_t s)
+{
+    int rc;
+    if ((rc = frame_size_checked(ctx, width, height)) != RVCP_OK) return rc;
+    if ((rc = rays_ctx_checked(ctx, "the primary rays' call")) != RVCP_OK) return rc;
+    if (!primary_t_range_ok(*push, width, height))
+        return fail(ctx, RVCP_E_INVALID, "camera t_far x t_coef must stay below 2^24 (the "
+                    "shader's miss test t_max + 1, :287, :424)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    FrameArgs A;
+    std::memset(&A, 0, sizeof(A));
+    primary_frame_args(ctx, *push, width, height, A);
+    A.shard_index = 0;
+    A.shard_count = 1;
+    A.n_pixels = width * height;
+    if (rvcp_launch_primary_rays(&A, first, count, d_rays, s) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string("primary rays launch failed: ") +
+                                         hipGetErrorString(hipGetLastError()));
+    return RVCP_OK;
+}
+
+static int impl_primary_rays_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push,
+                                   uint32_t width, uint32_t height, void *d_rays, void *stream)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!push || !d_rays || width == 0 || height == 0 || (uintptr_t)d_rays % 16)
+        return fail(ctx, RVCP_E_INVALID, "invalid primary rays arguments (d_rays: 16-byte aligned)");
+    return primary_rays_launch(ctx, push, width, height, 0, width * height, d_rays,
+                               stream ? (hipStream_t)stream : ctx->stream);
+}
+
+static int impl_trace_rays(rvcp_ctx_t *ctx, const rvcp_ray_t *rays, uint32_t n_rays, uint32_t mode,
+                           void *out, float *rays_ms)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!rays || !out || n_rays == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid ray query arguments");
+    if (n_rays >= (1u << 31))
+        return fail(ctx, RVCP_E_INVALID, "too many rays (n_rays must be < 2^31)");
+    if (mode != RVCP_RAYS_NEAREST && mode != RVCP_RAYS_ANY)
+        return fail(ctx, RVCP_E_INVALID, "ray query mode must be RVCP_RAYS_NEAREST or RVCP_RAYS_ANY");
+    int rc;
+    if ((rc = rays_ctx_checked(ctx, "a ray query")) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // (the staging is free: only the synchronous calls use it, and each waits for its query)
+    const size_t out_elem = mode == RVCP_RAYS_ANY ? sizeof(uint32_t) : sizeof(rvcp_ray_hit_t);
+    if ((rc = grow(ctx, &ctx->d_q_rays, &ctx->cap_q_rays, n_rays, sizeof(rvcp_ray_t))) != RVCP_OK) return rc;
+    if ((rc = grow(ctx, &ctx->d_q_out, &ctx->cap_q_out, n_rays, sizeof(rvcp_ray_hit_t))) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->d_q_rays, rays, (size_t)n_rays * sizeof(rvcp_ray_t),
+                           hipMemcpyHostToDevice));
+    if ((rc = trace_rays_enqueue(ctx, ctx->d_q_rays, n_rays, mode, ctx->d_q_out, ctx->stream,
+                                 ST_RAYS_SYNC)) != RVCP_OK)
+        return rc;
+    if ((rc = stage_sync(ctx, ST_RAYS_SYNC, rays_ms)) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipMemcpy(out, ctx->d_q_out, (size_t)n_rays * out_elem, hipMemcpyDeviceToHost));
+    return RVCP_OK;
+}
+
+static int impl_pick(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                     uint32_t height, uint32_t x, uint32_t y, rvcp_ray_hit_t *out_hit)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!push || !out_hit || width == 0 || height == 0 || x >= width || y >= height)
+        return fail(ctx, RVCP_E_INVALID, "invalid pick arguments (x < width, y < height)");
+    int rc;
+    if ((rc = frame_size_checked(ctx, width, height)) != RVCP_OK) return rc;
+    if ((rc = rays_ctx_checked(ctx, "a pick")) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = grow(ctx, &ctx->d_q_rays, &ctx->cap_q_rays, 1, sizeof(rvcp_ray_t))) != RVCP_OK) return rc;
+    if ((rc = grow(ctx, &ctx->d_q_out, &ctx->cap_q_out, 1, sizeof(rvcp_ray_hit_t))) != RVCP_OK) return rc;
+    if ((rc = primary_rays_launch(ctx, push, width, height, y * width + x, 1, ctx->d_q_rays,
+                                  ctx->stream)) != RVCP_OK)
+        return rc;
+    if ((rc = trace_rays_enqueue(ctx, ctx->d_q_rays, 1, RVCP_RAYS_NEAREST, ctx->d_q_out, ctx->stream,
+                                 ST_RAYS_SYNC)) != RVCP_OK)
+        return rc;
+    if ((rc = stage_sync(ctx, ST_RAYS_SYNC, nullptr)) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipMemcpy(out_hit, ctx->d_q_out, sizeof(*out_hit), hipMemcpyDeviceToHost));
+    return RVCP_OK;
 }
 
 // ---- temporal reprojection and accumulation -----------------------------
@@ -3603,6 +3765,35 @@ int rvcp_denoise_async(rvcp_ctx_t *ctx, const void *d_linear_rgb_in, const void 
 int rvcp_denoise_wait(rvcp_ctx_t *ctx, float *denoise_ms)
 {
     return barrier(ctx, [&] { return impl_denoise_wait(ctx, denoise_ms); });
+}
+
+int rvcp_trace_rays_async(rvcp_ctx_t *ctx, const void *d_rays, uint32_t n_rays, uint32_t mode,
+                          void *d_out, void *stream)
+{
+    return barrier(ctx, [&] { return impl_trace_rays_async(ctx, d_rays, n_rays, mode, d_out, stream); });
+}
+
+int rvcp_rays_wait(rvcp_ctx_t *ctx, float *rays_ms)
+{
+    return barrier(ctx, [&] { return impl_rays_wait(ctx, rays_ms); });
+}
+
+int rvcp_trace_rays(rvcp_ctx_t *ctx, const rvcp_ray_t *rays, uint32_t n_rays, uint32_t mode,
+                    void *out, float *rays_ms)
+{
+    return barrier(ctx, [&] { return impl_trace_rays(ctx, rays, n_rays, mode, out, rays_ms); });
+}
+
+int rvcp_primary_rays_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                            uint32_t height, void *d_rays, void *stream)
+{
+    return barrier(ctx, [&] { return impl_primary_rays_async(ctx, push, width, height, d_rays, stream); });
+}
+
+int rvcp_pick(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width, uint32_t height,
+              uint32_t x, uint32_t y, rvcp_ray_hit_t *out_hit)
+{
+    return barrier(ctx, [&] { return impl_pick(ctx, push, width, height, x, y, out_hit); });
 }
 
 int rvcp_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,

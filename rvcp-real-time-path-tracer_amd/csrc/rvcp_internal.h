@@ -217,6 +217,9 @@ constexpr int kBvhStack = 32;           // traversal stack entries per lane
 // them (2^-24 still loses some); the device's v_rcp_f32 adds up to 2^-23 to the model's IEEE
 // reciprocal, and 2^-21 is twice that sum.  Only ever conservative: it enters more boxes.
 constexpr float kBvhSlabSlack = 0x1p-21f;
+// The ray queries' traversal stack (ray_query_kernel): the private array, or (true) LDS columns.
+// Both are built; the measurement that chose is in DESIGN.md §4.19.
+constexpr bool kRayQueryLdsStack = true;
 
 // The traversed tree: up to 4 children per node, boxes stored per axis so one node is seven
 // 16-byte loads; a step tests the four boxes, pushes the hit children but the nearest (farthest
@@ -414,6 +417,17 @@ int rvcp_launch_mandelbrot(float pos_x, float pos_y, float scale, uint32_t width
 int rvcp_launch_gbuffer(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
                         const rvcp::FaceShade *shade, const rvcp::Bvh4Node *bvh_nodes,
                         const rvcp::TriRecord *bvh_tris, void *out, void *stream);
+// Ray queries (rvcp_trace_rays_async): args->n_pixels rays of 32 B from `rays`,
+// traced over args' faces (n_faces, or bvh_prefix and the tree with args->accel); `any` = 0: one
+// 16-B rvcp_ray_hit_t per ray into out, 1: one uint32_t.  lds_stack: the tree's stack in LDS
+// columns instead of the private array (the A/B of §4.19; the product passes kRayQueryLdsStack).
+int rvcp_launch_ray_query(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
+                          const rvcp::Bvh4Node *bvh_nodes, const rvcp::TriRecord *bvh_tris,
+                          const void *rays, int any, int lds_stack, void *out, void *stream);
+// The primary rays of pixels [first, first + count) of args' frame as rvcp_ray_t records into out
+// (rvcp_primary_rays_async, rvcp_pick)
+int rvcp_launch_primary_rays(const rvcp::FrameArgs *args, uint32_t first, uint32_t count, void *out,
+                             void *stream);
 // tonemap_kernel alone (the denoiser's RGBA8 store)
 int rvcp_launch_tonemap(const float *lin, uint32_t n, const float *gamma_t, uint32_t *out_rgba,
                         void *stream);

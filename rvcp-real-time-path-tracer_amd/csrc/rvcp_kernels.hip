@@ -541,6 +541,9 @@ typedef __attribute__((address_space(3))) int32_t lds_i32;
 // LDS = true: the stack is the caller's LDS column (stk[i * kBlock]; the lanes of a wave hit
 // distinct banks whatever their depths); LDS = false: a private array (the pre-pass kernel,
 // whose 1024-thread blocks would need 128 KiB of LDS).
+// (bvh_query, the ray queries' traversal further down, restates this function's PRIMARY form line
+// for line -- the slab arithmetic, the break rule, the sort and the push order -- with an early
+// exit for its ANY mode: a change to either belongs in both.)
 __device__ __forceinline__ void bvh4_cas(float &ka, int32_t &ca, float &kb, int32_t &cb) {
     const bool sw = kb < ka;
     const float k = sw ? kb : ka;
@@ -1891,6 +1894,176 @@ __global__ __launch_bounds__(kPrimaryBlock) void games101_gbuffer_kernel(
         out[2 * (size_t)pix + 1] = g1;
     }
 }
+
+#if !RVCP_GAMES101_ONLY  // (the ray queries exist in the default build only)
+// Ray queries (rvcp_trace_rays_async): the nearest hit, or whether there is one,
+// of rays the caller supplies -- what get_intersection_with_scene keeps for each, by the exact
+// test and the G-buffer kernel's order of tests.
+//
+// The tree's traversal for them: bvh_nearest in its PRIMARY form, and no other -- a caller's ray
+// may start anywhere, so the slab comparison is the conservative one (kBvhSlabSlack) and an
+// unused child slot is keyed +inf, never entered and never pushed; the stack then holds at most
+// what bvh4_collapse counted (§4.19), whatever the ray.  ANY: a lane that holds a hit leaves the
+// traversal; it skips only work the nearest-hit query does after it already holds one, so the
+// answer is that query's best >= 0.  LDS as bvh_nearest's.  All votes run among the lanes the
+// caller entered with; a lane that has left stays in the loops, idle, until the wave is done.
+// The body is bvh_nearest<LDS, true>'s, line for line, but for `alive`'s two ANY lines (its start
+// value and the drop after a leaf); it is a function of its own so that bvh_nearest's existing
+// instantiations keep their names and their instructions.  Keep the two in step: the slab
+// arithmetic, RVCP_BVH_NEAREST_BREAK_REL's rule, bvh4_cas's network and the push order.
+template <bool LDS, bool ANY>
+__device__ __forceinline__ void bvh_query(const Bvh4Node *__restrict__ nodes,
+                                          const TriRecord *__restrict__ btri, int32_t root,
+                                          lds_i32 *stk, f3 o, f3 d, float tmin, float &bt,
+                                          int &best, uint32_t n4, uint32_t slots) {
+    const f3 inv = slab_inv(d);
+    int32_t priv[LDS ? 1 : kBvhStack];
+    int sp = 0;
+    int32_t ref = root;
+    const Bvh4QNode *__restrict__ qn = reinterpret_cast<const Bvh4QNode *>(nodes + n4);
+    const bool px = inv.x >= 0.0f, py = inv.y >= 0.0f, pz = inv.z >= 0.0f;
+    bool alive = !(ANY && best >= 0), parked = false;
+    int32_t lref = 0;
+    for (;;) {
+        for (;;) {
+            if (alive && ref < 0 && !parked) {
+                parked = true;
+                lref = ref;
+                if (sp == 0) alive = false;
+                else { sp -= 1; ref = LDS ? stk[sp * kBlock] : priv[sp]; }
+            }
+            const bool step = alive && ref >= 0;
+            if (!__any(step) || __all(parked || !alive)) break;
+#if RVCP_BVH_NEAREST_BREAK_REL > 0
+            if (__popcll(__ballot(step)) * 64u <= (unsigned)RVCP_BVH_NEAREST_BREAK_REL * (unsigned)__popcll(__ballot(alive)) &&
+                __any(parked)) break;
+#endif
+            if (step) {
+                const float4 *q = reinterpret_cast<const float4 *>(qn + ref);
+                const float4 w0 = q[0], w1 = q[1], w2 = q[2];
+                const int4 r = reinterpret_cast<const int4 *>(qn + ref)[3];
+                const float ax = w0.w * inv.x, ay = w1.x * inv.y, az = w1.y * inv.z;
+                const float bx = (w0.x - o.x) * inv.x, by = (w0.y - o.y) * inv.y, bz = (w0.z - o.z) * inv.z;
+                const uint32_t lx = __float_as_uint(w1.z), ly = __float_as_uint(w1.w), lz = __float_as_uint(w2.x);
+                const uint32_t hx = __float_as_uint(w2.y), hy = __float_as_uint(w2.z), hz = __float_as_uint(w2.w);
+                const uint32_t nx = px ? lx : hx, fx = px ? hx : lx;
+                const uint32_t ny = py ? ly : hy, fy = py ? hy : ly;
+                const uint32_t nz = pz ? lz : hz, fz = pz ? hz : lz;
+                float kk[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const float tn = __builtin_fmaxf(
+                        __builtin_fmaxf(__builtin_fmaf(ubyte_f(nx, c), ax, bx), __builtin_fmaf(ubyte_f(ny, c), ay, by)),
+                        __builtin_fmaxf(__builtin_fmaf(ubyte_f(nz, c), az, bz), tmin));
+                    const float tf = __builtin_fminf(
+                        __builtin_fminf(__builtin_fmaf(ubyte_f(fx, c), ax, bx), __builtin_fmaf(ubyte_f(fy, c), ay, by)),
+                        __builtin_fminf(__builtin_fmaf(ubyte_f(fz, c), az, bz), bt));
+                    const float tfs = __builtin_fmaf(__builtin_fabsf(tf), kBvhSlabSlack, tf);
+                    const bool slot = ubyte_f(lx, c) <= ubyte_f(hx, c);      // unused: 255 > 0
+                    kk[c] = (tn <= tfs) & slot ? tn : __builtin_inff();
+                }
+                float k0 = kk[0], k1 = kk[1], k2 = kk[2], k3 = kk[3];
+                int32_t c0 = r.x, c1 = r.y, c2 = r.z, c3 = r.w;
+                bvh4_cas(k0, c0, k1, c1);
+                bvh4_cas(k2, c2, k3, c3);
+                bvh4_cas(k0, c0, k2, c2);
+                bvh4_cas(k1, c1, k3, c3);
+                bvh4_cas(k1, c1, k2, c2);
+                const float inf = __builtin_inff();
+                if (k3 < inf) { if (LDS) stk[sp * kBlock] = c3; else priv[sp] = c3; sp += 1; }
+                if (k2 < inf) { if (LDS) stk[sp * kBlock] = c2; else priv[sp] = c2; sp += 1; }
+                if (k1 < inf) { if (LDS) stk[sp * kBlock] = c1; else priv[sp] = c1; sp += 1; }
+                if (k0 < inf) ref = c0;
+                else if (sp == 0) alive = false;
+                else { sp -= 1; ref = LDS ? stk[sp * kBlock] : priv[sp]; }
+            }
+        }
+        if (parked) {
+            bvh_leaf(btri, lref, o, d, tmin, bt, best, slots);
+            parked = false;
+            if (ANY && best >= 0) alive = false;
+        }
+        if (!__any(alive)) break;
+    }
+}
+
+// A ray record's eight words are all finite (no exponent of all ones).  A ray that fails is a
+// miss and is not traced: the one place where a query decides before the scan does, so that no
+// NaN reaches the tree's slab arithmetic and stack.
+__device__ __forceinline__ bool ray_words_finite(float4 a, float4 b) {
+    const uint32_t e = 0x7F800000u;
+    const uint32_t w[8] = {__float_as_uint(a.x), __float_as_uint(a.y), __float_as_uint(a.z),
+                           __float_as_uint(a.w), __float_as_uint(b.x), __float_as_uint(b.y),
+                           __float_as_uint(b.z), __float_as_uint(b.w)};
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) ok &= (w[k] & e) != e;
+    return ok;
+}
+
+// One lane per ray, kBlock-lane blocks.  A ray enters as two 16-byte loads; BVH = false: the
+// generic scan with a wave-uniform index (scalar loads of the triangle records), BVH = true: the
+// hybrid's prefix faces, then the tree.  ANY: the scans stop once every traced lane of the wave
+// has a hit, and the answer is one word; else the hit leaves as one 16-byte store, its t, b1 and
+// b2 the winning test's own f (s2.e2), f n1, f n2, computed again from tri[best] by the same
+// operations (after the tree the winner's were not kept).
+template <bool BVH, bool ANY, bool LDS>
+__global__ __launch_bounds__(kBlock) void ray_query_kernel(
+    FrameArgs A, const TriRecord *__restrict__ tri, const Bvh4Node *__restrict__ bvh_nodes,
+    const TriRecord *__restrict__ bvh_tris, const float4 *__restrict__ rays, void *__restrict__ out)
+{
+    __shared__ int32_t stack[LDS ? kBvhStack * kBlock : 1];
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < A.n_pixels) {
+        const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];
+        const f3 o = mk(r0.x, r0.y, r0.z), d = mk(r0.w, r1.x, r1.y);
+        const float tmin = r1.z;
+        int best = -1;
+        float bt = r1.w;
+        if (ray_words_finite(r0, r1)) {
+            const uint32_t n_scan = BVH ? A.bvh_prefix : A.n_faces;
+#pragma unroll 2
+            for (uint32_t k = 0; k < n_scan; ++k) {
+                if (ANY && !__any(best < 0)) break;
+                float t;
+                if (tri_accept(tri[k], o, d, tmin, bt, t)) { bt = t; best = (int)k; }
+            }
+            if (BVH)
+                bvh_query<LDS, ANY>(bvh_nodes, bvh_tris, A.bvh_root, (lds_i32 *)stack + threadIdx.x,
+                                    o, d, tmin, bt, best, A.bvh_n4, A.bvh_slots);
+        }
+        if (ANY) {
+            static_cast<uint32_t *>(out)[i] = best >= 0 ? 1u : 0u;
+        } else {
+            float4 h = make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f);
+            if (best >= 0) {
+                const TriRecord T = tri[best];
+                const TriPart P = tri_stage1(T, o, d);
+                const float f = rcp_scan(P.den);
+                h = make_float4(__int_as_float(best), f * dot(P.s2, ld3(T.e2)), f * P.n1, f * P.n2);
+            }
+            static_cast<float4 *>(out)[i] = h;
+        }
+    }
+}
+
+// rvcp_primary_rays_async: the ray the pre-pass and the G-buffer trace through pixel first + lane
+// (pixel_uv, primary_ray), as a rvcp_ray_t record: two 16-byte stores.
+__global__ __launch_bounds__(kBlock) void primary_rays_kernel(FrameArgs A, uint32_t first,
+                                                              uint32_t count,
+                                                              float4 *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < count) {
+        float u_, v_, tmin, tmax;
+        f3 o, d;
+        pixel_uv(A, first + i, u_, v_);
+        primary_ray(A, u_, v_, o, d, tmin, tmax);
+        out[2 * (size_t)i] = make_float4(o.x, o.y, o.z, d.x);
+        out[2 * (size_t)i + 1] = make_float4(d.y, d.z, tmin, tmax);
+    }
+}
+#endif  // !RVCP_GAMES101_ONLY
 #endif
 
 // ======================================================================================
@@ -3648,6 +3821,40 @@ extern "C" int rvcp_launch_gbuffer(const rvcp::FrameArgs *args, const rvcp::TriR
                                    : rvcp::games101_gbuffer_kernel<false>,
                        dim3(blocks), dim3(rvcp::kPrimaryBlock), 0, (hipStream_t)stream, *args, tri,
                        shade, bvh_nodes, bvh_tris, (float4 *)out);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int rvcp_launch_ray_query(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
+                                     const rvcp::Bvh4Node *bvh_nodes,
+                                     const rvcp::TriRecord *bvh_tris, const void *rays, int any,
+                                     int lds_stack, void *out, void *stream)
+{
+    const uint32_t blocks = (args->n_pixels + rvcp::kBlock - 1) / rvcp::kBlock;
+    // the tree's stack: the release library holds the kept form (kRayQueryLdsStack) only; the
+    // debug build (make debug: -DRVCP_RAYS_STACK_AB) instantiates both for the A/B (lds_stack, §4.19)
+#ifdef RVCP_RAYS_STACK_AB
+    auto bvh = lds_stack
+        ? (any ? rvcp::ray_query_kernel<true, true, true> : rvcp::ray_query_kernel<true, false, true>)
+        : (any ? rvcp::ray_query_kernel<true, true, false> : rvcp::ray_query_kernel<true, false, false>);
+#else
+    (void)lds_stack;
+    auto bvh = any ? rvcp::ray_query_kernel<true, true, rvcp::kRayQueryLdsStack>
+                   : rvcp::ray_query_kernel<true, false, rvcp::kRayQueryLdsStack>;
+#endif
+    auto kern = !args->accel
+        ? (any ? rvcp::ray_query_kernel<false, true, false> : rvcp::ray_query_kernel<false, false, false>)
+        : bvh;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(rvcp::kBlock), 0, (hipStream_t)stream, *args, tri,
+                       bvh_nodes, bvh_tris, (const float4 *)rays, out);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int rvcp_launch_primary_rays(const rvcp::FrameArgs *args, uint32_t first,
+                                        uint32_t count, void *out, void *stream)
+{
+    const uint32_t blocks = (count + rvcp::kBlock - 1) / rvcp::kBlock;
+    hipLaunchKernelGGL(rvcp::primary_rays_kernel, dim3(blocks), dim3(rvcp::kBlock), 0,
+                       (hipStream_t)stream, *args, first, count, (float4 *)out);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

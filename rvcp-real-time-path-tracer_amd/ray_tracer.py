@@ -40,6 +40,7 @@ class RayTracer:
         self.last_denoise_ms = None
         self.last_svgf_accumulate_ms = None
         self.last_svgf_filter_ms = None
+        self.last_rays_ms = None
         # FPS counter (src/ray_tracer/ray_tracer.rs:80-86)
         self.fps_frame_count = 0
         self.fps_last_time = _time.perf_counter()
@@ -319,6 +320,55 @@ class RayTracer:
         self._check(self._lib.rvcp_denoise_wait(self._ctx, ctypes.cast(ctypes.byref(ms),
                                                                        ctypes.c_void_p)))
         return float(ms.value)
+
+    # ------------------------------------------------------------------ ray queries (§4.19)
+    def trace_rays_async(self, d_rays: int, n: int, d_out: int, mode: int = abi.RAYS_NEAREST,
+                         stream: int = 0):
+        """rvcp_trace_rays_async: enqueue a query of n abi.RAY_DTYPE rays in device memory;
+        d_out gets n abi.RAY_HIT_DTYPE records (RAYS_NEAREST) or n uint32 (RAYS_ANY).  Wait with
+        rays_wait()."""
+        P = ctypes.c_void_p
+        self._check(self._lib.rvcp_trace_rays_async(
+            self._ctx, P(d_rays) if d_rays else None, n, mode, P(d_out) if d_out else None,
+            P(stream) if stream else None))
+
+    def rays_wait(self) -> float:
+        """rvcp_rays_wait: block until the last trace_rays_async is done; its device time, ms."""
+        ms = ctypes.c_float(0.0)
+        self._check(self._lib.rvcp_rays_wait(self._ctx, ctypes.cast(ctypes.byref(ms),
+                                                                    ctypes.c_void_p)))
+        return float(ms.value)
+
+    def trace_rays(self, rays, mode: int = abi.RAYS_NEAREST) -> np.ndarray:
+        """rvcp_trace_rays: rays (abi.RAY_DTYPE records) from host memory, synchronously; returns
+        abi.RAY_HIT_DTYPE records (RAYS_NEAREST) or uint32 (RAYS_ANY) and sets last_rays_ms."""
+        rays = np.ascontiguousarray(rays, dtype=abi.RAY_DTYPE).reshape(-1)
+        out = np.empty(len(rays), dtype=np.uint32 if mode == abi.RAYS_ANY else abi.RAY_HIT_DTYPE)
+        ms = ctypes.c_float(0.0)
+        self._check(self._lib.rvcp_trace_rays(
+            self._ctx, abi.ptr(rays), len(rays), mode, abi.ptr(out),
+            ctypes.cast(ctypes.byref(ms), ctypes.c_void_p)))
+        self.last_rays_ms = float(ms.value)
+        return out
+
+    def primary_rays_async(self, push, width, height, d_rays: int, stream: int = 0):
+        """rvcp_primary_rays_async: enqueue the frame's width * height primary rays
+        (abi.RAY_DTYPE, pixel order) into device memory; ordered on the stream."""
+        push = np.ascontiguousarray(push, dtype=PUSH_DTYPE)
+        self._check(self._lib.rvcp_primary_rays_async(
+            self._ctx, abi.ptr(push), width, height, ctypes.c_void_p(d_rays) if d_rays else None,
+            ctypes.c_void_p(stream) if stream else None))
+
+    def pick(self, width: int, height: int, x: int, y: int, time: float = 0.0) -> np.ndarray:
+        """rvcp_pick: the nearest hit (one abi.RAY_HIT_DTYPE record) under pixel (x, y) of the
+        width x height frame through the uploaded scene's camera."""
+        if self.scene is None:
+            raise RuntimeError("upload_scene first")
+        push = np.ascontiguousarray(push_constant(self.scene.camera, time), dtype=PUSH_DTYPE)
+        hit = np.zeros((), dtype=abi.RAY_HIT_DTYPE)
+        self._check(self._lib.rvcp_pick(self._ctx, abi.ptr(push), width, height, x, y,
+                                        abi.ptr(hit)))
+        return hit
 
     def temporal_accumulate_async(self, view, d_cur_linear: int, d_cur_gbuffer: int,
                                   d_prev_linear: int, d_prev_gbuffer: int, d_prev_len: int,

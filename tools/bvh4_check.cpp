@@ -25,6 +25,7 @@
 // the nearest hit are culled (tn >= bt), 2 = the order rule without its tie half (t < bt),
 // 3 = the quantised lower bounds rounded inward, 4 = the build's box enlargement taken back,
 // 5 = unused child slots left to their inverted boxes alone (not keyed +inf) in the primary form.
+// -DBVH_CHECK_FUSED=1 is no fault: the triangle test with the device's fused dot and cross (tri()).
 #include <cstdio>
 #include <cstring>
 #include <cmath>
@@ -36,6 +37,9 @@
 using namespace rvcp;
 #ifndef BVH_CHECK_MUTATE
 #define BVH_CHECK_MUTATE 0
+#endif
+#ifndef BVH_CHECK_FUSED
+#define BVH_CHECK_FUSED 0
 #endif
 std::vector<float> P;
 static float g_slack = 0.0f;     // kBvhSlabSlack in rays mode unless `noslack` (the secondary rays' form)
@@ -51,15 +55,34 @@ static bool slab(const Bvh4Node &N, int i, const float *o, const float *inv, flo
     return tn <= tfs;
 #endif
 }
+static float dot3(const float *a, const float *b) { return std::fmaf(a[2], b[2], std::fmaf(a[1], b[1], a[0] * b[0])); }
+static void cross3(const float *a, const float *b, float *c) {
+    c[0] = std::fmaf(a[1], b[2], -(a[2] * b[1]));
+    c[1] = std::fmaf(a[2], b[0], -(a[0] * b[2]));
+    c[2] = std::fmaf(a[0], b[1], -(a[1] * b[0]));
+}
 static bool tri(const float *v, const float *o, const float *d, float tmin, float bt, float &t) {
     float e1[3] = {v[3]-v[0], v[4]-v[1], v[5]-v[2]}, e2[3] = {v[6]-v[0], v[7]-v[1], v[8]-v[2]};
     float s[3] = {o[0]-v[0], o[1]-v[1], o[2]-v[2]};
+#if BVH_CHECK_FUSED
+    // -DBVH_CHECK_FUSED=1: dot and cross as the device's and the oracle's fused chains (DESIGN.md
+    // §3.1), so that the brute column is the scan's own hit, bit for bit (tests/test_rays_cpu.py).
+    // The default build keeps the unfused products every figure of DESIGN.md §4.6 was measured with.
+    float s1[3], s2[3];
+    cross3(d, e2, s1);
+    cross3(s, e1, s2);
+    float ff = 1 / dot3(s1, e1);
+    t = ff * dot3(s2, e2);
+    float b1 = ff * dot3(s1, s);
+    float b2 = ff * dot3(s2, d);
+#else
     float s1[3] = {d[1]*e2[2]-d[2]*e2[1], d[2]*e2[0]-d[0]*e2[2], d[0]*e2[1]-d[1]*e2[0]};
     float s2[3] = {s[1]*e1[2]-s[2]*e1[1], s[2]*e1[0]-s[0]*e1[2], s[0]*e1[1]-s[1]*e1[0]};
     float ff = 1 / (s1[0]*e1[0]+s1[1]*e1[1]+s1[2]*e1[2]);
     t = ff * (s2[0]*e2[0]+s2[1]*e2[1]+s2[2]*e2[2]);
     float b1 = ff * (s1[0]*s[0]+s1[1]*s[1]+s1[2]*s[2]);
     float b2 = ff * (s2[0]*d[0]+s2[1]*d[1]+s2[2]*d[2]);
+#endif
     return b1 >= 0 && b2 >= 0 && b1 + b2 <= 1 && t >= tmin && t <= bt;
 }
 // the order rule of the leaf test (bvh_leaf): smaller t, or equal t and the later face
