@@ -810,6 +810,64 @@ int rvcp_pick(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
               uint32_t x, uint32_t y, rvcp_ray_hit_t *out_hit);
 
 /* ---------------------------------------------------------------------------------------
+ * Path queries: the radiance along rays the caller supplies (opt-in; no other entry point
+ * changes; additions to 0.3.0, RVCP_ABI_VERSION stays 2).  Triangles only, the
+ * games101 integrator with the uniform bounce.  No new structs: rays are rvcp_ray_t, seeds are
+ * float, a result is three float per ray, the layout of a linear frame.
+ * ------------------------------------------------------------------------------------- */
+
+/* Enqueue a query on `stream`: n_rays rvcp_ray_t (16-byte aligned) and n_rays float seeds
+ * (4-byte aligned) in device memory -> n_rays * 3 floats of linear RGB (4-byte aligned); spp in
+ * 1..RVCP_SPP_MAP_MAX.
+ *
+ * Result.  The result of ray i is what main (ray_tracer_games101_branch.comp:486-496) would leave
+ * in `color` for a pixel whose sample_ray is ray i taken as given (the direction is used as it is
+ * and is not normalised), whose srand result is seeds[i] (the rand() index starts at 0 and runs
+ * on from sample to sample) and whose SPP is spp: color += ray_trace(ray) / spp, spp times, in
+ * that order, with the context's max_bounces, rr_probability, eps, attenuation_stop_eps,
+ * ray_t_min, ray_t_max and light-pick quirk -- bit for bit.  The record's [t_min, t_max] bounds
+ * the first segment only; later segments use the configuration's range, as in the shader.
+ * "Nothing accepted" is a miss and adds the shader's 0.1: that is the shader's own t > t_max test
+ * (:424) for t_max < 2^24, where its t_max + 1 (:287) is still above t_max; a record with a
+ * larger t_max is traced all the same, by the absent face.
+ *
+ * Rejected rays.  A ray is not traced, draws no random number and returns (0, 0, 0) when any of
+ * its eight words is not finite, or when its seed is not in [0, 1) (a NaN seed is outside; srand
+ * only ever returns a fract).  It does not disturb the other rays of the query.
+ *
+ * Ordered on `stream` (NULL: the context's) like the other async calls, behind a render pending
+ * on the context (not an error) and behind the context's previous path query; one query is in
+ * flight per context (a second enqueue before rvcp_paths_wait replaces what the wait reports).
+ * It touches neither rvcp_stats_t nor the render's counters, and the ray queries not at all.
+ *
+ * RVCP_E_INVALID: a NULL or zero argument, n_rays >= 2^31, spp outside 1..RVCP_SPP_MAP_MAX, a
+ * misaligned buffer, an output that overlaps an input.  RVCP_E_NO_SCENE before an upload.
+ * RVCP_E_UNSUPPORTED: a RVCP_INTEGRATOR_LEGACY or n_gpus > 1 context, or one whose sampling mode
+ * is RVCP_SAMPLING_COSINE (the query kernel holds the uniform bounce only).  An error leaves the
+ * output untouched and nothing pending. */
+int rvcp_trace_paths_async(rvcp_ctx_t *ctx, const void *d_rays, const void *d_seeds,
+                           uint32_t n_rays, uint32_t spp, void *d_linear_rgb_out, void *stream);
+
+/* Wait for the pending path query: *paths_ms (optional) gets its device time (HIP events on its
+ * stream), *traversals (optional) the calls of get_intersection_with_scene it stands for, as the
+ * reference makes them: a first hit that the kernel keeps and reuses counts once per sample.
+ * RVCP_E_INVALID when no query was enqueued since the last call. */
+int rvcp_paths_wait(rvcp_ctx_t *ctx, float *paths_ms, uint64_t *traversals);
+
+/* The same from and to host memory, synchronously, on the context's stream and in staging the
+ * context owns.  It is ordered behind a pending rvcp_trace_paths_async and leaves it pending:
+ * that query's rvcp_paths_wait still returns its own time and traversals. */
+int rvcp_trace_paths(rvcp_ctx_t *ctx, const rvcp_ray_t *rays, const float *seeds, uint32_t n_rays,
+                     uint32_t spp, float *out_linear_rgb, float *paths_ms, uint64_t *traversals);
+
+/* Enqueue on `stream` the W*H seeds main() gives the frame's pixels, srand(push->time, u, v)
+ * (:153-155, :488-489), row-major, as float into device memory (4-byte aligned): the companion of
+ * rvcp_primary_rays_async, with its checks.  The frame's primary rays and these seeds through
+ * rvcp_trace_paths_async with the context's spp give rvcp_render_async's linear frame. */
+int rvcp_primary_seeds_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                             uint32_t height, void *d_seeds, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Temporal reprojection and accumulation of frames across calls (opt-in; no other entry point
  * changes).  No counterpart in the reference.
  * ------------------------------------------------------------------------------------- */

@@ -120,7 +120,9 @@ EXPORTED = ["rvcp_version", "rvcp_config_default", "rvcp_config_default_for", "r
             "rvcp_spp_plan_wait", "rvcp_set_adaptive", "rvcp_get_adaptive",
             "rvcp_adaptive_last_map",
             "rvcp_trace_rays_async", "rvcp_rays_wait", "rvcp_trace_rays", "rvcp_primary_rays_async",
-            "rvcp_pick"]
+            "rvcp_pick",
+            "rvcp_trace_paths_async", "rvcp_paths_wait", "rvcp_trace_paths",
+            "rvcp_primary_seeds_async"]
 
 
 # Integrator mode 2 (ray_tracer.comp ray_trace): its own #defines (ray_tracer.comp:5-13).
@@ -372,6 +374,10 @@ def load():
     L.rvcp_trace_rays.argtypes = [P, P, u32, u32, P, P]
     L.rvcp_primary_rays_async.argtypes = [P, P, u32, u32, P, P]
     L.rvcp_pick.argtypes = [P, P, u32, u32, u32, u32, P]
+    L.rvcp_trace_paths_async.argtypes = [P, P, P, u32, u32, P, P]
+    L.rvcp_paths_wait.argtypes = [P, P, P]
+    L.rvcp_trace_paths.argtypes = [P, P, P, u32, u32, P, P, P]
+    L.rvcp_primary_seeds_async.argtypes = [P, P, u32, u32, P, P]
     for name in ("rvcp_config_default", "rvcp_config_default_for", "rvcp_create", "rvcp_destroy", "rvcp_upload_scene",
                  "rvcp_render", "rvcp_render_shard_async", "rvcp_sync_stats",
                  "rvcp_assemble_frame_async", "rvcp_upload_scene_file", "rvcp_mandelbrot",
@@ -395,7 +401,9 @@ def load():
                  "rvcp_adaptive_params_default", "rvcp_spp_plan_async", "rvcp_spp_plan_wait",
                  "rvcp_set_adaptive", "rvcp_get_adaptive", "rvcp_adaptive_last_map",
                  "rvcp_trace_rays_async", "rvcp_rays_wait", "rvcp_trace_rays",
-                 "rvcp_primary_rays_async", "rvcp_pick"):
+                 "rvcp_primary_rays_async", "rvcp_pick",
+                 "rvcp_trace_paths_async", "rvcp_paths_wait", "rvcp_trace_paths",
+                 "rvcp_primary_seeds_async"):
         getattr(L, name).restype = ctypes.c_int
     if L.rvcp_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI revision {L.rvcp_abi_version()}, this binding "

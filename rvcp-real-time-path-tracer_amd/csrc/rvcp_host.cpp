@@ -76,7 +76,7 @@ struct Stage {
 
 enum StageId {
     ST_DENOISE, ST_TEMPORAL, ST_SVGF_ACC, ST_SVGF_FLT, ST_DEMOD, ST_REMOD, ST_TAA, ST_TAAU, ST_PLAN,
-    ST_RAYS, ST_RAYS_SYNC, N_STAGES
+    ST_RAYS, ST_RAYS_SYNC, ST_PATHS, ST_PATHS_SYNC, N_STAGES
 };
 
 constexpr uint32_t stage_bit(StageId id) { return 1u << id; }
@@ -88,12 +88,15 @@ constexpr uint32_t stage_bit(StageId id) { return 1u << id; }
 // adaptive sampling reuses its own priority plane and sums; a ray query is ordered behind the
 // context's previous one, asynchronous (ST_RAYS) or synchronous (ST_RAYS_SYNC: rvcp_trace_rays and
 // rvcp_pick, which bracket their query with events of their own so that they leave a pending
-// rvcp_trace_rays_async to its rvcp_rays_wait).  (In StageId order.)
+// rvcp_trace_rays_async to its rvcp_rays_wait); a path query likewise (ST_PATHS, and ST_PATHS_SYNC
+// for rvcp_trace_paths).  (In StageId order.)
 constexpr uint32_t kSvgfSteps = stage_bit(ST_SVGF_ACC) | stage_bit(ST_SVGF_FLT);
 constexpr uint32_t kRaySteps = stage_bit(ST_RAYS) | stage_bit(ST_RAYS_SYNC);
+constexpr uint32_t kPathSteps = stage_bit(ST_PATHS) | stage_bit(ST_PATHS_SYNC);
 constexpr uint32_t kStageBehind[N_STAGES] = {
     stage_bit(ST_DENOISE), stage_bit(ST_TEMPORAL), kSvgfSteps, kSvgfSteps, kSvgfSteps, kSvgfSteps,
-    stage_bit(ST_TAA), stage_bit(ST_TAAU), stage_bit(ST_PLAN), kRaySteps, kRaySteps};
+    stage_bit(ST_TAA), stage_bit(ST_TAAU), stage_bit(ST_PLAN), kRaySteps, kRaySteps,
+    kPathSteps, kPathSteps};
 
 // A history a stateful chain keeps from call to call, ping-ponging between slots `slot` (the
 // previous frame) and slot ^ 1
@@ -272,6 +275,13 @@ struct rvcp_ctx {
     // ray queries: the staging of the synchronous rvcp_trace_rays and rvcp_pick
     void *d_q_rays = nullptr, *d_q_out = nullptr;
     size_t cap_q_rays = 0, cap_q_out = 0;
+
+    // path queries: the staging of the synchronous rvcp_trace_paths, and the
+    // queries' own counter words (kPathCounterWords for ST_PATHS, then as many for ST_PATHS_SYNC:
+    // traversals, queue head, wave iterations), apart from the render's d_counters
+    void *d_p_rays = nullptr, *d_p_seeds = nullptr, *d_p_out = nullptr;
+    size_t cap_p_rays = 0, cap_p_seeds = 0, cap_p_out = 0;
+    unsigned long long *d_p_counters = nullptr;
 
     // albedo demodulation (rvcp_demodulate_async / rvcp_remodulate_async): the
     // scene's albedo table (one float4 per material, made by every upload) and the switch of
@@ -943,6 +953,10 @@ static int impl_destroy(rvcp_ctx_t *ctx)
     free_svgf_state(ctx);
     (void)hipFree(ctx->d_q_rays);
     (void)hipFree(ctx->d_q_out);
+    (void)hipFree(ctx->d_p_rays);
+    (void)hipFree(ctx->d_p_seeds);
+    (void)hipFree(ctx->d_p_out);
+    (void)hipFree(ctx->d_p_counters);
     (void)hipFree(ctx->d_ad_q);
     (void)hipFree(ctx->d_ad_sums);
     (void)hipFree(ctx->d_ad_map[0]);
@@ -1251,6 +1265,32 @@ static FramePlanIn frame_plan_input(const rvcp_ctx_t *ctx, uint32_t n_frames, ui
     return in;
 }
 
+// The shading parameters of a games101 launch: the configuration's, the scene's light table and
+// the constants derived from them (the render's and the path queries' FrameArgs share them)
+static void shading_frame_args(const rvcp_ctx_t *ctx, FrameArgs &A)
+{
+    A.max_bounces = ctx->cfg.max_bounces;
+    A.att_stop = ctx->cfg.attenuation_stop_eps;
+    A.t_min = ctx->cfg.ray_t_min;
+    A.t_max = ctx->cfg.ray_t_max;
+    A.rr = ctx->cfg.rr_probability;
+    A.eps = ctx->cfg.eps;
+    A.n_lights = ctx->n_lights;
+    A.lights_same = ctx->lights_same ? 1u : 0u;
+    A.rcp_fast = ctx->rcp_fast ? 1u : 0u;
+    A.has_metal = ctx->has_metal ? 1u : 0u;
+    A.light_total = ctx->light_total;
+    A.light_pdf = ctx->light_pdf;
+    {   // :465-471: denom = max(0.1, pdf) * rr, pdf = 0.5 / 3.1415926 (cos > 0) or 0; IEEE 1/denom
+        const float pdf1 = 0.5f / 3.1415926f;
+        A.brdf_den[1] = std::fmax(0.1f, pdf1) * A.rr;
+        A.brdf_den[0] = std::fmax(0.1f, 0.0f) * A.rr;
+        A.brdf_rcp[1] = 1.0f / A.brdf_den[1];
+        A.brdf_rcp[0] = 1.0f / A.brdf_den[0];
+    }
+    A.cos_k = 3.1415926f / A.rr;        // the cosine-weighted bounce's factor k = PI_F / rr
+}
+
 // n_frames consecutive frames of one shard (pushes[k] for frame k) into outputs laid out frame
 // after frame, `slot` = the largest shard's rows apart (rvcp_render_frames_async); n_frames = 1
 // is rvcp_render_shard_async.  d_spp_map (rvcp_render_spp_map_async; one whole frame): the
@@ -1313,26 +1353,7 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
     A.shard_count = shard_count;
     A.n_pixels = frame_px;
     A.spp = map ? spp_hint : ctx->cfg.spp;      // (a map build's kernels do not read it)
-    A.max_bounces = ctx->cfg.max_bounces;
-    A.att_stop = ctx->cfg.attenuation_stop_eps;
-    A.t_min = ctx->cfg.ray_t_min;
-    A.t_max = ctx->cfg.ray_t_max;
-    A.rr = ctx->cfg.rr_probability;
-    A.eps = ctx->cfg.eps;
-    A.n_lights = ctx->n_lights;
-    A.lights_same = ctx->lights_same ? 1u : 0u;
-    A.rcp_fast = ctx->rcp_fast ? 1u : 0u;
-    A.has_metal = ctx->has_metal ? 1u : 0u;
-    A.light_total = ctx->light_total;
-    A.light_pdf = ctx->light_pdf;
-    {   // :465-471: denom = max(0.1, pdf) * rr, pdf = 0.5 / 3.1415926 (cos > 0) or 0; IEEE 1/denom
-        const float pdf1 = 0.5f / 3.1415926f;
-        A.brdf_den[1] = std::fmax(0.1f, pdf1) * A.rr;
-        A.brdf_den[0] = std::fmax(0.1f, 0.0f) * A.rr;
-        A.brdf_rcp[1] = 1.0f / A.brdf_den[1];
-        A.brdf_rcp[0] = 1.0f / A.brdf_den[0];
-    }
-    A.cos_k = 3.1415926f / A.rr;        // the cosine-weighted bounce's factor k = PI_F / rr
+    shading_frame_args(ctx, A);
     A.want_linear = d_linear_rgb ? 1u : 0u;
     A.variant = P.variant;
     A.n_spheres = P.legacy ? ctx->n_spheres : 0u;
@@ -2076,6 +2097,162 @@ static int impl_pick(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t
         return rc;
     if ((rc = stage_sync(ctx, ST_RAYS_SYNC, nullptr)) != RVCP_OK) return rc;
     HIP_TRY(ctx, hipMemcpy(out_hit, ctx->d_q_out, sizeof(*out_hit), hipMemcpyDeviceToHost));
+    return RVCP_OK;
+}
+
+// ---- path queries --------------------------------------------------------
+
+constexpr size_t kPathCounterWords = 4;     // traversals, queue head, wave iterations, unused
+
+// the counter words of a path query under stage `id`
+static unsigned long long *path_counters(rvcp_ctx_t *ctx, StageId id)
+{
+    return ctx->d_p_counters + (id == ST_PATHS_SYNC ? kPathCounterWords : 0);
+}
+
+// the debug build's RVCP_DEBUG_PATHS_STATIC=1: one static ray per lane instead of the queue (the
+// A/B of tools/paths_time.py, §4.20; the product library runs the kept form only)
+static int path_query_static_lanes()
+{
+    const char *e = RVCP_KNOB("RVCP_DEBUG_PATHS_STATIC");
+    return e && *e == '1' ? 1 : 0;
+}
+
+// what the argument checks of the asynchronous and the synchronous call share
+static int trace_paths_checked(rvcp_ctx_t *ctx, const void *rays, const void *seeds,
+                               uint32_t n_rays, uint32_t spp, const void *out)
+{
+    if (!rays || !seeds || !out || n_rays == 0)
+        return fail(ctx, RVCP_E_INVALID, "invalid path query arguments");
+    if (n_rays >= (1u << 31))
+        return fail(ctx, RVCP_E_INVALID, "too many rays (n_rays must be < 2^31)");
+    if (spp < 1 || spp > RVCP_SPP_MAP_MAX)
+        return fail(ctx, RVCP_E_INVALID, "spp must be in 1..256");
+    int rc;
+    if ((rc = rays_ctx_checked(ctx, "a path query")) != RVCP_OK) return rc;
+    if (ctx->sampling == RVCP_SAMPLING_COSINE)
+        return fail(ctx, RVCP_E_UNSUPPORTED, "a path query is implemented for the uniform bounce "
+                    "(RVCP_SAMPLING_UNIFORM)");
+    return RVCP_OK;
+}
+
+// one query enqueued under stage `id` (ST_PATHS: the caller's, ST_PATHS_SYNC: rvcp_trace_paths')
+static int trace_paths_enqueue(rvcp_ctx_t *ctx, const void *d_rays, const void *d_seeds,
+                               uint32_t n_rays, uint32_t spp, void *d_out, void *stream, StageId id)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    int rc;
+    if ((rc = trace_paths_checked(ctx, d_rays, d_seeds, n_rays, spp, d_out)) != RVCP_OK) return rc;
+    if ((uintptr_t)d_rays % 16 || (uintptr_t)d_seeds % 4 || (uintptr_t)d_out % 4)
+        return fail(ctx, RVCP_E_INVALID, "path query buffers must be aligned (rays: 16 bytes, "
+                    "seeds and output: 4)");
+    if ((rc = overlap_checked(ctx, "a path query",
+                              {{d_rays, (size_t)n_rays * sizeof(rvcp_ray_t)},
+                               {d_seeds, (size_t)n_rays * sizeof(float)}},
+                              {{d_out, (size_t)n_rays * 3 * sizeof(float)}})) != RVCP_OK)
+        return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_p_counters) {
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_p_counters,
+                               2 * kPathCounterWords * sizeof(unsigned long long)));
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    FrameArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.n_pixels = n_rays;
+    A.spp = spp;
+    A.n_faces = ctx->n_faces;
+    A.accel = resolved_accel(ctx->cfg.accel, ctx->n_faces);
+    A.bvh_root = ctx->bvh_root;
+    A.bvh_n4 = ctx->bvh_n4;
+    A.bvh_slots = ctx->bvh_slots;
+    A.bvh_prefix = A.accel == RVCP_ACCEL_BVH ? ctx->bvh_prefix : 0u;
+    shading_frame_args(ctx, A);
+    A.n_mats = ctx->n_mats;
+    A.n_simds = ctx->n_simds;
+    A.shard_count = 1;
+    unsigned long long *counters = path_counters(ctx, id);
+    if ((rc = stage_begin(ctx, id, s)) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(counters, 0, kPathCounterWords * sizeof(unsigned long long), s));
+    if (rvcp_launch_path_query(&A, ctx->d_tri, ctx->d_shade, ctx->d_mats, ctx->d_lights,
+                               ctx->d_bvh_nodes, ctx->d_bvh_tris, d_rays, d_seeds, d_out, counters,
+                               ctx->cfg.grid_waves_per_simd, path_query_static_lanes(), s) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string("path query launch failed: ") +
+                                         hipGetErrorString(hipGetLastError()));
+    return stage_end(ctx, id, s);
+}
+
+// the traversals a finished query under stage `id` made
+static int paths_traversals(rvcp_ctx_t *ctx, StageId id, uint64_t *traversals)
+{
+    if (!traversals) return RVCP_OK;
+    unsigned long long t = 0;
+    HIP_TRY(ctx, hipMemcpy(&t, path_counters(ctx, id), sizeof(t), hipMemcpyDeviceToHost));
+    *traversals = t;
+    return RVCP_OK;
+}
+
+static int impl_trace_paths_async(rvcp_ctx_t *ctx, const void *d_rays, const void *d_seeds,
+                                  uint32_t n_rays, uint32_t spp, void *d_out, void *stream)
+{
+    return trace_paths_enqueue(ctx, d_rays, d_seeds, n_rays, spp, d_out, stream, ST_PATHS);
+}
+
+static int impl_paths_wait(rvcp_ctx_t *ctx, float *paths_ms, uint64_t *traversals)
+{
+    int rc;
+    if ((rc = stage_wait(ctx, ST_PATHS, "no path query in flight", paths_ms)) != RVCP_OK) return rc;
+    return paths_traversals(ctx, ST_PATHS, traversals);
+}
+
+static int impl_trace_paths(rvcp_ctx_t *ctx, const rvcp_ray_t *rays, const float *seeds,
+                            uint32_t n_rays, uint32_t spp, float *out, float *paths_ms,
+                            uint64_t *traversals)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    int rc;
+    if ((rc = trace_paths_checked(ctx, rays, seeds, n_rays, spp, out)) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // (the staging is free: only this call uses it, and it waits for its query)
+    if ((rc = grow(ctx, &ctx->d_p_rays, &ctx->cap_p_rays, n_rays, sizeof(rvcp_ray_t))) != RVCP_OK) return rc;
+    if ((rc = grow(ctx, &ctx->d_p_seeds, &ctx->cap_p_seeds, n_rays, sizeof(float))) != RVCP_OK) return rc;
+    if ((rc = grow(ctx, &ctx->d_p_out, &ctx->cap_p_out, n_rays, 3 * sizeof(float))) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->d_p_rays, rays, (size_t)n_rays * sizeof(rvcp_ray_t),
+                           hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_p_seeds, seeds, (size_t)n_rays * sizeof(float),
+                           hipMemcpyHostToDevice));
+    if ((rc = trace_paths_enqueue(ctx, ctx->d_p_rays, ctx->d_p_seeds, n_rays, spp, ctx->d_p_out,
+                                  ctx->stream, ST_PATHS_SYNC)) != RVCP_OK)
+        return rc;
+    if ((rc = stage_sync(ctx, ST_PATHS_SYNC, paths_ms)) != RVCP_OK) return rc;
+    HIP_TRY(ctx, hipMemcpy(out, ctx->d_p_out, (size_t)n_rays * 3 * sizeof(float),
+                           hipMemcpyDeviceToHost));
+    return paths_traversals(ctx, ST_PATHS_SYNC, traversals);
+}
+
+static int impl_primary_seeds_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push,
+                                    uint32_t width, uint32_t height, void *d_seeds, void *stream)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!push || !d_seeds || width == 0 || height == 0 || (uintptr_t)d_seeds % 4)
+        return fail(ctx, RVCP_E_INVALID, "invalid primary seeds arguments (d_seeds: 4-byte aligned)");
+    int rc;
+    if ((rc = frame_size_checked(ctx, width, height)) != RVCP_OK) return rc;
+    if ((rc = rays_ctx_checked(ctx, "the primary seeds' call")) != RVCP_OK) return rc;
+    if (!primary_t_range_ok(*push, width, height))
+        return fail(ctx, RVCP_E_INVALID, "camera t_far x t_coef must stay below 2^24 (the "
+                    "shader's miss test t_max + 1, :287, :424)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    FrameArgs A;
+    std::memset(&A, 0, sizeof(A));
+    primary_frame_args(ctx, *push, width, height, A);
+    A.shard_index = 0;
+    A.shard_count = 1;
+    A.n_pixels = width * height;
+    if (rvcp_launch_primary_seeds(&A, width * height, d_seeds,
+                                  stream ? (hipStream_t)stream : ctx->stream) != 0)
+        return fail(ctx, RVCP_E_HIP, std::string("primary seeds launch failed: ") +
+                                         hipGetErrorString(hipGetLastError()));
     return RVCP_OK;
 }
 
@@ -3794,6 +3971,33 @@ int rvcp_pick(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
               uint32_t x, uint32_t y, rvcp_ray_hit_t *out_hit)
 {
     return barrier(ctx, [&] { return impl_pick(ctx, push, width, height, x, y, out_hit); });
+}
+
+int rvcp_trace_paths_async(rvcp_ctx_t *ctx, const void *d_rays, const void *d_seeds,
+                           uint32_t n_rays, uint32_t spp, void *d_linear_rgb_out, void *stream)
+{
+    return barrier(ctx, [&] {
+        return impl_trace_paths_async(ctx, d_rays, d_seeds, n_rays, spp, d_linear_rgb_out, stream);
+    });
+}
+
+int rvcp_paths_wait(rvcp_ctx_t *ctx, float *paths_ms, uint64_t *traversals)
+{
+    return barrier(ctx, [&] { return impl_paths_wait(ctx, paths_ms, traversals); });
+}
+
+int rvcp_trace_paths(rvcp_ctx_t *ctx, const rvcp_ray_t *rays, const float *seeds, uint32_t n_rays,
+                     uint32_t spp, float *out_linear_rgb, float *paths_ms, uint64_t *traversals)
+{
+    return barrier(ctx, [&] {
+        return impl_trace_paths(ctx, rays, seeds, n_rays, spp, out_linear_rgb, paths_ms, traversals);
+    });
+}
+
+int rvcp_primary_seeds_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,
+                             uint32_t height, void *d_seeds, void *stream)
+{
+    return barrier(ctx, [&] { return impl_primary_seeds_async(ctx, push, width, height, d_seeds, stream); });
 }
 
 int rvcp_render_denoised(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,

@@ -428,6 +428,22 @@ int rvcp_launch_ray_query(const rvcp::FrameArgs *args, const rvcp::TriRecord *tr
 // (rvcp_primary_rays_async, rvcp_pick)
 int rvcp_launch_primary_rays(const rvcp::FrameArgs *args, uint32_t first, uint32_t count, void *out,
                              void *stream);
+// Path queries (rvcp_trace_paths_async): the radiance along args->n_pixels rays
+// of 32 B from `rays` with one float seed each, args->spp samples per ray with args' shading
+// parameters, three floats per ray into out.  A persistent grid over a queue, as the render
+// kernels': the launcher sizes it (at most the resident workgroups, or grid_waves_per_simd > 0
+// waves per SIMD) and fills args' queue members itself; static_lanes (the debug build's A/B of
+// §4.20, 0 in the product): one ray per lane in a grid of as many lanes as rays instead.
+// counters: four u64 words of the query's own, zeroed on the stream before the launch
+// ([0] traversals, [1] queue head, [2] iterations).
+int rvcp_launch_path_query(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
+                           const rvcp::FaceShade *shade, const rvcp::MatRecord *mats,
+                           const rvcp::LightRecord *lights, const rvcp::Bvh4Node *bvh_nodes,
+                           const rvcp::TriRecord *bvh_tris, const void *rays, const void *seeds,
+                           void *out, unsigned long long *counters, uint32_t grid_waves_per_simd,
+                           int static_lanes, void *stream);
+// The seeds of the first `count` pixels of args' frame, one float each (rvcp_primary_seeds_async)
+int rvcp_launch_primary_seeds(const rvcp::FrameArgs *args, uint32_t count, void *out, void *stream);
 // tonemap_kernel alone (the denoiser's RGBA8 store)
 int rvcp_launch_tonemap(const float *lin, uint32_t n, const float *gamma_t, uint32_t *out_rgba,
                         void *stream);

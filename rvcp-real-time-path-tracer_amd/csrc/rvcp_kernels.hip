@@ -2063,6 +2063,224 @@ __global__ __launch_bounds__(kBlock) void primary_rays_kernel(FrameArgs A, uint3
         out[2 * (size_t)i + 1] = make_float4(d.y, d.z, tmin, tmax);
     }
 }
+
+// Path queries (rvcp_trace_paths_async): the radiance main (:486-496) leaves in
+// `color` for a pixel whose sample_ray is ray i as given (the direction is not normalised), whose
+// srand result is seeds[i] and whose SPP is A.spp -- color += ray_trace(ray) / spp, spp times,
+// the rand() index running on from sample to sample.
+//
+// Variant 1's machine (games101_kernel above) on rays and seeds from a buffer: a settle loop that
+// advances every lane until it holds a ray to trace or is done, then one scan per iteration
+// shared by the lanes that hold a ray, and the queue (queue_init / queue_take over A.n_pixels =
+// the ray count; `counters` are the query's own words: [0] traversals, [1] queue head, [2] wave
+// iterations).  A lane's start is two 16-byte loads and its seed, its store three floats.  The
+// first hit is kept and reused by the later samples; a first hit that is a miss or a light is
+// the same L for every sample, without a random number (:424-427).  The ray's own [t_min, t_max]
+// bounds the first segment; shadow and path rays use A.t_min / A.t_max.  A miss is "nothing
+// accepted": the shader's t > t_max for t_max < 2^24.
+//
+// A ray is not traced, draws no random number and stores (0, 0, 0) when one of its eight words is
+// not finite or its seed is not in [0, 1) (a NaN seed is outside): rand_of's argument range
+// (seed + index in [1, 2^25]) is the one the sine and v_fract were checked on.  So does every ray
+// when the frame is "trivial" (:413-419: MAX_BOUNCES == 0 or ATTENUATION_STOP_EPS > 1 end every
+// sample before its first traversal).  Such a lane stays A_NEED and takes its next ray in the
+// same settle pass: the settle loop runs until no lane needs one, so a wave of rejected rays
+// cannot end the kernel early.
+//
+// BVH = false: the generic scan with a wave-uniform index (scalar loads of the triangle records).
+// BVH = true: the hybrid's prefix faces, then the tree through bvh_query<true, false> for every
+// kind of ray -- a caller's ray may start anywhere and a secondary ray wherever the exact test put
+// a sliver "hit", and bvh_query's form alone has a stack bound that holds for any ray (§4.19); the
+// stack is an LDS column per lane.  The shadow test needs the nearest hit's distance (:447-449),
+// so no ray leaves the traversal early.
+//
+// trav counts get_intersection_with_scene's calls as the shader makes them: the kept first hit
+// once per sample.
+template <bool BVH>
+__global__ __launch_bounds__(kBlock) void path_query_kernel(
+    FrameArgs A, const TriRecord *__restrict__ tri, const FaceShade *__restrict__ shade,
+    const MatRecord *__restrict__ mats, const LightRecord *__restrict__ lights,
+    const Bvh4Node *__restrict__ bvh_nodes, const TriRecord *__restrict__ bvh_tris,
+    const float4 *__restrict__ rays, const float *__restrict__ seeds, float *__restrict__ out,
+    unsigned long long *__restrict__ counters)
+{
+    __shared__ int32_t stack[BVH ? kBvhStack * kBlock : 1];
+    const uint32_t lane = lane_id();
+    Queue q = queue_init(A);
+    const float sppf = (float)A.spp;
+    const float inv_spp = rcp_ieee(sppf);     // divs_y's shared reciprocal
+    const bool trivial = A.max_bounces == 0 || 1.0f < A.att_stop;
+
+    int action = A_NEED, kind = K_PRIMARY;
+    uint32_t ray = 0, k = 0, depth = 0, trav = 0, iters = 0;
+    float seed = 0.0f, ridx = 0.0f;
+    f3 acc = mk(0, 0, 0), att = mk(1, 1, 1), col = mk(0, 0, 0);
+    f3 P_pos = mk(0, 0, 0), P_nrm = mk(0, 0, 0);   // the kept first hit (surface)
+    uint32_t P_mat = 0;
+    f3 S_pos = mk(0, 0, 0), S_nrm = mk(0, 0, 0);   // current shading point
+    uint32_t S_mat = 0;
+    f3 nee_C = mk(0, 0, 0);
+    float nee_dist = 0.0f;
+    f3 ro = mk(0, 0, 0), rd = mk(0, 0, 1);
+    float rtmin = 0.0f, rtmax = 0.0f;
+
+    for (;;) {
+        // ============ settle: advance every lane until it has a ray or is done ============
+        for (;;) {
+            if (action == A_RR) {                                   // :461-478
+                f3 wi;
+                if (!brdf_continue(A, mats[S_mat], S_nrm, seed, ridx, att, wi)) {
+                    action = A_END;
+                } else {
+                    depth += 1;
+                    ro = add(S_pos, muls(wi, A.eps));
+                    rd = wi;
+                    rtmin = A.t_min;
+                    rtmax = A.t_max;
+                    kind = K_PATH;
+                    action = (depth >= A.max_bounces || att_stop(A, att)) ? A_END : A_TRACE;
+                }
+            }
+            if (action == A_END) {                                  // color += L / SPP (:495)
+                acc = add(acc, divs_y(col, sppf, inv_spp));
+                k += 1;
+                if (k >= A.spp) {
+                    store_acc(ray, acc, out);
+                    action = A_NEED;
+                } else {
+                    trav += 1;                                      // the kept first hit, again
+                    depth = 0;
+                    att = mk(1, 1, 1);
+                    col = mk(0, 0, 0);
+                    S_pos = P_pos;
+                    S_nrm = P_nrm;
+                    S_mat = P_mat;
+                    action = A_SURF;
+                }
+            }
+            if (action == A_SURF) {                                 // :431-447
+                f3 ws;
+                if (!nee_sample(A, lights, ld3(mats[S_mat].alb_pi), S_pos, S_nrm, att, seed, ridx,
+                                nee_C, nee_dist, ws)) {
+                    action = A_RR;
+                } else {
+                    ro = add(S_pos, muls(ws, A.eps));
+                    rd = ws;
+                    rtmin = A.t_min;
+                    rtmax = A.t_max;
+                    kind = K_SHADOW;
+                    action = A_TRACE;
+                }
+            }
+            {   // take new rays from the queue (wave-uniform control flow)
+                bool got;
+                uint32_t nr = ray;
+                queue_take(q, __ballot(action == A_NEED), lane, A, counters, got, nr);
+                if (got) {
+                    ray = nr;
+                    const float4 r0 = rays[2 * (size_t)ray], r1 = rays[2 * (size_t)ray + 1];
+                    seed = seeds[ray];
+                    if (ray_words_finite(r0, r1) && seed >= 0.0f && seed < 1.0f && !trivial) {
+                        ro = mk(r0.x, r0.y, r0.z);
+                        rd = mk(r0.w, r1.x, r1.y);
+                        rtmin = r1.z;
+                        rtmax = r1.w;
+                        ridx = 0.0f;
+                        kind = K_PRIMARY;
+                        k = 0;
+                        acc = mk(0, 0, 0);
+                        action = A_TRACE;
+                    } else {
+                        store_acc(ray, mk(0, 0, 0), out);           // (stays A_NEED)
+                    }
+                }
+            }
+            if (q.exhausted && action == A_NEED) action = A_DONE;
+            if (!__any(action == A_RR || action == A_END || action == A_SURF || action == A_NEED))
+                break;
+        }
+        if (!__any(action == A_TRACE)) break;
+        iters += 1;
+
+        // ============ trace: nearest hit (:283-298) ============
+        int best = -1;
+        float bt = rtmax;
+        if (action == A_TRACE) {
+            trav += 1;
+            const uint32_t n_scan = BVH ? A.bvh_prefix : A.n_faces;
+            for (uint32_t i = 0; i < n_scan; ++i) {
+                float t;
+                if (tri_accept(tri[i], ro, rd, rtmin, bt, t)) { bt = t; best = (int)i; }
+            }
+            if (BVH)
+                bvh_query<true, false>(bvh_nodes, bvh_tris, A.bvh_root,
+                                       (lds_i32 *)stack + threadIdx.x, ro, rd, rtmin, bt, best,
+                                       A.bvh_n4, A.bvh_slots);
+        }
+
+        // ============ post-trace shading ============
+        if (action == A_TRACE) {
+            if (kind == K_SHADOW) {                                 // :447-459
+                const f3 hp = best >= 0 ? add(ro, muls(rd, bt))
+                                        : mk(__builtin_inff(), __builtin_inff(), __builtin_inff());
+                const float dist_blocked = len(sub(hp, S_pos));
+                if (__builtin_fabsf(nee_dist - dist_blocked) < A.eps) col = add(col, nee_C);
+                action = A_RR;
+            } else {
+                f3 hpos = mk(0, 0, 0), hn = mk(0, 0, 0);
+                FaceShade fs;
+                fs.mat = 0;
+                fs.ty = 0;
+                if (best >= 0) hit_shade(tri, shade, best, ro, rd, bt, hpos, hn, fs);
+                const bool miss = best < 0;
+                const bool is_light = !miss && fs.ty == kLight;
+                if (kind == K_PRIMARY) {
+                    if (miss || is_light) {
+                        // every sample returns the same L without touching the RNG:
+                        // miss -> 0.1 (:424), light at depth 0 -> Le (:425-427)
+                        const f3 L = miss ? mk(0.1f, 0.1f, 0.1f) : ld3(mats[fs.mat].albedo);
+                        const f3 Ls = divs(L, sppf);
+                        for (uint32_t i = 0; i < A.spp; ++i) acc = add(acc, Ls);
+                        trav += A.spp - 1;
+                        store_acc(ray, acc, out);
+                        action = A_NEED;
+                    } else {
+                        P_pos = hpos; P_nrm = hn; P_mat = fs.mat;
+                        S_pos = hpos; S_nrm = hn; S_mat = fs.mat;
+                        depth = 0;
+                        att = mk(1, 1, 1);
+                        col = mk(0, 0, 0);
+                        action = A_SURF;
+                    }
+                } else {                                            // K_PATH
+                    if (miss) {
+                        col = add(col, mk(0.1f, 0.1f, 0.1f));
+                        action = A_END;
+                    } else if (is_light) {
+                        action = A_END;     // depth >= 1: no emission term (:426)
+                    } else {
+                        S_pos = hpos; S_nrm = hn; S_mat = fs.mat;
+                        action = A_SURF;
+                    }
+                }
+            }
+        }
+    }
+    flush_counters(counters, lane, trav, iters);
+}
+
+// rvcp_primary_seeds_async: the seed main() gives pixel i, srand(push->time, uv) (:153-155,
+// :488-489): pixel_uv + pixel_seed, one float per pixel -- the companion of primary_rays_kernel.
+__global__ __launch_bounds__(kBlock) void primary_seeds_kernel(FrameArgs A, uint32_t count,
+                                                               float *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < count) {
+        float u_, v_;
+        pixel_uv(A, i, u_, v_);
+        out[i] = pixel_seed(A, u_, v_);
+    }
+}
 #endif  // !RVCP_GAMES101_ONLY
 #endif
 
@@ -3855,6 +4073,61 @@ extern "C" int rvcp_launch_primary_rays(const rvcp::FrameArgs *args, uint32_t fi
     const uint32_t blocks = (count + rvcp::kBlock - 1) / rvcp::kBlock;
     hipLaunchKernelGGL(rvcp::primary_rays_kernel, dim3(blocks), dim3(rvcp::kBlock), 0,
                        (hipStream_t)stream, *args, first, count, (float4 *)out);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int rvcp_launch_path_query(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
+                                      const rvcp::FaceShade *shade, const rvcp::MatRecord *mats,
+                                      const rvcp::LightRecord *lights,
+                                      const rvcp::Bvh4Node *bvh_nodes,
+                                      const rvcp::TriRecord *bvh_tris, const void *rays,
+                                      const void *seeds, void *out, unsigned long long *counters,
+                                      uint32_t grid_waves_per_simd, int static_lanes,
+                                      void *stream)
+{
+    auto kern = args->accel ? rvcp::path_query_kernel<true> : rvcp::path_query_kernel<false>;
+    // a persistent grid: at most what is resident, and the queue's static split over it, as the
+    // frame plan's for the render kernels (plan_frame)
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, rvcp::kBlock, 0) != hipSuccess ||
+        per_cu < 1)
+        return -2;
+    const uint32_t wpb = rvcp::kBlock / rvcp::kWave;
+    uint32_t cap = (uint32_t)per_cu * (args->n_simds / 4u);
+    if (grid_waves_per_simd > 0) {        // the caller's grid (rvcp_config_t::grid_waves_per_simd)
+        const uint64_t lim = (uint64_t)grid_waves_per_simd * args->n_simds / wpb;
+        if (lim < cap) cap = lim > 0 ? (uint32_t)lim : 1u;
+    }
+    rvcp::FrameArgs A = *args;
+    uint32_t waves = 0, chunk = 0;
+    rvcp::static_split(A.n_pixels, cap * wpb, A.n_simds, waves, chunk);
+    uint32_t blocks = (waves + wpb - 1) / wpb;
+    if (blocks > cap) blocks = cap;
+    if (blocks == 0) blocks = 1;
+    A.static_chunk = chunk;
+    A.static_chunks = waves * chunk;
+    if (static_lanes) {
+        // the A/B of §4.20 (debug build's knob only): one ray per lane and a grid of as many
+        // lanes as rays, so that no wave ever comes back to the queue
+        blocks = (A.n_pixels + rvcp::kBlock - 1) / rvcp::kBlock;
+        A.static_chunk = rvcp::kWave;
+        A.static_chunks = blocks * rvcp::kBlock;
+    }
+    A.dyn_chunk = rvcp::kDynChunk;
+    A.chunk_min = rvcp::kMinChunk;
+    A.chunk_window = rvcp::kChunkWindow;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(rvcp::kBlock), 0, (hipStream_t)stream, A, tri, shade,
+                       mats, lights, bvh_nodes, bvh_tris, (const float4 *)rays, (const float *)seeds,
+                       (float *)out, counters);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int rvcp_launch_primary_seeds(const rvcp::FrameArgs *args, uint32_t count, void *out,
+                                         void *stream)
+{
+    const uint32_t blocks = (count + rvcp::kBlock - 1) / rvcp::kBlock;
+    hipLaunchKernelGGL(rvcp::primary_seeds_kernel, dim3(blocks), dim3(rvcp::kBlock), 0,
+                       (hipStream_t)stream, *args, count, (float *)out);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

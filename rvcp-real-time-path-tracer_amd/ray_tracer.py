@@ -41,6 +41,8 @@ class RayTracer:
         self.last_svgf_accumulate_ms = None
         self.last_svgf_filter_ms = None
         self.last_rays_ms = None
+        self.last_paths_ms = None
+        self.last_paths_traversals = None
         # FPS counter (src/ray_tracer/ray_tracer.rs:80-86)
         self.fps_frame_count = 0
         self.fps_last_time = _time.perf_counter()
@@ -369,6 +371,59 @@ class RayTracer:
         self._check(self._lib.rvcp_pick(self._ctx, abi.ptr(push), width, height, x, y,
                                         abi.ptr(hit)))
         return hit
+
+    # ------------------------------------------------------------------ path queries (§4.20)
+    def trace_paths_async(self, d_rays: int, d_seeds: int, n: int, spp: int, d_out: int,
+                          stream: int = 0):
+        """rvcp_trace_paths_async: enqueue a query of n abi.RAY_DTYPE rays and n float32 seeds in
+        device memory, spp samples per ray; d_out gets n x 3 float32 of linear RGB.  Wait with
+        paths_wait()."""
+        P = ctypes.c_void_p
+        self._check(self._lib.rvcp_trace_paths_async(
+            self._ctx, P(d_rays) if d_rays else None, P(d_seeds) if d_seeds else None, n, spp,
+            P(d_out) if d_out else None, P(stream) if stream else None))
+
+    def paths_wait(self):
+        """rvcp_paths_wait: block until the last trace_paths_async is done; (its device time in
+        ms, the traversals it made)."""
+        ms = ctypes.c_float(0.0)
+        trav = ctypes.c_uint64(0)
+        self._check(self._lib.rvcp_paths_wait(self._ctx,
+                                              ctypes.cast(ctypes.byref(ms), ctypes.c_void_p),
+                                              ctypes.cast(ctypes.byref(trav), ctypes.c_void_p)))
+        return float(ms.value), int(trav.value)
+
+    def trace_paths(self, rays, seeds=None, spp: Optional[int] = None, seed: int = 0) -> np.ndarray:
+        """rvcp_trace_paths: the radiance along rays (abi.RAY_DTYPE records) from host memory,
+        synchronously: an (n, 3) float32 array of linear RGB.  seeds: one float32 in [0, 1) per
+        ray, or None to draw them from numpy.random.default_rng(seed); spp: samples per ray, or
+        None for the context's.  Sets last_paths_ms and last_paths_traversals."""
+        rays = np.ascontiguousarray(rays, dtype=abi.RAY_DTYPE).reshape(-1)
+        if seeds is None:
+            seeds = np.random.default_rng(seed).random(len(rays), dtype=np.float32)
+        seeds = np.ascontiguousarray(seeds, dtype=np.float32).reshape(-1)
+        if len(seeds) != len(rays):
+            raise ValueError("one seed per ray")
+        if spp is None:
+            spp = int(np.asarray(self.config["spp"]).reshape(-1)[0])
+        out = np.empty((len(rays), 3), dtype=np.float32)
+        ms = ctypes.c_float(0.0)
+        trav = ctypes.c_uint64(0)
+        self._check(self._lib.rvcp_trace_paths(
+            self._ctx, abi.ptr(rays), abi.ptr(seeds), len(rays), spp, abi.ptr(out),
+            ctypes.cast(ctypes.byref(ms), ctypes.c_void_p),
+            ctypes.cast(ctypes.byref(trav), ctypes.c_void_p)))
+        self.last_paths_ms = float(ms.value)
+        self.last_paths_traversals = int(trav.value)
+        return out
+
+    def primary_seeds_async(self, push, width, height, d_seeds: int, stream: int = 0):
+        """rvcp_primary_seeds_async: enqueue the frame's width * height pixel seeds (float32,
+        pixel order) into device memory; ordered on the stream."""
+        push = np.ascontiguousarray(push, dtype=PUSH_DTYPE)
+        self._check(self._lib.rvcp_primary_seeds_async(
+            self._ctx, abi.ptr(push), width, height, ctypes.c_void_p(d_seeds) if d_seeds else None,
+            ctypes.c_void_p(stream) if stream else None))
 
     def temporal_accumulate_async(self, view, d_cur_linear: int, d_cur_gbuffer: int,
                                   d_prev_linear: int, d_prev_gbuffer: int, d_prev_len: int,
