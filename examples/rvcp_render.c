@@ -5,13 +5,16 @@
  * a binary PPM and prints one JSON line of stats per frame.
  *
  *   make -C examples            # gcc, links ../rvcp-real-time-path-tracer_amd/csrc/build/librvcp.so
- *   examples/build/rvcp_render scene.rvcpscn W H SPP TIME FRAMES out.ppm [--cosine | --adaptive]
+ *   examples/build/rvcp_render scene.rvcpscn W H SPP TIME FRAMES out.ppm
+ *                              [--cosine | --adaptive | --materials]
  *
  * --cosine: trace with the cosine-weighted bounce (rvcp_set_sampling) instead of
  * the shader's uniform one: less noise per sample, frames no longer the reference's bit for bit.
  * --adaptive: every frame through SVGF (rvcp_render_svgf) with adaptive sampling
  * (rvcp_set_adaptive) at a budget of SPP samples per pixel: the samples go where
  * the previous frame's variance says the error is; `samples` is what the frame really traced.
+ * --materials: Metal and Dielectric faces reflect and refract by their material
+ * (rvcp_set_materials) instead of being shaded as Lambertian surfaces.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,9 +33,10 @@ int main(int argc, char **argv)
 {
     const int cosine = argc == 9 && strcmp(argv[8], "--cosine") == 0;
     const int adaptive = argc == 9 && strcmp(argv[8], "--adaptive") == 0;
-    if (argc != 8 && !cosine && !adaptive) {
-        fprintf(stderr, "usage: %s scene.rvcpscn W H SPP TIME FRAMES out.ppm [--cosine | --adaptive]\n",
-                argv[0]);
+    const int materials = argc == 9 && strcmp(argv[8], "--materials") == 0;
+    if (argc != 8 && !cosine && !adaptive && !materials) {
+        fprintf(stderr, "usage: %s scene.rvcpscn W H SPP TIME FRAMES out.ppm "
+                "[--cosine | --adaptive | --materials]\n", argv[0]);
         return 2;
     }
     const uint32_t W = (uint32_t)strtoul(argv[2], NULL, 10);
@@ -57,6 +61,10 @@ int main(int argc, char **argv)
     if (cosine) {                             /* no counterpart in the reference */
         rc = rvcp_set_sampling(ctx, RVCP_SAMPLING_COSINE);
         if (rc) return die(ctx, "rvcp_set_sampling", rc);
+    }
+    if (materials) {                          /* the shader reads the type of lights only (:425) */
+        rc = rvcp_set_materials(ctx, RVCP_MATERIALS_SCATTER);
+        if (rc) return die(ctx, "rvcp_set_materials", rc);
     }
     if (adaptive) {                           /* no counterpart in the reference */
         rvcp_adaptive_params_t ap;

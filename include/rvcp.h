@@ -227,7 +227,8 @@ typedef struct rvcp_stats {
     uint32_t faces;                   /* F, triangles tested per traversal */
     int32_t kernel_variant;           /* the kernel schedule that ran (rvcp_config_t::
                                          kernel_variant resolved; 7 = BVH path kernel,
-                                         8 = RVCP_INTEGRATOR_LEGACY kernel, 0 = none), plus
+                                         8 = RVCP_INTEGRATOR_LEGACY kernel, 11 = the
+                                         RVCP_MATERIALS_SCATTER kernel, 0 = none), plus
                                          RVCP_VARIANT_SPECIALIZED when the scene-specialised
                                          path kernel ran */
     uint64_t wave_iterations;         /* wave-level trace iterations; lane utilisation of the
@@ -1237,6 +1238,53 @@ int rvcp_set_sampling(rvcp_ctx_t *ctx, int32_t sampling);
 
 /* *sampling = the context's bounce sampling. */
 int rvcp_get_sampling(rvcp_ctx_t *ctx, int32_t *sampling);
+
+/* ---------------------------------------------------------------------------------------
+ * Material scattering on meshes (opt-in).  ray_tracer_games101_branch.comp
+ * defines the four material types (:22-25) and reads one: the light test (:425).  Every other
+ * face is shaded as a Lambertian surface, whatever rvcp_material_t::ty says.
+ * ------------------------------------------------------------------------------------- */
+
+/* RVCP_MATERIALS_LAMBERTIAN (the default): the shader's behaviour, bit-identical to the oracle.
+ * RVCP_MATERIALS_SCATTER: ray_trace_games101 (:406-482) with these changes and no other.
+ *   - At a hit on a Metal or Dielectric face no light sample is drawn and no shadow ray traced.
+ *     The roulette comes first (:462), then the new direction and colour (nd, na) are
+ *     material_scatter's for the type (ray_tracer.comp:515-581: metal reflects, flips the
+ *     reflection into the normal's hemisphere and redraws normalize(r + fuzz * unit vector) while
+ *     it points below the surface, na = albedo; dielectric picks its ratio by the hit's `outward`
+ *     flag, tests total internal reflection, compares one rand() with Schlick only when
+ *     refraction is possible, na = 1), attenuation *= na / RR_PROBABILITY, and the next ray is
+ *     Ray(p + nd * EPS, nd, RAY_T_MIN, RAY_T_MAX).  The metal redraw is bounded: after 16
+ *     rejected draws nd = normalize(r).
+ *   - The emission rule (:426) becomes depth == 0 || the previous vertex was specular: a light
+ *     seen in a mirror or through glass counts once.  The miss term (:424) is unchanged.
+ *   - Shadow rays are unchanged: a metal or glass face blocks them like any face.
+ * While it is set, rvcp_trace_paths(_async) run its kernel, and rvcp_render, rvcp_render_async
+ * and rvcp_render_shard_async (shard_count = 1) render through it: the frame's primary rays and
+ * seeds, that kernel, the tone map -- the generic scan or the BVH, not the scene-specialised
+ * kernels.  rvcp_stats_t::kernel_variant is then 11, and traversals is counted by the kernel.
+ * rvcp_render_denoised, rvcp_render_temporal and rvcp_render_svgf run on top unchanged (their
+ * G-buffer is still the primary hit).  RVCP_E_UNSUPPORTED, before any launch: n_frames > 1,
+ * shard_count > 1, rvcp_render_spp_map_async (and so the adaptive switch).  Ray queries and the
+ * G-buffer do not depend on the mode.
+ * A scene is accepted only if every Metal material has a finite fuzz in [0, 1] and every
+ * Dielectric a finite refraction_ratio > 0: rvcp_upload_scene while the mode is set, and
+ * rvcp_set_materials on a loaded scene, return RVCP_E_INVALID naming the material otherwise. */
+#define RVCP_MATERIALS_LAMBERTIAN 0
+#define RVCP_MATERIALS_SCATTER 1
+
+/* Set the context's materials mode; it holds from the next render or path query on and across
+ * rvcp_upload_scene.  Changing the value drops the temporal, SVGF, TAA and upsampling
+ * histories; setting the value it has does nothing.  RVCP_E_INVALID: a null context, an unknown
+ * value, a frame pending, a loaded scene with an invalid fuzz or refraction_ratio.
+ * RVCP_E_UNSUPPORTED for RVCP_MATERIALS_SCATTER on a RVCP_INTEGRATOR_LEGACY context (mode 2
+ * scatters by material already), an n_gpus > 1 context, or one whose sampling is
+ * RVCP_SAMPLING_COSINE; rvcp_set_sampling(RVCP_SAMPLING_COSINE) is refused likewise while the
+ * mode is set.  No counterpart in the reference. */
+int rvcp_set_materials(rvcp_ctx_t *ctx, int32_t materials);
+
+/* *materials = the context's materials mode. */
+int rvcp_get_materials(rvcp_ctx_t *ctx, int32_t *materials);
 
 /* ---------------------------------------------------------------------------------------
  * Adaptive sampling (opt-in): frames traced with a per-pixel sample count, a

@@ -75,7 +75,7 @@ RAYS_NEAREST, RAYS_ANY = 0, 1
 KERNEL_NAMES = {1: "games101_kernel", 2: "games101_dual_kernel", 3: "games101_path_kernel<5>",
                 4: "games101_tiled_kernel", 5: "games101_tiled_single_kernel",
                 6: "games101_path_kernel<6>", 7: "games101_bvh_path_kernel", 8: "legacy_kernel",
-                10: "games101_tiled_pool_kernel",
+                10: "games101_tiled_pool_kernel", 11: "path_scatter_kernel",
                 # + RVCP_VARIANT_SPECIALIZED (16): the scene-specialised module (rvcp_jit.cpp)
                 19: "rvcp_spec_path_kernel5", 22: "rvcp_spec_path_kernel6", 23: "rvcp_spec_bvh_path_kernel",
                 24: "rvcp_spec_legacy_kernel"}
@@ -115,7 +115,7 @@ EXPORTED = ["rvcp_version", "rvcp_config_default", "rvcp_config_default_for", "r
             "rvcp_taa_reset",
             "rvcp_taau_params_default", "rvcp_taa_upsample_async", "rvcp_taau_wait",
             "rvcp_set_taa_upsample", "rvcp_get_taa_upsample",
-            "rvcp_set_sampling", "rvcp_get_sampling",
+            "rvcp_set_sampling", "rvcp_get_sampling", "rvcp_set_materials", "rvcp_get_materials",
             "rvcp_render_spp_map_async", "rvcp_adaptive_params_default", "rvcp_spp_plan_async",
             "rvcp_spp_plan_wait", "rvcp_set_adaptive", "rvcp_get_adaptive",
             "rvcp_adaptive_last_map",
@@ -136,6 +136,8 @@ UNORM_DRIVER, UNORM_NEAREST = 0, 1
 SPECIALIZE_AUTO, SPECIALIZE_OFF = 0, 1
 # rvcp_set_sampling: the games101 bounce
 SAMPLING_UNIFORM, SAMPLING_COSINE = 0, 1
+# rvcp_set_materials: material scattering on meshes
+MATERIALS_LAMBERTIAN, MATERIALS_SCATTER = 0, 1
 
 
 def make_config(**kw) -> np.ndarray:
@@ -362,6 +364,8 @@ def load():
     L.rvcp_get_taa_upsample.argtypes = [P, P]
     L.rvcp_set_sampling.argtypes = [P, ctypes.c_int32]
     L.rvcp_get_sampling.argtypes = [P, P]
+    L.rvcp_set_materials.argtypes = [P, ctypes.c_int32]
+    L.rvcp_get_materials.argtypes = [P, P]
     L.rvcp_render_spp_map_async.argtypes = [P, P, u32, u32, P, u32, P, P, P]
     L.rvcp_adaptive_params_default.argtypes = [P]
     L.rvcp_spp_plan_async.argtypes = [P, P, P, P, P, u32, u32, P, P, P]
@@ -397,7 +401,8 @@ def load():
                  "rvcp_taa_resolve_async", "rvcp_taa_wait", "rvcp_set_taa", "rvcp_get_taa",
                  "rvcp_taa_reset", "rvcp_taau_params_default", "rvcp_taa_upsample_async",
                  "rvcp_taau_wait", "rvcp_set_taa_upsample", "rvcp_get_taa_upsample",
-                 "rvcp_set_sampling", "rvcp_get_sampling", "rvcp_render_spp_map_async",
+                 "rvcp_set_sampling", "rvcp_get_sampling", "rvcp_set_materials",
+                 "rvcp_get_materials", "rvcp_render_spp_map_async",
                  "rvcp_adaptive_params_default", "rvcp_spp_plan_async", "rvcp_spp_plan_wait",
                  "rvcp_set_adaptive", "rvcp_get_adaptive", "rvcp_adaptive_last_map",
                  "rvcp_trace_rays_async", "rvcp_rays_wait", "rvcp_trace_rays",

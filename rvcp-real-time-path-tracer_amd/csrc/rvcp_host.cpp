@@ -283,6 +283,16 @@ struct rvcp_ctx {
     size_t cap_p_rays = 0, cap_p_seeds = 0, cap_p_out = 0;
     unsigned long long *d_p_counters = nullptr;
 
+    // material scattering (rvcp_set_materials): the mode, the scene's materials
+    // as uploaded (the mode's validation reads fuzz and refraction_ratio when it is switched on
+    // after an upload) and the frame route's primary rays and seeds
+    int32_t materials = RVCP_MATERIALS_LAMBERTIAN;
+    std::vector<rvcp_material_t> h_rawmats;
+    void *d_ms_rays = nullptr, *d_ms_seeds = nullptr;
+    size_t cap_ms_rays = 0, cap_ms_seeds = 0;
+    bool last_scatter = false;      // the last render took that route: its kernel counts every
+                                    // traversal, the kept first hit's included
+
     // albedo demodulation (rvcp_demodulate_async / rvcp_remodulate_async): the
     // scene's albedo table (one float4 per material, made by every upload) and the switch of
     // rvcp_set_demodulation: while it is set rvcp_render_denoised, rvcp_render_temporal and
@@ -953,6 +963,8 @@ static int impl_destroy(rvcp_ctx_t *ctx)
     free_svgf_state(ctx);
     (void)hipFree(ctx->d_q_rays);
     (void)hipFree(ctx->d_q_out);
+    (void)hipFree(ctx->d_ms_rays);
+    (void)hipFree(ctx->d_ms_seeds);
     (void)hipFree(ctx->d_p_rays);
     (void)hipFree(ctx->d_p_seeds);
     (void)hipFree(ctx->d_p_out);
@@ -1010,6 +1022,28 @@ static int impl_upload_scene(rvcp_ctx_t *ctx, const rvcp_material_t *materials, 
     return rc;
 }
 
+// What RVCP_MATERIALS_SCATTER asks of a scene's materials: a finite fuzz in
+// [0, 1] for every Metal (the reference asserts fuzz <= 1, material.rs:52) and a finite
+// refraction_ratio > 0 for every Dielectric; `why` names the first material that breaks it.
+static bool scatter_materials_ok(const rvcp_material_t *materials, uint32_t n_materials,
+                                 std::string &why)
+{
+    for (uint32_t i = 0; i < n_materials; i++) {
+        const rvcp_material_t &m = materials[i];
+        if (m.ty == 1u && !(m.fuzz >= 0.0f && m.fuzz <= 1.0f)) {
+            why = "RVCP_MATERIALS_SCATTER: material " + std::to_string(i) +
+                  " (Metal) needs a finite fuzz in [0, 1]";
+            return false;
+        }
+        if (m.ty == 2u && !(m.refraction_ratio > 0.0f && std::isfinite(m.refraction_ratio))) {
+            why = "RVCP_MATERIALS_SCATTER: material " + std::to_string(i) +
+                  " (Dielectric) needs a finite refraction_ratio > 0";
+            return false;
+        }
+    }
+    return true;
+}
+
 static int upload_one(rvcp_ctx_t *ctx, const rvcp_material_t *materials, uint32_t n_materials,
                       const rvcp_vertex_t *vertices, uint32_t n_vertices,
                       const rvcp_face_t *faces, uint32_t n_faces,
@@ -1030,6 +1064,9 @@ static int upload_one(rvcp_ctx_t *ctx, const rvcp_material_t *materials, uint32_
     SceneTables tab;
     std::string err;
     if (prepare_scene(in, ctx->cfg.lum_id_std140_quirk != 0, tab, err) != RVCP_OK)
+        return fail(ctx, RVCP_E_INVALID, err);
+    if (ctx->materials == RVCP_MATERIALS_SCATTER &&
+        !scatter_materials_ok(materials, n_materials, err))
         return fail(ctx, RVCP_E_INVALID, err);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const std::vector<TriRecord> &tri = tab.tri;
@@ -1170,6 +1207,7 @@ static int upload_one(rvcp_ctx_t *ctx, const rvcp_material_t *materials, uint32_
         if (tab.lights[i].face != tab.lights[0].face) ctx->lights_same = false;
     ctx->light_total = total;
     ctx->light_pdf = 1.0f / total;
+    ctx->h_rawmats.assign(materials, materials + n_materials);
     ctx->has_scene = true;
     return RVCP_OK;
 }
@@ -1291,6 +1329,68 @@ static void shading_frame_args(const rvcp_ctx_t *ctx, FrameArgs &A)
     A.cos_k = 3.1415926f / A.rr;        // the cosine-weighted bounce's factor k = PI_F / rr
 }
 
+// kernel_variant of a frame rendered with material scattering (rvcp.h)
+constexpr int32_t kScatterStatsCode = 11;
+
+// One whole frame with material scattering (rvcp_set_materials), the composition
+// §4.20 proves equal to a frame: the frame's primary rays and seeds into buffers of the context,
+// path_scatter_kernel over them into the linear frame, the tone map into RGBA8.  render_frames
+// has checked the arguments; the statistics are the render's (d_counters, ev0 / evm / ev1).
+static int render_scatter(rvcp_ctx_t *ctx, const rvcp_push_constant_t &push, uint32_t width,
+                          uint32_t height, void *d_rgba8, void *d_linear_rgb, hipStream_t s)
+{
+    const uint32_t n = width * height;
+    int rc;
+    if ((rc = grow(ctx, &ctx->d_ms_rays, &ctx->cap_ms_rays, n, sizeof(rvcp_ray_t))) != RVCP_OK) return rc;
+    if ((rc = grow(ctx, &ctx->d_ms_seeds, &ctx->cap_ms_seeds, n, sizeof(float))) != RVCP_OK) return rc;
+    float *lin = (float *)d_linear_rgb;
+    if (!lin) {
+        if ((rc = grow(ctx, (void **)&ctx->d_acc, &ctx->cap_acc, n, 12)) != RVCP_OK) return rc;
+        lin = ctx->d_acc;
+    }
+    FrameArgs A;
+    std::memset(&A, 0, sizeof(A));
+    primary_frame_args(ctx, push, width, height, A);
+    A.shard_index = 0;
+    A.shard_count = 1;
+    A.n_pixels = n;
+    A.spp = ctx->cfg.spp;
+    shading_frame_args(ctx, A);
+    A.n_mats = ctx->n_mats;
+    A.n_simds = ctx->n_simds;
+    ctx->last_timeline_waves = 0;
+    // a gather of this context's previous frame may still read the caller's buffer
+    if (ctx->gather_on_gstream) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->evg1, 0));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, kCounterWords * sizeof(unsigned long long), s));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
+    int launch_rc = rvcp_launch_primary_rays(&A, 0, n, ctx->d_ms_rays, s);
+    if (launch_rc == 0) launch_rc = rvcp_launch_primary_seeds(&A, n, ctx->d_ms_seeds, s);
+    HIP_TRY(ctx, hipEventRecord(ctx->evm, s));
+    if (launch_rc == 0)
+        launch_rc = rvcp_launch_path_scatter(&A, ctx->d_tri, ctx->d_shade, ctx->d_mats,
+                                             ctx->d_rawmats, ctx->d_lights, ctx->d_bvh_nodes,
+                                             ctx->d_bvh_tris, ctx->d_ms_rays, ctx->d_ms_seeds, lin,
+                                             ctx->d_counters, ctx->cfg.grid_waves_per_simd, s);
+    if (launch_rc == 0)
+        launch_rc = rvcp_launch_tonemap(lin, n, ctx->d_gamma, (uint32_t *)d_rgba8, s);
+    if (launch_rc != 0) return fail(ctx, RVCP_E_HIP, std::string("kernel launch failed: ") +
+                                                         hipGetErrorString(hipGetLastError()));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, s));
+    ctx->pending = true;
+    ctx->render_stream = s;
+    ctx->last_trivial = false;
+    ctx->last_scatter = true;
+    ctx->last_variant = kScatterStatsCode;
+    ctx->last_pixels = n;
+    ctx->last_spp = A.spp;
+    ctx->last_map = false;
+    ctx->last_shard_index = 0;
+    ctx->last_shard_count = 1;
+    ctx->last_width = width;
+    ctx->last_height = height;
+    return RVCP_OK;
+}
+
 // n_frames consecutive frames of one shard (pushes[k] for frame k) into outputs laid out frame
 // after frame, `slot` = the largest shard's rows apart (rvcp_render_frames_async); n_frames = 1
 // is rvcp_render_shard_async.  d_spp_map (rvcp_render_spp_map_async; one whole frame): the
@@ -1323,8 +1423,22 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
     // one frame in flight per context: its surface list, counters and events are the frame's
     if (ctx->pending)
         return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    // material scattering (rvcp_set_materials) renders one whole frame
+    if (ctx->materials == RVCP_MATERIALS_SCATTER) {
+        if (map)
+            return fail(ctx, RVCP_E_UNSUPPORTED, "RVCP_MATERIALS_SCATTER renders no per-pixel "
+                        "sample count (rvcp_render_spp_map_async, the adaptive switch)");
+        if (n_frames > 1)
+            return fail(ctx, RVCP_E_UNSUPPORTED, "RVCP_MATERIALS_SCATTER renders no frame batch "
+                        "(n_frames must be 1)");
+        if (shard_count > 1)
+            return fail(ctx, RVCP_E_UNSUPPORTED, "RVCP_MATERIALS_SCATTER renders whole frames "
+                        "(shard_count must be 1)");
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if (ctx->materials == RVCP_MATERIALS_SCATTER)
+        return render_scatter(ctx, *push, width, height, d_rgba8, d_linear_rgb, s);
 
     // the cosine-weighted bounce (rvcp_set_sampling): its kernels, and a
     // specialised module compiled for it
@@ -1484,6 +1598,7 @@ static int render_frames(rvcp_ctx_t *ctx, const rvcp_push_constant_t *pushes, ui
     ctx->pending = true;
     ctx->render_stream = s;
     ctx->last_trivial = P.trivial;
+    ctx->last_scatter = false;
     ctx->last_variant = P.stats_code;
     ctx->last_pixels = (uint64_t)frame_px * n_frames;       // stats cover the whole batch
     ctx->last_spp = A.spp;
@@ -1572,6 +1687,13 @@ static int impl_sync_stats(rvcp_ctx_t *ctx, rvcp_stats_t *stats)
         stats->traversals_executed = c[0];
         // the reference re-traces the (RNG-independent) primary ray in every sample
         stats->traversals = ctx->last_trivial ? 0 : c[0] + ctx->last_pixels * (ctx->last_spp - 1);
+        if (ctx->last_scatter) {
+            // its kernel counts as the shader does, the kept first hit once per sample (no
+            // traversal at all in a frame whose configuration ends every sample at once)
+            const uint64_t reused = ctx->last_pixels * (ctx->last_spp - 1);
+            stats->traversals = c[0];
+            stats->traversals_executed = c[0] >= reused ? c[0] - reused : 0;
+        }
         stats->samples = ctx->last_pixels * ctx->last_spp;
         if (ctx->last_map) {
             // a map render: the pre-pass's sum of the clamped counts (0 for a trivial frame, whose
@@ -2174,9 +2296,15 @@ static int trace_paths_enqueue(rvcp_ctx_t *ctx, const void *d_rays, const void *
     unsigned long long *counters = path_counters(ctx, id);
     if ((rc = stage_begin(ctx, id, s)) != RVCP_OK) return rc;
     HIP_TRY(ctx, hipMemsetAsync(counters, 0, kPathCounterWords * sizeof(unsigned long long), s));
-    if (rvcp_launch_path_query(&A, ctx->d_tri, ctx->d_shade, ctx->d_mats, ctx->d_lights,
-                               ctx->d_bvh_nodes, ctx->d_bvh_tris, d_rays, d_seeds, d_out, counters,
-                               ctx->cfg.grid_waves_per_simd, path_query_static_lanes(), s) != 0)
+    // with material scattering (rvcp_set_materials, §4.21) its kernel, whatever the scene holds
+    const int launch_rc = ctx->materials == RVCP_MATERIALS_SCATTER
+        ? rvcp_launch_path_scatter(&A, ctx->d_tri, ctx->d_shade, ctx->d_mats, ctx->d_rawmats,
+                                   ctx->d_lights, ctx->d_bvh_nodes, ctx->d_bvh_tris, d_rays,
+                                   d_seeds, d_out, counters, ctx->cfg.grid_waves_per_simd, s)
+        : rvcp_launch_path_query(&A, ctx->d_tri, ctx->d_shade, ctx->d_mats, ctx->d_lights,
+                                 ctx->d_bvh_nodes, ctx->d_bvh_tris, d_rays, d_seeds, d_out, counters,
+                                 ctx->cfg.grid_waves_per_simd, path_query_static_lanes(), s);
+    if (launch_rc != 0)
         return fail(ctx, RVCP_E_HIP, std::string("path query launch failed: ") +
                                          hipGetErrorString(hipGetLastError()));
     return stage_end(ctx, id, s);
@@ -2515,6 +2643,14 @@ static int impl_get_taa(rvcp_ctx_t *ctx, int *on)
 
 // ---- bounce sampling: the switch -------------------------------------------
 
+// the temporal, SVGF, TAA and upsampling histories, dropped when the frames' integrand changes
+static void drop_chain_histories(rvcp_ctx_t *ctx)
+{
+    ctx->tp_hist.valid = ctx->sv_hist.valid = false;
+    ctx->taa_tp.hist.valid = ctx->taa_sv.hist.valid = false;
+    ctx->taau_tp.hist.valid = ctx->taau_sv.hist.valid = false;
+}
+
 static int impl_set_sampling(rvcp_ctx_t *ctx, int32_t sampling)
 {
     if (!ctx) return RVCP_E_INVALID;
@@ -2528,13 +2664,52 @@ static int impl_set_sampling(rvcp_ctx_t *ctx, int32_t sampling)
     for (rvcp_ctx *sub : ctx->subs)
         if (sub->pending)
             return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    if (sampling == RVCP_SAMPLING_COSINE && ctx->materials == RVCP_MATERIALS_SCATTER)
+        return fail(ctx, RVCP_E_UNSUPPORTED, "RVCP_SAMPLING_COSINE is not implemented with "
+                    "RVCP_MATERIALS_SCATTER (its kernel holds the uniform bounce only)");
     if (sampling == ctx->sampling) return RVCP_OK;
     ctx->sampling = sampling;
     for (rvcp_ctx *sub : ctx->subs) sub->sampling = sampling;
     // histories of frames with another expectation and another noise do not mix
-    ctx->tp_hist.valid = ctx->sv_hist.valid = false;
-    ctx->taa_tp.hist.valid = ctx->taa_sv.hist.valid = false;
-    ctx->taau_tp.hist.valid = ctx->taau_sv.hist.valid = false;
+    drop_chain_histories(ctx);
+    return RVCP_OK;
+}
+
+// ---- material scattering: the switch ----------------------------------------
+
+static int impl_set_materials(rvcp_ctx_t *ctx, int32_t materials)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (materials != RVCP_MATERIALS_LAMBERTIAN && materials != RVCP_MATERIALS_SCATTER)
+        return fail(ctx, RVCP_E_INVALID, "unknown materials mode");
+    if (materials == RVCP_MATERIALS_SCATTER) {
+        if (ctx->cfg.integrator == RVCP_INTEGRATOR_LEGACY)
+            return fail(ctx, RVCP_E_UNSUPPORTED, "RVCP_MATERIALS_SCATTER is for the games101 "
+                        "integrator (mode 2 scatters by material already)");
+        if (!ctx->subs.empty())
+            return fail(ctx, RVCP_E_UNSUPPORTED, "RVCP_MATERIALS_SCATTER drives one GPU (n_gpus = 1)");
+        if (ctx->sampling == RVCP_SAMPLING_COSINE)
+            return fail(ctx, RVCP_E_UNSUPPORTED, "RVCP_MATERIALS_SCATTER is not implemented with "
+                        "RVCP_SAMPLING_COSINE (its kernel holds the uniform bounce only)");
+    }
+    if (ctx->pending)
+        return fail(ctx, RVCP_E_INVALID, "a frame is in flight on this context (rvcp_wait first)");
+    if (materials == ctx->materials) return RVCP_OK;
+    std::string why;
+    if (materials == RVCP_MATERIALS_SCATTER && ctx->has_scene &&
+        !scatter_materials_ok(ctx->h_rawmats.data(), (uint32_t)ctx->h_rawmats.size(), why))
+        return fail(ctx, RVCP_E_INVALID, why);
+    ctx->materials = materials;
+    // histories of frames of another integrand do not mix
+    drop_chain_histories(ctx);
+    return RVCP_OK;
+}
+
+static int impl_get_materials(rvcp_ctx_t *ctx, int32_t *materials)
+{
+    if (!ctx) return RVCP_E_INVALID;
+    if (!materials) return fail(ctx, RVCP_E_INVALID, "invalid get_materials arguments");
+    *materials = ctx->materials;
     return RVCP_OK;
 }
 
@@ -4283,6 +4458,16 @@ int rvcp_set_sampling(rvcp_ctx_t *ctx, int32_t sampling)
 int rvcp_get_sampling(rvcp_ctx_t *ctx, int32_t *sampling)
 {
     return barrier(ctx, [&] { return impl_get_sampling(ctx, sampling); });
+}
+
+int rvcp_set_materials(rvcp_ctx_t *ctx, int32_t materials)
+{
+    return barrier(ctx, [&] { return impl_set_materials(ctx, materials); });
+}
+
+int rvcp_get_materials(rvcp_ctx_t *ctx, int32_t *materials)
+{
+    return barrier(ctx, [&] { return impl_get_materials(ctx, materials); });
 }
 
 int rvcp_render_spp_map_async(rvcp_ctx_t *ctx, const rvcp_push_constant_t *push, uint32_t width,

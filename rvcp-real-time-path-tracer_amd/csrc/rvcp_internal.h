@@ -442,6 +442,15 @@ int rvcp_launch_path_query(const rvcp::FrameArgs *args, const rvcp::TriRecord *t
                            const rvcp::TriRecord *bvh_tris, const void *rays, const void *seeds,
                            void *out, unsigned long long *counters, uint32_t grid_waves_per_simd,
                            int static_lanes, void *stream);
+// The same query with material scattering (rvcp_set_materials): the queue form
+// only; raw_materials is the scene's rvcp_material_t array as uploaded (fuzz, refraction_ratio).
+int rvcp_launch_path_scatter(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
+                             const rvcp::FaceShade *shade, const rvcp::MatRecord *mats,
+                             const void *raw_materials, const rvcp::LightRecord *lights,
+                             const rvcp::Bvh4Node *bvh_nodes, const rvcp::TriRecord *bvh_tris,
+                             const void *rays, const void *seeds, void *out,
+                             unsigned long long *counters, uint32_t grid_waves_per_simd,
+                             void *stream);
 // The seeds of the first `count` pixels of args' frame, one float each (rvcp_primary_seeds_async)
 int rvcp_launch_primary_seeds(const rvcp::FrameArgs *args, uint32_t count, void *out, void *stream);
 // tonemap_kernel alone (the denoiser's RGBA8 store)

@@ -3768,6 +3768,305 @@ __global__ __launch_bounds__(kBlock, RVCP_LEGACY_MIN_WAVES) void legacy_kernel(
     legacy_body(A, tri, shade, sph, mats, unorm_t, out_rgba, out_lin, counters, coop_tab,
                 start_slots);
 }
+
+// ======================================================================================
+// Material scattering on meshes (rvcp_set_materials RVCP_MATERIALS_SCATTER):
+// ray_trace_games101 (:406-482) in which a hit on a Metal or Dielectric face draws no light
+// sample and traces no shadow ray, but takes the roulette (:462) and then material_scatter's
+// direction and colour for its type (ray_tracer.comp:515-581, mode 2's arithmetic above), with
+// attenuation *= na / RR_PROBABILITY and games101's ray offset; a light reached from such a
+// vertex counts (the vertex sampled none), one reached from a Lambertian vertex still does not.
+// The metal redraw is bounded: after kMetalRetries rejected draws the direction is the unfuzzed
+// flipped reflection, normalised.  tests/materials_ref.py is the contract.
+//
+// path_query_kernel's machine (§4.20) -- the queue, the kept first hit, rays and seeds from
+// buffers, its rejections, bvh_query<true, false> on an LDS column -- with one more transition:
+// a specular surface goes from A_SURF to the roulette and the scatter in the same settle pass
+// and so costs no trace iteration for the shadow ray it does not have.  The metal draws of a
+// wave share coop_unit_sphere's rounds.  Per lane, beside the query kernel's state: one word of
+// flags (the surface's and the kept first hit's `outward` bit and material class, and whether
+// the previous vertex was specular); the incoming direction at a scatter is still in rd (a
+// specular surface is settled before anything overwrites it), and a later sample of a ray whose
+// kept first hit is specular reads the ray's direction again from its record.  `raw` is the
+// scene's materials as uploaded (fuzz, refraction_ratio).
+//
+// The machine is a copy of path_query_kernel's body, not a shared template with a SCATTER
+// parameter, on purpose: the existing kernels are held to their instructions (`make isa` on
+// parent and branch, §4.21), and the copy is what makes that hold by construction.  Keep the two
+// in step: the queue, the settle order (A_RR, A_END, A_SURF, take), the rejections, the trace and
+// the Lambertian post-trace shading are path_query_kernel's line for line.
+// ======================================================================================
+namespace {
+constexpr uint32_t kMetalRetries = 16;
+// flags: the current surface's bits, and the kept first hit's kScatKeep bits higher
+constexpr uint32_t kScatOut = 1u, kScatMetal = 2u, kScatGlass = 4u, kScatSurf = 7u;
+constexpr uint32_t kScatKeep = 4u;          // shift of the kept first hit's copy of kScatSurf
+constexpr uint32_t kScatSpec = 1u << 8;     // the previous vertex was specular
+
+// hit_shade with the record's `outward` flag (:268-277): true when the interpolated normal
+// already faced the ray.  Returned as the surface bits of `flags`.
+__device__ __forceinline__ uint32_t hit_scatter(const TriRecord *__restrict__ tri,
+                                                const FaceShade *__restrict__ shade, int best,
+                                                f3 o, f3 d, float t, f3 &pos, f3 &n,
+                                                FaceShade &fs) {
+    const TriRecord T = tri[best];
+    fs = shade[best];
+    const f3 s = mk(o.x - T.v0[0], o.y - T.v0[1], o.z - T.v0[2]);
+    const f3 e1 = ld3(T.e1), e2 = ld3(T.e2);
+    const f3 s1 = cross(d, e2);
+    const f3 s2 = cross(s, e1);
+    const float f = rcp_ieee(dot(s1, e1));
+    const float b1 = f * dot(s1, s);
+    const float b2 = f * dot(s2, d);
+    n = normalize(add(add(muls(ld3(fs.n0), 1.0f - b1 - b2), muls(ld3(fs.n1), b1)),
+                      muls(ld3(fs.n2), b2)));
+    const bool inward = dot(n, d) > 0.0f;
+    if (inward) n = neg(n);
+    pos = add(o, muls(d, t));
+    return (inward ? 0u : kScatOut) | (fs.ty == 1u ? kScatMetal : 0u) |
+           (fs.ty == 2u ? kScatGlass : 0u);
+}
+}  // namespace
+
+template <bool BVH>
+__global__ __launch_bounds__(kBlock) void path_scatter_kernel(
+    FrameArgs A, const TriRecord *__restrict__ tri, const FaceShade *__restrict__ shade,
+    const MatRecord *__restrict__ mats, const rvcp_material_t *__restrict__ raw,
+    const LightRecord *__restrict__ lights, const Bvh4Node *__restrict__ bvh_nodes,
+    const TriRecord *__restrict__ bvh_tris, const float4 *__restrict__ rays,
+    const float *__restrict__ seeds, float *__restrict__ out,
+    unsigned long long *__restrict__ counters)
+{
+    __shared__ int32_t stack[BVH ? kBvhStack * kBlock : 1];
+    __shared__ uint8_t coop_tab[kBlock / kWave][kWave];
+    uint8_t *tab = coop_tab[threadIdx.x / kWave];
+    const uint32_t lane = lane_id();
+    Queue q = queue_init(A);
+    const float sppf = (float)A.spp;
+    const float inv_spp = rcp_ieee(sppf);     // divs_y's shared reciprocal
+    const bool trivial = A.max_bounces == 0 || 1.0f < A.att_stop;
+
+    int action = A_NEED, kind = K_PRIMARY;
+    uint32_t ray = 0, k = 0, depth = 0, trav = 0, iters = 0, flags = 0;
+    float seed = 0.0f, ridx = 0.0f;
+    f3 acc = mk(0, 0, 0), att = mk(1, 1, 1), col = mk(0, 0, 0);
+    f3 P_pos = mk(0, 0, 0), P_nrm = mk(0, 0, 0);   // the kept first hit (surface)
+    uint32_t P_mat = 0;
+    f3 S_pos = mk(0, 0, 0), S_nrm = mk(0, 0, 0);   // current shading point
+    uint32_t S_mat = 0;
+    f3 nee_C = mk(0, 0, 0);
+    float nee_dist = 0.0f;
+    f3 ro = mk(0, 0, 0), rd = mk(0, 0, 1);
+    float rtmin = 0.0f, rtmax = 0.0f;
+
+    for (;;) {
+        // ============ settle: advance every lane until it has a ray or is done ============
+        for (;;) {
+            if (action == A_RR) {                                   // :461-478
+                f3 wi;
+                if (!brdf_continue(A, mats[S_mat], S_nrm, seed, ridx, att, wi)) {
+                    action = A_END;
+                } else {
+                    depth += 1;
+                    ro = add(S_pos, muls(wi, A.eps));
+                    rd = wi;
+                    rtmin = A.t_min;
+                    rtmax = A.t_max;
+                    kind = K_PATH;
+                    action = (depth >= A.max_bounces || att_stop(A, att)) ? A_END : A_TRACE;
+                }
+            }
+            if (action == A_END) {                                  // color += L / SPP (:495)
+                acc = add(acc, divs_y(col, sppf, inv_spp));
+                k += 1;
+                if (k >= A.spp) {
+                    store_acc(ray, acc, out);
+                    action = A_NEED;
+                } else {
+                    trav += 1;                                      // the kept first hit, again
+                    depth = 0;
+                    att = mk(1, 1, 1);
+                    col = mk(0, 0, 0);
+                    S_pos = P_pos;
+                    S_nrm = P_nrm;
+                    S_mat = P_mat;
+                    flags = (flags & (kScatSurf << kScatKeep)) | ((flags >> kScatKeep) & kScatSurf);
+                    if (flags & (kScatMetal | kScatGlass)) {        // the scatter's incoming direction
+                        const float4 r0 = rays[2 * (size_t)ray], r1 = rays[2 * (size_t)ray + 1];
+                        rd = mk(r0.w, r1.x, r1.y);
+                    }
+                    action = A_SURF;
+                }
+            }
+            const bool specular = action == A_SURF && (flags & (kScatMetal | kScatGlass)) != 0u;
+            if (action == A_SURF && !specular) {                    // :431-447
+                f3 ws;
+                flags &= ~kScatSpec;
+                if (!nee_sample(A, lights, ld3(mats[S_mat].alb_pi), S_pos, S_nrm, att, seed, ridx,
+                                nee_C, nee_dist, ws)) {
+                    action = A_RR;
+                } else {
+                    ro = add(S_pos, muls(ws, A.eps));
+                    rd = ws;
+                    rtmin = A.t_min;
+                    rtmax = A.t_max;
+                    kind = K_SHADOW;
+                    action = A_TRACE;
+                }
+            }
+            if (__any(specular)) {
+                // the roulette (:462), then material_scatter (ray_tracer.comp:515-581) for rd at
+                // S_pos / S_nrm: wave-uniform control flow around the cooperative draws
+                const bool go = specular && !(rnd(seed, ridx) > A.rr);
+                if (specular && !go) action = A_END;
+                const bool metal = go && (flags & kScatMetal) != 0u;
+                const bool glass = go && !metal;
+                f3 na = mk(1, 1, 1), dir = mk(0, 0, 0), refl = mk(0, 0, 0);
+                float fuzz = 0.0f;
+                if (metal) {                                        // :526-527
+                    const rvcp_material_t &M = raw[S_mat];
+                    na = ld3(M.albedo);
+                    fuzz = M.fuzz;
+                    refl = reflect_glsl(rd, S_nrm);
+                    if (dot(refl, S_nrm) < 0.0f) refl = neg(refl);
+                }
+                bool pend = metal;
+                uint32_t tries = 0;
+                while (__any(pend)) {                               // :528-530, bounded
+                    f3 p = mk(0, 0, 0);
+                    coop_unit_sphere(pend, seed, ridx, p, lane, tab);
+                    if (pend) {
+                        dir = normalize(add(refl, muls(normalize(p), fuzz)));
+                        tries += 1;
+                        pend = dot(dir, S_nrm) < 0.0f;
+                        if (pend && tries >= kMetalRetries) {
+                            dir = normalize(refl);
+                            pend = false;
+                        }
+                    }
+                }
+                if (glass) {                                        // :553-581
+                    const float ior = raw[S_mat].refraction_ratio;
+                    const float ratio = (flags & kScatOut) ? (1.0f / ior) : ior;
+                    const float cos_t = dot(neg(rd), S_nrm);
+                    const float sin_t = sqrt_c(1.0f - cos_t * cos_t);
+                    bool refracted = ratio * sin_t <= 1.0f;
+                    if (refracted) refracted = rnd(seed, ridx) >= fresnel_schlick(cos_t, ratio);
+                    dir = refracted ? refract_glsl(rd, S_nrm, ratio) : reflect_glsl(rd, S_nrm);
+                }
+                if (go) {
+                    att = mulv(att, divs_pos(na, A.rr));
+                    flags |= kScatSpec;
+                    depth += 1;
+                    ro = add(S_pos, muls(dir, A.eps));
+                    rd = dir;
+                    rtmin = A.t_min;
+                    rtmax = A.t_max;
+                    kind = K_PATH;
+                    action = (depth >= A.max_bounces || att_stop(A, att)) ? A_END : A_TRACE;
+                }
+            }
+            {   // take new rays from the queue (wave-uniform control flow)
+                bool got;
+                uint32_t nr = ray;
+                queue_take(q, __ballot(action == A_NEED), lane, A, counters, got, nr);
+                if (got) {
+                    ray = nr;
+                    const float4 r0 = rays[2 * (size_t)ray], r1 = rays[2 * (size_t)ray + 1];
+                    seed = seeds[ray];
+                    if (ray_words_finite(r0, r1) && seed >= 0.0f && seed < 1.0f && !trivial) {
+                        ro = mk(r0.x, r0.y, r0.z);
+                        rd = mk(r0.w, r1.x, r1.y);
+                        rtmin = r1.z;
+                        rtmax = r1.w;
+                        ridx = 0.0f;
+                        kind = K_PRIMARY;
+                        k = 0;
+                        acc = mk(0, 0, 0);
+                        action = A_TRACE;
+                    } else {
+                        store_acc(ray, mk(0, 0, 0), out);           // (stays A_NEED)
+                    }
+                }
+            }
+            if (q.exhausted && action == A_NEED) action = A_DONE;
+            if (!__any(action == A_RR || action == A_END || action == A_SURF || action == A_NEED))
+                break;
+        }
+        if (!__any(action == A_TRACE)) break;
+        iters += 1;
+
+        // ============ trace: nearest hit (:283-298) ============
+        int best = -1;
+        float bt = rtmax;
+        if (action == A_TRACE) {
+            trav += 1;
+            const uint32_t n_scan = BVH ? A.bvh_prefix : A.n_faces;
+            for (uint32_t i = 0; i < n_scan; ++i) {
+                float t;
+                if (tri_accept(tri[i], ro, rd, rtmin, bt, t)) { bt = t; best = (int)i; }
+            }
+            if (BVH)
+                bvh_query<true, false>(bvh_nodes, bvh_tris, A.bvh_root,
+                                       (lds_i32 *)stack + threadIdx.x, ro, rd, rtmin, bt, best,
+                                       A.bvh_n4, A.bvh_slots);
+        }
+
+        // ============ post-trace shading ============
+        if (action == A_TRACE) {
+            if (kind == K_SHADOW) {                                 // :447-459
+                const f3 hp = best >= 0 ? add(ro, muls(rd, bt))
+                                        : mk(__builtin_inff(), __builtin_inff(), __builtin_inff());
+                const float dist_blocked = len(sub(hp, S_pos));
+                if (__builtin_fabsf(nee_dist - dist_blocked) < A.eps) col = add(col, nee_C);
+                action = A_RR;
+            } else {
+                f3 hpos = mk(0, 0, 0), hn = mk(0, 0, 0);
+                FaceShade fs;
+                fs.mat = 0;
+                fs.ty = 0;
+                uint32_t hbits = 0;
+                if (best >= 0) hbits = hit_scatter(tri, shade, best, ro, rd, bt, hpos, hn, fs);
+                const bool miss = best < 0;
+                const bool is_light = !miss && fs.ty == kLight;
+                if (kind == K_PRIMARY) {
+                    if (miss || is_light) {
+                        // every sample returns the same L without touching the RNG:
+                        // miss -> 0.1 (:424), light at depth 0 -> Le (:425-427)
+                        const f3 L = miss ? mk(0.1f, 0.1f, 0.1f) : ld3(mats[fs.mat].albedo);
+                        const f3 Ls = divs(L, sppf);
+                        for (uint32_t i = 0; i < A.spp; ++i) acc = add(acc, Ls);
+                        trav += A.spp - 1;
+                        store_acc(ray, acc, out);
+                        action = A_NEED;
+                    } else {
+                        P_pos = hpos; P_nrm = hn; P_mat = fs.mat;
+                        S_pos = hpos; S_nrm = hn; S_mat = fs.mat;
+                        flags = hbits | (hbits << kScatKeep);
+                        depth = 0;
+                        att = mk(1, 1, 1);
+                        col = mk(0, 0, 0);
+                        action = A_SURF;
+                    }
+                } else {                                            // K_PATH
+                    if (miss) {
+                        col = add(col, mk(0.1f, 0.1f, 0.1f));
+                        action = A_END;
+                    } else if (is_light) {
+                        // :426 with rule 2: the light counts behind a specular vertex
+                        if (flags & kScatSpec) col = add(col, mulv(att, ld3(mats[fs.mat].albedo)));
+                        action = A_END;
+                    } else {
+                        S_pos = hpos; S_nrm = hn; S_mat = fs.mat;
+                        flags = (flags & ~kScatSurf) | hbits;
+                        action = A_SURF;
+                    }
+                }
+            }
+        }
+    }
+    flush_counters(counters, lane, trav, iters);
+}
 #else
 // mode 2 with the scene-specialised triangle scan (rvcp_jit.cpp, RVCP_JIT_LEGACY)
 #ifndef RVCP_LEGACY_MIN_WAVES
@@ -4076,32 +4375,29 @@ extern "C" int rvcp_launch_primary_rays(const rvcp::FrameArgs *args, uint32_t fi
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-extern "C" int rvcp_launch_path_query(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
-                                      const rvcp::FaceShade *shade, const rvcp::MatRecord *mats,
-                                      const rvcp::LightRecord *lights,
-                                      const rvcp::Bvh4Node *bvh_nodes,
-                                      const rvcp::TriRecord *bvh_tris, const void *rays,
-                                      const void *seeds, void *out, unsigned long long *counters,
-                                      uint32_t grid_waves_per_simd, int static_lanes,
-                                      void *stream)
+// The persistent grid of a path query's kernel (path_query_kernel, path_scatter_kernel) and the
+// queue members of its arguments: A = *args with them filled in; false when the occupancy query
+// fails.
+template <class Kernel>
+static bool path_query_grid(Kernel kern, const rvcp::FrameArgs *args, uint32_t grid_waves_per_simd,
+                            int static_lanes, rvcp::FrameArgs &A, uint32_t &blocks)
 {
-    auto kern = args->accel ? rvcp::path_query_kernel<true> : rvcp::path_query_kernel<false>;
     // a persistent grid: at most what is resident, and the queue's static split over it, as the
     // frame plan's for the render kernels (plan_frame)
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, rvcp::kBlock, 0) != hipSuccess ||
         per_cu < 1)
-        return -2;
+        return false;
     const uint32_t wpb = rvcp::kBlock / rvcp::kWave;
     uint32_t cap = (uint32_t)per_cu * (args->n_simds / 4u);
     if (grid_waves_per_simd > 0) {        // the caller's grid (rvcp_config_t::grid_waves_per_simd)
         const uint64_t lim = (uint64_t)grid_waves_per_simd * args->n_simds / wpb;
         if (lim < cap) cap = lim > 0 ? (uint32_t)lim : 1u;
     }
-    rvcp::FrameArgs A = *args;
+    A = *args;
     uint32_t waves = 0, chunk = 0;
     rvcp::static_split(A.n_pixels, cap * wpb, A.n_simds, waves, chunk);
-    uint32_t blocks = (waves + wpb - 1) / wpb;
+    blocks = (waves + wpb - 1) / wpb;
     if (blocks > cap) blocks = cap;
     if (blocks == 0) blocks = 1;
     A.static_chunk = chunk;
@@ -4116,9 +4412,43 @@ extern "C" int rvcp_launch_path_query(const rvcp::FrameArgs *args, const rvcp::T
     A.dyn_chunk = rvcp::kDynChunk;
     A.chunk_min = rvcp::kMinChunk;
     A.chunk_window = rvcp::kChunkWindow;
+    return true;
+}
+
+extern "C" int rvcp_launch_path_query(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
+                                      const rvcp::FaceShade *shade, const rvcp::MatRecord *mats,
+                                      const rvcp::LightRecord *lights,
+                                      const rvcp::Bvh4Node *bvh_nodes,
+                                      const rvcp::TriRecord *bvh_tris, const void *rays,
+                                      const void *seeds, void *out, unsigned long long *counters,
+                                      uint32_t grid_waves_per_simd, int static_lanes,
+                                      void *stream)
+{
+    auto kern = args->accel ? rvcp::path_query_kernel<true> : rvcp::path_query_kernel<false>;
+    rvcp::FrameArgs A;
+    uint32_t blocks = 0;
+    if (!path_query_grid(kern, args, grid_waves_per_simd, static_lanes, A, blocks)) return -2;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(rvcp::kBlock), 0, (hipStream_t)stream, A, tri, shade,
                        mats, lights, bvh_nodes, bvh_tris, (const float4 *)rays, (const float *)seeds,
                        (float *)out, counters);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int rvcp_launch_path_scatter(const rvcp::FrameArgs *args, const rvcp::TriRecord *tri,
+                                        const rvcp::FaceShade *shade, const rvcp::MatRecord *mats,
+                                        const void *raw_materials, const rvcp::LightRecord *lights,
+                                        const rvcp::Bvh4Node *bvh_nodes,
+                                        const rvcp::TriRecord *bvh_tris, const void *rays,
+                                        const void *seeds, void *out, unsigned long long *counters,
+                                        uint32_t grid_waves_per_simd, void *stream)
+{
+    auto kern = args->accel ? rvcp::path_scatter_kernel<true> : rvcp::path_scatter_kernel<false>;
+    rvcp::FrameArgs A;
+    uint32_t blocks = 0;
+    if (!path_query_grid(kern, args, grid_waves_per_simd, 0, A, blocks)) return -2;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(rvcp::kBlock), 0, (hipStream_t)stream, A, tri, shade,
+                       mats, (const rvcp_material_t *)raw_materials, lights, bvh_nodes, bvh_tris,
+                       (const float4 *)rays, (const float *)seeds, (float *)out, counters);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

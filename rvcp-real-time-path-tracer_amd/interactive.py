@@ -159,7 +159,7 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
                  on_fps: Optional[Callable[[int], None]] = None, denoise=None,
                  temporal=None, svgf=None, demodulate: Optional[bool] = None,
                  taa: Optional[bool] = None, sampling: Optional[int] = None,
-                 adaptive=None) -> dict:
+                 adaptive=None, materials: Optional[int] = None) -> dict:
     """``main_loop`` (ray_tracer.rs:22-100) without a window.
 
     Per frame: apply this frame's scripted events, count FPS (printed once a second as
@@ -188,6 +188,10 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
     loop (False switches it off), so that the ``svgf`` chain traces every frame through the
     per-pixel sample counts planned from the previous frame's variance; None
     (default) leaves the tracer's switch as it is.
+    ``materials``: abi.MATERIALS_LAMBERTIAN / abi.MATERIALS_SCATTER sets ``tracer.materials``
+    before the loop, so that every frame, through whichever chain, scatters at Metal and
+    Dielectric faces by their material; None (default) leaves the tracer's mode
+    as it is.
     Returns per-frame render times and the final camera."""
     if demodulate is not None:
         tracer.demodulation = bool(demodulate)
@@ -195,6 +199,8 @@ def run_headless(tracer, scene, frames: int, width: int, height: int,
         tracer.taa = bool(taa)
     if sampling is not None:
         tracer.sampling = int(sampling)
+    if materials is not None:
+        tracer.materials = int(materials)
     if adaptive is not None:
         tracer.adaptive = None if adaptive is False else adaptive
     info = RuntimeInfo(window_size=(width, height))

@@ -613,6 +613,25 @@ class RayTracer:
     def sampling(self, mode: int):
         self._check(self._lib.rvcp_set_sampling(self._ctx, int(mode)))
 
+    # material scattering on meshes
+    @property
+    def materials(self) -> int:
+        """The context's materials mode (rvcp_get_materials / rvcp_set_materials):
+        abi.MATERIALS_LAMBERTIAN (the default: every non-emissive face is a Lambertian surface,
+        as in the shader; frames bit-identical to the oracle) or abi.MATERIALS_SCATTER (Metal
+        and Dielectric faces reflect and refract as the reference's material_scatter defines;
+        render, the chains and trace_paths run the material kernel).  It holds across
+        upload_scene, which then rejects a fuzz outside [0, 1] or a refraction ratio that is
+        not positive; changing it drops the temporal chains' histories."""
+        mode = ctypes.c_int32(0)
+        self._check(self._lib.rvcp_get_materials(self._ctx, ctypes.cast(ctypes.byref(mode),
+                                                                       ctypes.c_void_p)))
+        return int(mode.value)
+
+    @materials.setter
+    def materials(self, mode: int):
+        self._check(self._lib.rvcp_set_materials(self._ctx, int(mode)))
+
     # adaptive sampling: per-pixel sample counts (DESIGN.md §4.18)
     def render_spp_map_async(self, push, width, height, d_spp_map: int, spp_hint: int, d_rgba: int,
                              d_linear: int = 0, stream: int = 0):

@@ -383,6 +383,25 @@ def checker_floor_scene(base: Optional[Scene] = None, n: int = 4,
     return Scene(base.camera, mats, list(base.spheres), Mesh(V, F))
 
 
+def specular_cornell_scene(fuzz: float = 1.0, ior: float = 1.5, mirror_floor: bool = True) -> Scene:
+    """The Cornell box with three materials appended and given to its boxes and floor, for the
+    opt-in material scattering (rvcp_set_materials): a metal of albedo 0.8 and
+    `fuzz` on the tall box (faces 12-21), a dielectric of refraction ratio `ior` on the short box
+    (faces 22-31) and, with `mirror_floor`, a fuzz-0 metal of albedo 0.9 on the floor (faces
+    10-11).  With the mode off every one of them renders as a Lambertian surface of its albedo."""
+    base = cornell_box()
+    mats = list(base.materials)
+    metal, glass, mirror = len(mats), len(mats) + 1, len(mats) + 2
+    mats += [Material.new_metal(vec3(0.8, 0.8, 0.8), fuzz), Material.new_dielectric(ior),
+             Material.new_metal(vec3(0.9, 0.9, 0.9), 0.0)]
+    F = []
+    for i, f in enumerate(base.mesh.faces):
+        m = metal if 12 <= i <= 21 else glass if 22 <= i <= 31 else \
+            mirror if mirror_floor and 10 <= i <= 11 else f.material_id
+        F.append(Face(f.vertices, m))
+    return Scene(base.camera, mats, [], Mesh(list(base.mesh.vertices), F))
+
+
 def rotated_scene(base: Scene, yaw_deg: float = 23.0, pitch_deg: float = 17.0,
                   roll_deg: float = 11.0, center=(0.0, 274.4, 0.0)) -> Scene:
     """`base` with its mesh AND camera turned by R = Rz(roll) Rx(pitch) Ry(yaw) about `center` (the
