@@ -196,6 +196,7 @@ struct rvcp_ctx {
     int32_t jit_sampling[2] = {RVCP_SAMPLING_UNIFORM, -1};
     std::vector<TriRecord> jit_tri;
     bool jit_bvh = false;
+    uint64_t jit_lum = 0;       // the luminous faces' mask the module was asked with (JitSpec::lum_mask)
     float light_total = 0.0f, light_pdf = 0.0f;
     bool has_scene = false;
 
@@ -1171,6 +1172,7 @@ static int upload_one(rvcp_ctx_t *ctx, const rvcp_material_t *materials, uint32_
     ctx->jit_err.clear();
     ctx->jit_tri.clear();
     ctx->jit_bvh = false;
+    ctx->jit_lum = 0;
     ctx->jit_sampling[0] = ctx->sampling;
     ctx->jit_sampling[1] = -1;
     if (bvh_jit) {                            // the BVH hybrid's module (above)
@@ -1190,6 +1192,9 @@ static int upload_one(rvcp_ctx_t *ctx, const rvcp_material_t *materials, uint32_
         spec.spheres = spheres;
         spec.n_spheres = n_spheres;
         spec.n_materials = n_materials;
+        for (uint32_t i = 0; i < n_lum_face_ids; i++)
+            if (tab.lights[i].face < 64u) spec.lum_mask |= 1ull << tab.lights[i].face;
+        ctx->jit_lum = spec.lum_mask;
         ctx->jit[0] = jit_path_kernels(ctx->device, tri.data(), n_faces, spec, ctx->jit_err);
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         if (!legacy) ctx->jit_tri = tri;      // (mode 2 has one sampling: nothing to ask again)
@@ -1255,6 +1260,7 @@ static void jit_for_render(rvcp_ctx_t *ctx, bool map)
     spec.bvh = ctx->jit_bvh;
     spec.sampling = ctx->sampling;
     spec.spp_map = map;
+    spec.lum_mask = ctx->jit_lum;
     jit = jit_path_kernels(ctx->device, ctx->jit_tri.data(), (uint32_t)ctx->jit_tri.size(), spec,
                            map ? map_err : ctx->jit_err);
     (void)hipSetDevice(ctx->device);

@@ -468,11 +468,15 @@ bool emit_triangle(std::string &decl, std::string &accept, const TriRecord &T, u
 // t, RangeMask) is not committed on its own -- the two tests of each ray and the other ray's
 // tests between them form one region, so the compiler can merge the two acceptances of a ray
 // (both write the same t) into one select of bt.
+//
+// `ids` (the grouped scan, jit_groups_source): the scan covers the n faces ids[0..n) of `tri`, in
+// that order, each under its own index in the scene -- nullptr: faces 0..n.
 void emit_scan(std::string &out, const TriRecord *tri, uint32_t n, const char *const *rays,
-               int n_rays, unsigned opts = 0)
+               int n_rays, unsigned opts = 0, const uint32_t *ids = nullptr)
 {
     const bool skip_b = (opts & kScanSkipB) != 0, eager = (opts & kScanEagerSplit) != 0;
     const uint32_t N = n * (uint32_t)n_rays;
+    auto face = [&](uint32_t k) { return ids ? ids[k] : k; };
     std::vector<char> used(N), reused(N);
     {   // dry run: which tests are emitted and which reuse their ray's previous range mask
         std::map<std::string, std::string> seen;
@@ -480,7 +484,7 @@ void emit_scan(std::string &out, const TriRecord *tri, uint32_t n, const char *c
         for (uint32_t u = 0; u < N; u++) {
             std::string decl, accept;
             bool ru = false;
-            used[u] = emit_triangle(decl, accept, tri[u / (uint32_t)n_rays], u / (uint32_t)n_rays,
+            used[u] = emit_triangle(decl, accept, tri[face(u / (uint32_t)n_rays)], face(u / (uint32_t)n_rays),
                                     rays[u % (uint32_t)n_rays], seen, prev, &ru);
             reused[u] = used[u] && ru;
         }
@@ -503,8 +507,8 @@ void emit_scan(std::string &out, const TriRecord *tri, uint32_t n, const char *c
         std::string decl, accept;
         const std::string R(rays[u % (uint32_t)n_rays]);
         const bool defer = defers(u);
-        emit_triangle(decl, accept, tri[u / (uint32_t)n_rays], u / (uint32_t)n_rays, R.c_str(),
-                      seen, prev, nullptr, defer);
+        emit_triangle(decl, accept, tri[face(u / (uint32_t)n_rays)], face(u / (uint32_t)n_rays),
+                      R.c_str(), seen, prev, nullptr, defer);
         out += decl;
         if (!used[u]) return;
         out += "    {\n" + accept + "    }\n";
@@ -533,12 +537,12 @@ void emit_scan(std::string &out, const TriRecord *tri, uint32_t n, const char *c
             const bool defer = k + 1 < run.size();
             std::string decl, inner, acc;
             if (k == 0) {
-                emit_triangle(decl, acc, tri[u / 2], u / 2, R, seen, prev, nullptr, defer,
+                emit_triangle(decl, acc, tri[face(u / 2)], face(u / 2), R, seen, prev, nullptr, defer,
                               &inner, &inner_seen, eager);
                 head += decl;
                 body += inner;
             } else {
-                emit_triangle(decl, acc, tri[u / 2], u / 2, R, inner_seen, prev, nullptr, defer);
+                emit_triangle(decl, acc, tri[face(u / 2)], face(u / 2), R, inner_seen, prev, nullptr, defer);
                 body += decl;
             }
             accept += acc;
@@ -690,6 +694,216 @@ std::string jit_scan_source(const TriRecord *tri, uint32_t n, unsigned opts)
     out += "__device__ __forceinline__ void spec_scan2(f3 oA, f3 dA, f3 oB, f3 dB, float tmin, "
            "float &btA, float &btB, int &bestB) {\n";
     emit_scan(out, tri, n, two, 2, opts);
+    out += "}\n";
+    return out;
+}
+
+// ------------------------------------------------------------------ face groups ---------
+// The grouped scan (DESIGN.md §4.7 "Face groups"): the scene's faces split into an always set,
+// scanned for every ray as before, and up to kMaxGroups groups, each tested only for the rays
+// that reach its padded box or run nearly parallel to one of its planes.  The constants below
+// are the ones §4.7's bound is written for; change them there too.
+namespace {
+constexpr uint32_t kMaxGroups = 4;         // a bit per group in spec_group_reach's mask
+constexpr uint32_t kGroupMinFaces = 6;
+constexpr uint32_t kGroupMaxNormals = 6;   // distinct plane directions per group (a hexahedron's)
+constexpr double kGroupPad = 1.0 / 64;     // the box pad, of the scene box's longest extent L
+constexpr double kGroupHeight = 0.25;      // a face's height, of its longest edge, at least
+constexpr double kGroupCoord = 1024.0;     // every |coordinate| at most this many L
+constexpr double kGroupOrigin = 1.5;       // origins within this many L of the scene box's centre
+constexpr double kGroupNormalCos = 1.0 - 1e-9;   // |n . representative| of one plane direction
+constexpr float kGroupParallel = 0x1p-7f;  // |d . n| below this many |d|_1: "nearly parallel"
+
+float round_down(double x)                 // the largest float <= x
+{
+    float f = (float)x;
+    return (double)f > x ? std::nextafterf(f, -INFINITY) : f;
+}
+float round_up(double x)
+{
+    float f = (float)x;
+    return (double)f < x ? std::nextafterf(f, INFINITY) : f;
+}
+void face_points(const TriRecord &T, double p[3][3])   // the triangle the test sees: v0, v0 + e1, v0 + e2
+{
+    for (int k = 0; k < 3; k++) {
+        p[0][k] = T.v0[k];
+        p[1][k] = (double)T.v0[k] + (double)T.e1[k];
+        p[2][k] = (double)T.v0[k] + (double)T.e2[k];
+    }
+}
+}  // namespace
+
+ScanGroups jit_scan_groups(const TriRecord *tri, uint32_t n, uint64_t lum_mask)
+{
+    ScanGroups G;
+    G.group_of.assign(n, -1);
+    if (n == 0 || n > 64) return G;
+    // the scene box (of the triangles as the test sees them) and its longest extent L
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, amax = 0.0;
+    for (uint32_t i = 0; i < n; i++) {
+        double p[3][3];
+        face_points(tri[i], p);
+        for (int v = 0; v < 3; v++)
+            for (int k = 0; k < 3; k++) {
+                if (!std::isfinite(p[v][k])) return G;
+                lo[k] = std::min(lo[k], p[v][k]);
+                hi[k] = std::max(hi[k], p[v][k]);
+                amax = std::max(amax, std::fabs(p[v][k]));
+            }
+    }
+    const double L = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
+    if (!(L > 0.0) || !(amax <= kGroupCoord * L) || !(L <= 0x1p40)) return G;
+    const double pad = kGroupPad * L;
+    auto area_of = [](const double a[3], const double b[3], double grow) {
+        const double x = b[0] - a[0] + 2 * grow, y = b[1] - a[1] + 2 * grow, z = b[2] - a[2] + 2 * grow;
+        return 2.0 * (x * y + y * z + z * x);
+    };
+    const double scene_area = area_of(lo, hi, 0.0);
+    // connected components by exactly equal vertex positions (the float v0, RN(v0 + e1), RN(v0 + e2))
+    std::vector<uint32_t> parent(n);
+    for (uint32_t i = 0; i < n; i++) parent[i] = i;
+    auto find = [&](uint32_t x) {
+        while (parent[x] != x) x = parent[x] = parent[parent[x]];
+        return x;
+    };
+    std::map<std::vector<uint32_t>, uint32_t> first;      // position bits (-0 as +0) -> a face
+    for (uint32_t i = 0; i < n; i++) {
+        for (int v = 0; v < 3; v++) {
+            std::vector<uint32_t> key(3);
+            for (int k = 0; k < 3; k++) {
+                float c = v == 0 ? tri[i].v0[k] : tri[i].v0[k] + (v == 1 ? tri[i].e1[k] : tri[i].e2[k]);
+                if (c == 0.0f) c = 0.0f;
+                std::memcpy(&key[k], &c, 4);
+            }
+            const auto it = first.find(key);
+            if (it == first.end()) first[key] = i;
+            else parent[find(i)] = find(it->second);
+        }
+    }
+    for (uint32_t root = 0; root < n && G.groups.size() < kMaxGroups; root++) {
+        if (find(root) != root) continue;
+        ScanGroup g;
+        double glo[3] = {INFINITY, INFINITY, INFINITY}, ghi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        bool ok = true;
+        for (uint32_t i = 0; i < n && ok; i++) {
+            if (find(i) != root) continue;
+            g.faces.push_back(i);
+            if ((lum_mask >> i) & 1ull) ok = false;       // luminous faces lead the always set
+            double p[3][3], e[3][3], len2[3], nrm[3];
+            face_points(tri[i], p);
+            for (int k = 0; k < 3; k++) {
+                e[0][k] = p[1][k] - p[0][k];
+                e[1][k] = p[2][k] - p[0][k];
+                e[2][k] = p[2][k] - p[1][k];
+            }
+            for (int j = 0; j < 3; j++) len2[j] = e[j][0] * e[j][0] + e[j][1] * e[j][1] + e[j][2] * e[j][2];
+            nrm[0] = e[0][1] * e[1][2] - e[0][2] * e[1][1];
+            nrm[1] = e[0][2] * e[1][0] - e[0][0] * e[1][2];
+            nrm[2] = e[0][0] * e[1][1] - e[0][1] * e[1][0];
+            const double area2 = std::sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
+            const double longest2 = std::max(len2[0], std::max(len2[1], len2[2]));
+            // conditioning: height = 2 area / longest edge >= kGroupHeight x longest edge
+            if (!(longest2 > 0.0) || !(area2 >= kGroupHeight * longest2)) { ok = false; break; }
+            for (int k = 0; k < 3; k++) nrm[k] /= area2;
+            bool known = false;
+            for (const auto &r : g.normals)
+                if (std::fabs(r[0] * nrm[0] + r[1] * nrm[1] + r[2] * nrm[2]) >= kGroupNormalCos) known = true;
+            if (!known) g.normals.push_back({nrm[0], nrm[1], nrm[2]});
+            for (int v = 0; v < 3; v++)
+                for (int k = 0; k < 3; k++) {
+                    glo[k] = std::min(glo[k], p[v][k]);
+                    ghi[k] = std::max(ghi[k], p[v][k]);
+                }
+        }
+        if (!ok || g.faces.size() < kGroupMinFaces || g.normals.size() > kGroupMaxNormals) continue;
+        if (!(area_of(glo, ghi, pad) <= 0.25 * scene_area)) continue;
+        for (int k = 0; k < 3; k++) {
+            g.lo[k] = round_down(glo[k] - pad);
+            g.hi[k] = round_up(ghi[k] + pad);
+        }
+        for (uint32_t f : g.faces) G.group_of[f] = (int)G.groups.size();
+        G.groups.push_back(g);
+    }
+    for (int k = 0; k < 3; k++) {
+        G.centre[k] = (float)(0.5 * (lo[k] + hi[k]));
+        G.reach[k] = round_down(kGroupOrigin * L);
+    }
+    return G;
+}
+
+std::string jit_groups_source(const TriRecord *tri, uint32_t n, uint64_t lum_mask, unsigned opts)
+{
+    const ScanGroups G = jit_scan_groups(tri, n, lum_mask);
+    if (G.groups.empty()) return std::string();
+    static const char *const one[] = {""}, *const two[] = {"A", "B"};
+    std::string out = "// the grouped scan (rvcp_jit.cpp jit_groups_source, DESIGN.md §4.7): " +
+                      std::to_string(G.groups.size()) + " face groups\n#define RVCP_SPEC_GROUPS " +
+                      std::to_string(G.groups.size()) + "\n";
+    // the origin limit of the bound, part of the per-wave ray guard
+    out += "__device__ __forceinline__ bool spec_group_origin_ok(f3 o) {\n    return ";
+    for (int k = 0; k < 3; k++) {
+        const std::string c = std::string("o.") + "xyz"[k];
+        out += std::string(k ? " &\n           " : "") + "(__builtin_fabsf(" + c + " - " + lit_text(G.centre[k]) +
+               ") <= " + lit_text(G.reach[k]) + ")";
+    }
+    out += ";\n}\n";
+    // the reach test: bit g set when the ray's [tmin, bt] meets group g's padded box (slabs;
+    // min / max drop a NaN operand, and a NaN bound compares false: both count as reached) or
+    // the ray runs nearly parallel to one of the group's planes
+    out += "__device__ __forceinline__ unsigned spec_group_reach(f3 o, f3 d, float tmin, float bt) {\n"
+           "    const float ix = RVCP_SPEC_BOX_RCP(d.x), iy = RVCP_SPEC_BOX_RCP(d.y), iz = RVCP_SPEC_BOX_RCP(d.z);\n"
+           "    const float dn = ((__builtin_fabsf(d.x) + __builtin_fabsf(d.y)) + __builtin_fabsf(d.z)) * " +
+           lit_text(kGroupParallel) + ";\n    unsigned m = 0u;\n";
+    for (size_t gi = 0; gi < G.groups.size(); gi++) {
+        const ScanGroup &g = G.groups[gi];
+        out += "    {\n";
+        for (int k = 0; k < 3; k++) {
+            const std::string c(1, "xyz"[k]);
+            out += "        const float a" + c + " = (" + lit_text(g.lo[k]) + " - o." + c + ") * i" + c +
+                   ", b" + c + " = (" + lit_text(g.hi[k]) + " - o." + c + ") * i" + c + ";\n";
+        }
+        out += "        const float tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(ax, bx), __builtin_fminf(ay, by)), "
+               "__builtin_fmaxf(__builtin_fminf(az, bz), tmin));\n"
+               "        const float tf = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(ax, bx), __builtin_fmaxf(ay, by)), "
+               "__builtin_fminf(__builtin_fmaxf(az, bz), bt));\n"
+               "        bool r = !(tn > tf);\n";
+        for (const auto &nr : g.normals) {
+            std::string e;
+            for (int k = 0; k < 3; k++) {
+                const float c = (float)nr[k];
+                if (c == 0.0f) continue;                // an exact-zero component: the term is a zero
+                const std::string dk = std::string("d.") + "xyz"[k];
+                e = e.empty() ? dk + " * " + lit_text(c)
+                              : "__builtin_fmaf(" + dk + ", " + lit_text(c) + ", " + e + ")";
+            }
+            if (e.empty()) e = "0.0f";
+            out += "        r |= __builtin_fabsf(" + e + ") < dn;\n";
+        }
+        out += "        m |= r ? " + std::to_string(1u << gi) + "u : 0u;\n    }\n";
+    }
+    out += "    return m;\n}\n";
+    // the always set's scans, under the faces' own indices
+    std::vector<uint32_t> always;
+    for (uint32_t i = 0; i < n; i++)
+        if (G.group_of[i] < 0) always.push_back(i);
+    out += "__device__ __forceinline__ void spec_always1(f3 o, f3 d, float tmin, float &bt, int &best) {\n";
+    emit_scan(out, tri, (uint32_t)always.size(), one, 1, 0, always.data());
+    out += "}\n__device__ __forceinline__ void spec_always2(f3 oA, f3 dA, f3 oB, f3 dB, float tmin, "
+           "float &btA, float &btB, int &bestB) {\n";
+    emit_scan(out, tri, (uint32_t)always.size(), two, 2, opts, always.data());
+    out += "}\n";
+    // each group's single-ray scan, and the one an item's group index selects
+    for (size_t gi = 0; gi < G.groups.size(); gi++) {
+        out += "__device__ __forceinline__ void spec_group_scan" + std::to_string(gi) +
+               "(f3 o, f3 d, float tmin, float &bt, int &best) {\n";
+        emit_scan(out, tri, (uint32_t)G.groups[gi].faces.size(), one, 1, 0, G.groups[gi].faces.data());
+        out += "}\n";
+    }
+    out += "__device__ __forceinline__ void spec_group_scan(int g, f3 o, f3 d, float tmin, float &bt, int &best) {\n";
+    for (size_t gi = 0; gi < G.groups.size(); gi++)
+        out += "    if (g == " + std::to_string(gi) + ") spec_group_scan" + std::to_string(gi) +
+               "(o, d, tmin, bt, best);\n";
     out += "}\n";
     return out;
 }
@@ -1067,7 +1281,11 @@ std::string jit_module_source(const TriRecord *tri, uint32_t n, const JitSpec &s
     cc.spp_map = spec.spp_map;
     std::string key_flags;
     for (const std::string &x : jit_extra_flags()) key_flags += " " + x;
+    // (the face groups: only the schedule-3/6 path kernels of a plain games101 module read them --
+    // mode 2's module and the BVH hybrid's keep the ungrouped scan alone; a scene without an
+    // eligible group adds no text, so its module and key are the ungrouped ones)
     return jit_scan_source(tri, n, jit_scan_opts()) +
+        (spec.legacy || spec.bvh ? std::string() : jit_groups_source(tri, n, spec.lum_mask, jit_scan_opts())) +
         (spec.legacy ? "// +legacy " + std::to_string(cc.legacy_waves) + (cc.lds_scene ? " lds" : "") + "\n"
 #ifndef RVCP_NO_SPHERE_LITERALS     // (A/B variant only, tools/build_variant.sh)
                       + jit_sphere_source(spec.spheres, spec.n_spheres)
@@ -1305,6 +1523,38 @@ extern "C" size_t rvcp_internal_jit_scan_source(const void *tri_records, uint32_
                                                 size_t cap)
 {
     return rvcp_internal_jit_scan_source_opt(tri_records, n, 0, out, cap);
+}
+
+// The grouped scan's text for n triangle records and the luminous faces' mask ("" without an
+// eligible group), and the partition behind it: group_of[n] gets each face's group or -1, box[6 g
+// ...] each group's padded box (lo, hi); returns the number of groups.
+extern "C" size_t rvcp_internal_jit_groups_source(const void *tri_records, uint32_t n,
+                                                  uint64_t lum_mask, char *out, size_t cap)
+{
+    try {
+        return copy_out(rvcp::jit_groups_source(static_cast<const rvcp::TriRecord *>(tri_records), n,
+                                                lum_mask), out, cap);
+    } catch (...) {
+        return 0;
+    }
+}
+
+extern "C" int rvcp_internal_jit_groups(const void *tri_records, uint32_t n, uint64_t lum_mask,
+                                        int32_t *group_of, float *box)
+{
+    try {
+        const rvcp::ScanGroups G =
+            rvcp::jit_scan_groups(static_cast<const rvcp::TriRecord *>(tri_records), n, lum_mask);
+        for (uint32_t i = 0; group_of && i < n; i++) group_of[i] = G.group_of[i];
+        for (size_t g = 0; box && g < G.groups.size(); g++)
+            for (int k = 0; k < 3; k++) {
+                box[6 * g + k] = G.groups[g].lo[k];
+                box[6 * g + 3 + k] = G.groups[g].hi[k];
+            }
+        return (int)G.groups.size();
+    } catch (...) {
+        return -1;
+    }
 }
 
 // The sphere X-macro of a mode-2 module for n sphere records (rvcp_sphere_t); the length without

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <memory>
 #include <string>
 #include <vector>
@@ -44,6 +45,23 @@ std::vector<std::string> jit_extra_flags();
 // opts: kScanSkipB | kScanEagerSplit (experiment knobs, jit_scan_opts)
 constexpr unsigned kScanSkipB = 1u, kScanEagerSplit = 2u;
 std::string jit_scan_source(const TriRecord *tri, uint32_t n, unsigned opts = 0);
+// Face groups: the partition of a scene's faces into an always set and groups
+// that a ray tests only when it reaches the group's padded box or runs nearly parallel to one of
+// its planes.  lum_mask: bit i set for a luminous face i (they stay in the always set).
+struct ScanGroup {
+    std::vector<uint32_t> faces;                 // ascending
+    float lo[3], hi[3];                          // the padded box, rounded outward
+    std::vector<std::array<double, 3>> normals;  // one unit normal per distinct plane direction
+};
+struct ScanGroups {
+    std::vector<int> group_of;                   // per face: its group, or -1 (always set)
+    std::vector<ScanGroup> groups;
+    float centre[3] = {0, 0, 0}, reach[3] = {0, 0, 0};   // origins admitted: |o - centre| <= reach
+};
+ScanGroups jit_scan_groups(const TriRecord *tri, uint32_t n, uint64_t lum_mask);
+// The grouped scan's text (RVCP_SPEC_GROUPS, spec_group_origin_ok, spec_group_reach, spec_always1/2,
+// spec_group_scan), appended to a games101 module's scan; "" for a scene without an eligible group.
+std::string jit_groups_source(const TriRecord *tri, uint32_t n, uint64_t lum_mask, unsigned opts = 0);
 // What a module is compiled with besides its scan: the options' variant defines (jit_options)
 // and so, with the scan, the module's compile key.
 struct JitCompile {
@@ -82,6 +100,9 @@ struct JitSpec {
     // (jit_sphere_source) -- the module is then valid for these spheres only, like its scan
     const rvcp_sphere_t *spheres = nullptr;
     uint32_t n_spheres = 0, n_materials = 64;
+    // the scene's luminous faces (bit i: face i), which the grouped scan keeps in its always set;
+    // read only for a module that may get face groups (neither legacy nor bvh)
+    uint64_t lum_mask = 0;
 };
 // Compiled + loaded kernels for the scene on `device` (process-wide cache keyed by the module's
 // source text: the scan and the spec's tags); nullptr with err set when hipRTC is unavailable or

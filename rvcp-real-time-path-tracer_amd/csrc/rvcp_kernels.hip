@@ -387,6 +387,9 @@ __device__ __forceinline__ bool dir_fast_ok(f3 d) {
 // `grain`) that the denominator is +-0 or in [2^-126, 2^126] in magnitude for every ray the
 // wave admits (ray_in_range with dir_grain_ok)
 #define RVCP_SPEC_RCP_FAST(den) rcp_scan_fast(den)
+// the reach test's slab reciprocals (spec_group_reach): v_rcp_f32 as it is, 1 ulp -- the box pad
+// covers it (DESIGN.md §4.7 "Face groups"); rcp(+-0) = +-inf
+#define RVCP_SPEC_BOX_RCP(x) __builtin_amdgcn_rcpf(x)
 #include RVCP_SPEC_SCAN
 // The specialised scan drops products with exact-zero triangle components.  That is exact
 // when no intermediate of the generic test overflows (inf * 0 = NaN rejects there, while the
@@ -401,6 +404,91 @@ __device__ __forceinline__ bool ray_in_range(f3 o, f3 d) {
            (((__builtin_fabsf(d.x) + __builtin_fabsf(d.y)) + __builtin_fabsf(d.z)) <= 16.0f) &
            dir_grain_ok(d);
 }
+#ifdef RVCP_SPEC_GROUPS
+// Face groups: the module's scans spec_always1 / spec_always2 cover the always
+// set; each of the RVCP_SPEC_GROUPS groups is tested only for the rays that spec_group_reach
+// admits -- no (ray, face) pair the full scan would accept is left out for a ray that passes
+// spec_ray_ok (the bound's origin limit on top of ray_in_range).
+__device__ __forceinline__ bool spec_ray_ok(f3 o, f3 d) {
+    return ray_in_range(o, d) & spec_group_origin_ok(o);
+}
+// After the always-set scan: every live ray of the wave (slot A: a_*, btA, no face kept; slot B:
+// b_*, btB, bestB) is tested against the groups it reaches, over [tmin, its bound].  A (ray,
+// group) pair is an item; items are numbered group by group (slot A's in lane order, then slot
+// B's), written to the wave's rows (origin + bound, direction + group: two float4 each, 64 a
+// pass), scanned one per lane -- a group at a time under the exec mask -- and their results read
+// back by the owners from the same rows and merged by the order-free rule of the tail partition
+// (smaller t, or equal t and larger face).  Passes of 64 while items remain.  Wave-local: wave
+// barriers and wavefront fences only, as the compact scan.
+__device__ __forceinline__ void spec_group_pass(float4 *rows, float tmin, bool hasA, f3 a_o, f3 a_d,
+                                                float &btA, bool hasB, f3 b_o, f3 b_d, float &btB,
+                                                int &bestB) {
+    const uint32_t rA = hasA ? spec_group_reach(a_o, a_d, tmin, btA) : 0u;
+    const uint32_t rB = hasB ? spec_group_reach(b_o, b_d, tmin, btB) : 0u;
+    if (__builtin_amdgcn_ballot_w64((rA | rB) != 0u) == 0ull) return;
+    uint64_t m[2 * RVCP_SPEC_GROUPS];
+    uint32_t base[2 * RVCP_SPEC_GROUPS], total = 0u;
+#pragma unroll
+    for (int g = 0; g < RVCP_SPEC_GROUPS; g++) {
+        m[2 * g] = __builtin_amdgcn_ballot_w64(((rA >> g) & 1u) != 0u);
+        base[2 * g] = total;
+        total += (uint32_t)__builtin_popcountll(m[2 * g]);
+        m[2 * g + 1] = __builtin_amdgcn_ballot_w64(((rB >> g) & 1u) != 0u);
+        base[2 * g + 1] = total;
+        total += (uint32_t)__builtin_popcountll(m[2 * g + 1]);
+    }
+    for (uint32_t p0 = 0u; p0 < total; p0 += (uint32_t)kWave) {
+        // (the rows are free: whatever read them before this pass has its values)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int g = 0; g < RVCP_SPEC_GROUPS; g++) {
+            // an item before this pass wraps to a huge j, one after it is >= kWave
+            const uint32_t jA = base[2 * g] + rank_in(m[2 * g]) - p0;
+            if (((rA >> g) & 1u) != 0u && jA < (uint32_t)kWave) {
+                rows[2 * jA] = make_float4(a_o.x, a_o.y, a_o.z, btA);
+                rows[2 * jA + 1] = make_float4(a_d.x, a_d.y, a_d.z, __int_as_float(g));
+            }
+            const uint32_t jB = base[2 * g + 1] + rank_in(m[2 * g + 1]) - p0;
+            if (((rB >> g) & 1u) != 0u && jB < (uint32_t)kWave) {
+                rows[2 * jB] = make_float4(b_o.x, b_o.y, b_o.z, btB);
+                rows[2 * jB + 1] = make_float4(b_d.x, b_d.y, b_d.z, __int_as_float(g));
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint32_t lane_r = lane_id();
+        const float4 ro = rows[2 * lane_r], rd = rows[2 * lane_r + 1];
+        float bt = ro.w;
+        int best = -1;
+        if (lane_r < total - p0)        // (the lanes past the items hold stale rows)
+            spec_group_scan(__float_as_int(rd.w), mk(ro.x, ro.y, ro.z), mk(rd.x, rd.y, rd.z), tmin, bt, best);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        rows[2 * lane_r] = make_float4(bt, __int_as_float(best), 0.0f, 0.0f);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int g = 0; g < RVCP_SPEC_GROUPS; g++) {
+            const uint32_t jA = base[2 * g] + rank_in(m[2 * g]) - p0;
+            if (((rA >> g) & 1u) != 0u && jA < (uint32_t)kWave) {
+                const float4 r = rows[2 * jA];
+                if (__float_as_int(r.y) >= 0 && r.x < btA) btA = r.x;     // slot A keeps no face
+            }
+            const uint32_t jB = base[2 * g + 1] + rank_in(m[2 * g + 1]) - p0;
+            if (((rB >> g) & 1u) != 0u && jB < (uint32_t)kWave) {
+                const float4 r = rows[2 * jB];
+                const int ob = __float_as_int(r.y);
+                if (ob >= 0 && (r.x < btB || (r.x == btB && ob > bestB))) { btB = r.x; bestB = ob; }
+            }
+        }
+    }
+}
+#endif
 #endif
 // A necessary condition for tri_stage2 to accept, from stage 1 alone: |n1| and |n2| at most
 // RN(|den| (1 + 2^-20)) (proof: DESIGN.md §4.2).  A wave skips stage 2 of a triangle when no
@@ -3001,7 +3089,15 @@ __device__ __forceinline__ void path_body(
             const f3 o = mk(ro.x, ro.y, ro.z), d = mk(rd.x, rd.y, rd.z);
             float bt = A.t_max;
             int best = -1;
-#ifdef RVCP_SPEC_SCAN
+#ifdef RVCP_SPEC_GROUPS
+            // the always set for every ray, then each group for the rays that reach it (the
+            // rows are free: every lane holds its ray)
+            if (!__any(lane_r < nr && !spec_ray_ok(o, d))) {
+                spec_always1(o, d, A.t_min, bt, best);
+                float no_bt = -1.0f;
+                spec_group_pass(rows, A.t_min, false, o, d, no_bt, lane_r < nr, o, d, bt, best);
+            } else
+#elif defined(RVCP_SPEC_SCAN)
             if (!__any(lane_r < nr && !ray_in_range(o, d))) {
                 spec_scan1(o, d, A.t_min, bt, best);
             } else
@@ -3030,7 +3126,16 @@ __device__ __forceinline__ void path_body(
             }
         } else {
             // ---- scan: both rays against every triangle (wave-uniform face index) ----
-#ifdef RVCP_SPEC_SCAN
+#ifdef RVCP_SPEC_GROUPS
+            if (!TILED && !BVH &&
+                !__any((hasA && !spec_ray_ok(a_o, a_d)) || (hasB && !spec_ray_ok(b_o, b_d)))) {
+                // as below, over the always set; then each group for the rays that reach it
+                if (!hasA) btA = -1.0f;
+                spec_always2(a_o, a_d, b_o, b_d, A.t_min, btA, btB, bestB);
+                spec_group_pass(compact_lds + wv * (2 * kWave), A.t_min, hasA, a_o, a_d, btA, hasB,
+                                b_o, b_d, btB, bestB);
+            } else
+#elif defined(RVCP_SPEC_SCAN)
             if (!__any((hasA && !ray_in_range(a_o, a_d)) || (hasB && !ray_in_range(b_o, b_d)))) {
                 // the shadow ray's nearest face is not needed, only whether it hit (resolve
                 // A): a nearest t other than t_max is a hit; t_max itself (a miss, or a hit at
@@ -3488,9 +3593,10 @@ __device__ __forceinline__ void legacy_body(
     float seed = 0.0f, ridx = 0.0f;
     f3 acc = mk(0, 0, 0), att = mk(1, 1, 1), col = mk(0, 0, 0);
 #ifdef RVCP_LEGACY_LDS_PRIMARY
-    // the cached primary hit in this lane's LDS column (prim_lds[f * kBlock], f = 0..10:
-    // position, normal, direction, material | front-face bit 31) instead of 11 VGPRs held for
-    // the whole pixel: it is written once per pixel and read once per sample
+    // the cached primary hit in this lane's LDS column (prim_lds[f * kBlock], f = 0..9: ten
+    // fields -- position, normal, direction, material | front-face bit 31) instead of the 11
+    // VGPRs held for the whole pixel (the front-face bit had its own): it is written once per
+    // pixel and read once per sample
     float *const pcol = prim_lds + threadIdx.x;
     auto prim_put = [&](f3 p, f3 n, f3 d, uint32_t m, bool out) {
         pcol[0 * kBlock] = p.x; pcol[1 * kBlock] = p.y; pcol[2 * kBlock] = p.z;

@@ -25,6 +25,8 @@ def main():
     ap.add_argument("--scene", default="cornell", choices=["cornell", "spheres"])
     ap.add_argument("--legacy", action="store_true", help="the mode-2 module (RVCP_JIT_LEGACY)")
     ap.add_argument("--opts", type=int, default=0, help="generator options (rvcp_jit.h kScan*)")
+    ap.add_argument("--no-groups", action="store_true",
+                    help="the module without the face groups (DESIGN.md §4.7): the ungrouped scan alone")
     ap.add_argument("--no-sphere-literals", action="store_true",
                     help="--legacy: the module without the spheres as literals (the record loop)")
     a = ap.parse_args()
@@ -43,6 +45,17 @@ def main():
     buf = ctypes.create_string_buffer(n + 1)
     fn(rec.ctypes.data, len(rec), a.opts, buf, n + 1)
     text = buf.value.decode()
+    if not a.legacy and not a.no_groups:           # the face groups of a plain games101 module
+        lum = 0
+        for i in sc.luminous_face_ids():
+            lum |= 1 << int(i)
+        fg = L.rvcp_internal_jit_groups_source
+        fg.restype = ctypes.c_size_t
+        fg.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_size_t]
+        m = fg(rec.ctypes.data, len(rec), lum, None, 0)
+        gb = ctypes.create_string_buffer(m + 1)
+        fg(rec.ctypes.data, len(rec), lum, gb, m + 1)
+        text += gb.value.decode()
     if a.legacy and not a.no_sphere_literals:      # the mode-2 module's sphere literals
         sph = np.ascontiguousarray(sc.aligned_spheres())
         fs = L.rvcp_internal_jit_sphere_source
