@@ -1082,7 +1082,7 @@ std::string code_key(const std::string &scan, const std::vector<std::string> &op
     if (rtc().version) (void)rtc().version(&maj, &mnr);
     std::string k = "rvcp code object\nhiprtc " + std::to_string(maj) + "." + std::to_string(mnr) + "\n";
     for (const std::string &o : opts) k += o + "\n";
-    for (const char *src : {kJitSrcKernels, kJitSrcInternal, kJitSrcAbi, kJitSrcSqrt, kJitSrcTonemap}) {
+    for (const char *src : {kJitSrcKernels, kJitSrcInternal, kJitSrcAbi, kJitSrcSqrt, kJitSrcTonemap, kJitSrcGroupPack}) {
         const std::string s(src);
         k += "src " + std::to_string(s.size()) + " " + std::to_string(fnv1a(s)) + "\n";
     }
@@ -1227,11 +1227,12 @@ int jit_compile_code(const std::string &scan, std::vector<char> &code, std::stri
         err = api.why;
         return -1;
     }
-    const char *hdr_src[] = {kJitSrcInternal, kJitSrcAbi, kJitSrcSqrt, kJitSrcTonemap, scan.c_str()};
+    const char *hdr_src[] = {kJitSrcInternal, kJitSrcAbi, kJitSrcSqrt, kJitSrcTonemap, kJitSrcGroupPack,
+                             scan.c_str()};
     const char *hdr_name[] = {"rvcp_internal.h", "../../include/rvcp.h", "rvcp_sqrt.h", "rvcp_tonemap.h",
-                              "rvcp_spec_scan.inc"};
+                              "rvcp_group_pack.h", "rvcp_spec_scan.inc"};
     rtc_program prog = nullptr;
-    if (api.create(&prog, kJitSrcKernels, "rvcp_kernels.hip", 5, hdr_src, hdr_name) != 0) {
+    if (api.create(&prog, kJitSrcKernels, "rvcp_kernels.hip", 6, hdr_src, hdr_name) != 0) {
         err = "hiprtcCreateProgram failed";
         return -1;
     }

@@ -66,6 +66,7 @@
 #include "../../include/rvcp.h"
 #include "rvcp_sqrt.h"
 #include "rvcp_tonemap.h"
+#include "rvcp_group_pack.h"
 
 // The build tag: a build other than the default one names its games101 kernels (the pre-pass too
 // in a map build) and its KernelBuild object (rvcp_internal.h) after its macros, so that the four
@@ -414,44 +415,74 @@ __device__ __forceinline__ bool spec_ray_ok(f3 o, f3 d) {
 }
 // After the always-set scan: every live ray of the wave (slot A: a_*, btA, no face kept; slot B:
 // b_*, btB, bestB) is tested against the groups it reaches, over [tmin, its bound].  A (ray,
-// group) pair is an item; items are numbered group by group (slot A's in lane order, then slot
-// B's), written to the wave's rows (origin + bound, direction + group: two float4 each, 64 a
-// pass), scanned one per lane -- a group at a time under the exec mask -- and their results read
-// back by the owners from the same rows and merged by the order-free rule of the tail partition
-// (smaller t, or equal t and larger face).  Passes of 64 while items remain.  Wave-local: wave
+// group) pair is an item; a group's items (slot A's in lane order, then slot B's) are contiguous
+// and the groups are laid out over passes of 64 by rvcp_group_pack.h, so that no pass holds part
+// of a group that fits a pass of its own: a pass costs one scan per group it holds.  An item is
+// written to the wave's rows (origin + bound, direction + group: two float4 each), scanned by the
+// lane of its index -- a group at a time under the exec mask, over the pass's prefix of occupied
+// lanes -- and its result read back by the owner from the same rows and merged by the order-free
+// rule of the tail partition (smaller t, or equal t and larger face).  The write and merge
+// blocks of a group that holds no item of the pass are skipped (wave-uniform).  Wave-local: wave
 // barriers and wavefront fences only, as the compact scan.
+// RVCP_GROUP_COUNT=k (debug builds of the specialised module only, as RVCP_REGION_CLOCK): per
+// wave, summed over the iterations that entered the item passes (their number in timeline
+// rec[7]), into rec[6]: 1 items, 2 passes, 3 group-scan executions, 4 iterations over 64 items.
+#ifdef RVCP_GROUP_COUNT
+#define RVCP_GC_PARAMS , unsigned long long &gc_sum, unsigned long long &gc_n
+#define RVCP_GC_ARGS , c_scan, c_iter
+#else
+#define RVCP_GC_PARAMS
+#define RVCP_GC_ARGS
+#endif
 __device__ __forceinline__ void spec_group_pass(float4 *rows, float tmin, bool hasA, f3 a_o, f3 a_d,
                                                 float &btA, bool hasB, f3 b_o, f3 b_d, float &btB,
-                                                int &bestB) {
+                                                int &bestB RVCP_GC_PARAMS) {
     const uint32_t rA = hasA ? spec_group_reach(a_o, a_d, tmin, btA) : 0u;
     const uint32_t rB = hasB ? spec_group_reach(b_o, b_d, tmin, btB) : 0u;
     if (__builtin_amdgcn_ballot_w64((rA | rB) != 0u) == 0ull) return;
-    uint64_t m[2 * RVCP_SPEC_GROUPS];
-    uint32_t base[2 * RVCP_SPEC_GROUPS], total = 0u;
+    // per lane, a byte per group: 0x80 | the item's index within its group, 0 for no item (the
+    // ballots are not held across the passes)
+    uint32_t cnt[RVCP_SPEC_GROUPS], start[RVCP_SPEC_GROUPS], iA = 0u, iB = 0u;
 #pragma unroll
     for (int g = 0; g < RVCP_SPEC_GROUPS; g++) {
-        m[2 * g] = __builtin_amdgcn_ballot_w64(((rA >> g) & 1u) != 0u);
-        base[2 * g] = total;
-        total += (uint32_t)__builtin_popcountll(m[2 * g]);
-        m[2 * g + 1] = __builtin_amdgcn_ballot_w64(((rB >> g) & 1u) != 0u);
-        base[2 * g + 1] = total;
-        total += (uint32_t)__builtin_popcountll(m[2 * g + 1]);
+        const uint64_t mA = __builtin_amdgcn_ballot_w64(((rA >> g) & 1u) != 0u);
+        const uint64_t mB = __builtin_amdgcn_ballot_w64(((rB >> g) & 1u) != 0u);
+        const uint32_t nA = (uint32_t)__builtin_popcountll(mA);
+        cnt[g] = nA + (uint32_t)__builtin_popcountll(mB);
+        if (((rA >> g) & 1u) != 0u) iA |= (0x80u | rvcp_group_pack_item(0u, nA, 0, rank_in(mA))) << (8 * g);
+        if (((rB >> g) & 1u) != 0u) iB |= (0x80u | rvcp_group_pack_item(0u, nA, 1, rank_in(mB))) << (8 * g);
     }
-    for (uint32_t p0 = 0u; p0 < total; p0 += (uint32_t)kWave) {
+    const uint32_t passes = rvcp_group_pack(cnt, RVCP_SPEC_GROUPS, start);
+#ifdef RVCP_GROUP_COUNT
+    {
+        uint32_t total = 0u, scans = 0u;
+        for (int g = 0; g < RVCP_SPEC_GROUPS; g++) {
+            total += cnt[g];
+            for (uint32_t p = 0u; p < passes; p++) scans += rvcp_group_pack_in_pass(cnt[g], start[g], p) ? 1u : 0u;
+        }
+        gc_sum += RVCP_GROUP_COUNT == 1 ? total : RVCP_GROUP_COUNT == 2 ? passes
+                : RVCP_GROUP_COUNT == 3 ? scans : (total > 64u ? 1u : 0u);
+        gc_n += 1ull;
+    }
+#endif
+    for (uint32_t p = 0u; p < passes; p++) {
+        const uint32_t p0 = p * (uint32_t)kWave;
         // (the rows are free: whatever read them before this pass has its values)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
         for (int g = 0; g < RVCP_SPEC_GROUPS; g++) {
+            if (!rvcp_group_pack_in_pass(cnt[g], start[g], p)) continue;        // wave-uniform
             // an item before this pass wraps to a huge j, one after it is >= kWave
-            const uint32_t jA = base[2 * g] + rank_in(m[2 * g]) - p0;
-            if (((rA >> g) & 1u) != 0u && jA < (uint32_t)kWave) {
+            const uint32_t eA = (iA >> (8 * g)) & 0xFFu, eB = (iB >> (8 * g)) & 0xFFu;
+            const uint32_t jA = (eA & 0x7Fu) + (start[g] - p0);
+            if ((eA & 0x80u) != 0u && jA < (uint32_t)kWave) {
                 rows[2 * jA] = make_float4(a_o.x, a_o.y, a_o.z, btA);
                 rows[2 * jA + 1] = make_float4(a_d.x, a_d.y, a_d.z, __int_as_float(g));
             }
-            const uint32_t jB = base[2 * g + 1] + rank_in(m[2 * g + 1]) - p0;
-            if (((rB >> g) & 1u) != 0u && jB < (uint32_t)kWave) {
+            const uint32_t jB = (eB & 0x7Fu) + (start[g] - p0);
+            if ((eB & 0x80u) != 0u && jB < (uint32_t)kWave) {
                 rows[2 * jB] = make_float4(b_o.x, b_o.y, b_o.z, btB);
                 rows[2 * jB + 1] = make_float4(b_d.x, b_d.y, b_d.z, __int_as_float(g));
             }
@@ -463,7 +494,9 @@ __device__ __forceinline__ void spec_group_pass(float4 *rows, float tmin, bool h
         const float4 ro = rows[2 * lane_r], rd = rows[2 * lane_r + 1];
         float bt = ro.w;
         int best = -1;
-        if (lane_r < total - p0)        // (the lanes past the items hold stale rows)
+        // (the lanes past the pass's prefix hold stale rows; the group word of the row selects
+        // the scan -- a scan whose group the pass does not hold is skipped with an empty exec)
+        if (lane_r < rvcp_group_pack_lanes(cnt, start, RVCP_SPEC_GROUPS, p))
             spec_group_scan(__float_as_int(rd.w), mk(ro.x, ro.y, ro.z), mk(rd.x, rd.y, rd.z), tmin, bt, best);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -474,13 +507,15 @@ __device__ __forceinline__ void spec_group_pass(float4 *rows, float tmin, bool h
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
         for (int g = 0; g < RVCP_SPEC_GROUPS; g++) {
-            const uint32_t jA = base[2 * g] + rank_in(m[2 * g]) - p0;
-            if (((rA >> g) & 1u) != 0u && jA < (uint32_t)kWave) {
+            if (!rvcp_group_pack_in_pass(cnt[g], start[g], p)) continue;        // wave-uniform
+            const uint32_t eA = (iA >> (8 * g)) & 0xFFu, eB = (iB >> (8 * g)) & 0xFFu;
+            const uint32_t jA = (eA & 0x7Fu) + (start[g] - p0);
+            if ((eA & 0x80u) != 0u && jA < (uint32_t)kWave) {
                 const float4 r = rows[2 * jA];
                 if (__float_as_int(r.y) >= 0 && r.x < btA) btA = r.x;     // slot A keeps no face
             }
-            const uint32_t jB = base[2 * g + 1] + rank_in(m[2 * g + 1]) - p0;
-            if (((rB >> g) & 1u) != 0u && jB < (uint32_t)kWave) {
+            const uint32_t jB = (eB & 0x7Fu) + (start[g] - p0);
+            if ((eB & 0x80u) != 0u && jB < (uint32_t)kWave) {
                 const float4 r = rows[2 * jB];
                 const int ob = __float_as_int(r.y);
                 if (ob >= 0 && (r.x < btB || (r.x == btB && ob > bestB))) { btB = r.x; bestB = ob; }
@@ -3095,7 +3130,7 @@ __device__ __forceinline__ void path_body(
             if (!__any(lane_r < nr && !spec_ray_ok(o, d))) {
                 spec_always1(o, d, A.t_min, bt, best);
                 float no_bt = -1.0f;
-                spec_group_pass(rows, A.t_min, false, o, d, no_bt, lane_r < nr, o, d, bt, best);
+                spec_group_pass(rows, A.t_min, false, o, d, no_bt, lane_r < nr, o, d, bt, best RVCP_GC_ARGS);
             } else
 #elif defined(RVCP_SPEC_SCAN)
             if (!__any(lane_r < nr && !ray_in_range(o, d))) {
@@ -3133,7 +3168,7 @@ __device__ __forceinline__ void path_body(
                 if (!hasA) btA = -1.0f;
                 spec_always2(a_o, a_d, b_o, b_d, A.t_min, btA, btB, bestB);
                 spec_group_pass(compact_lds + wv * (2 * kWave), A.t_min, hasA, a_o, a_d, btA, hasB,
-                                b_o, b_d, btB, bestB);
+                                b_o, b_d, btB, bestB RVCP_GC_ARGS);
             } else
 #elif defined(RVCP_SPEC_SCAN)
             if (!__any((hasA && !ray_in_range(a_o, a_d)) || (hasB && !ray_in_range(b_o, b_d)))) {

@@ -21,11 +21,14 @@ def main():
     ap.add_argument("--tris", type=int, default=0)
     ap.add_argument("--integrator", type=int, default=0)
     ap.add_argument("--accel", type=int, default=0)
-    ap.add_argument("--scene", default="cornell", choices=["cornell", "spheres"])
+    ap.add_argument("--scene", default="cornell", choices=["cornell", "rotated", "spheres"],
+                    help="rotated: scene.rotated_scene of the Cornell box (the bench's c3rot)")
     ap.add_argument("--generic", action="store_true", help="specialize = OFF (generic scan)")
     ap.add_argument("--grid", type=int, default=0, help="rvcp_config_t.grid_waves_per_simd (0: full)")
     a = ap.parse_args()
-    sc = rvcp_amd.Scene.default() if a.scene == "cornell" else rvcp_amd.scene.sphere_scene()
+    sc = rvcp_amd.scene.sphere_scene() if a.scene == "spheres" else rvcp_amd.Scene.default()
+    if a.scene == "rotated":
+        sc = rvcp_amd.scene.rotated_scene(sc)
     if a.tris:
         sc = rvcp_amd.scene.with_random_triangles(sc, a.tris)
     with rvcp_amd.RayTracer(spp=a.spp, kernel_variant=a.variant, integrator=a.integrator,

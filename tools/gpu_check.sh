@@ -96,6 +96,10 @@ for s in $STEPS; do
         valupmc) run valupmc 180 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d "$OUT/valupmc_$TAG" -o run --output-format csv -- tools/build/valu_rate ;;
         tlc3) tl tlc3 40 ;;
         tlreg) for k in 1 2 3 4 5; do run tlreg$k 300 bash -c "rm -f /tmp/tl_reg.bin && RVCP_LIB=$DBG RVCP_JIT_FLAGS=-DRVCP_REGION_CLOCK=$k RVCP_DEBUG_TIMELINE=/tmp/tl_reg.bin python tools/frames.py --frames 6 $TLARGS && python tools/timeline.py /tmp/tl_reg.bin --waves \$(python -c 'import os; print(os.path.getsize(\"/tmp/tl_reg.bin\") // 64 // 6)')"; done ;;
+        # the grouped scan's item statistics (RVCP_GROUP_COUNT=k: 1 items, 2 passes, 3 group scans,
+        # 4 iterations over 64 items); GCEXTRA=,-DRVCP_GROUP_PACK_CONTIGUOUS: the unpadded numbering;
+        # GCNAME names the logs (the scene of TLARGS, the numbering)
+        grpcount) for k in 1 2 3 4; do run grpcount${GCNAME:-}_$k 300 bash -c "rm -f /tmp/tl_gc.bin && RVCP_LIB=$DBG RVCP_JIT_FLAGS=-DRVCP_GROUP_COUNT=$k${GCEXTRA:-} RVCP_DEBUG_TIMELINE=/tmp/tl_gc.bin python tools/frames.py --frames 3 $TLARGS && python tools/timeline.py /tmp/tl_gc.bin --group-count $k --waves \$(python -c 'import os; print(os.path.getsize(\"/tmp/tl_gc.bin\") // 64 // 3)')"; done ;;
         tlc2) tl tlc2 40 --size 384 --spp 10 ;;
         rehearse2) run rehearse2 300 env RVCP_BENCH_REHEARSAL=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 bench.py --full --gpus 2 --steps 5 --warmup 1 ;;
         frames) run frames 300 python tools/frames.py --frames 20 ;;
